@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - sampled-nodes/sec of the PC-GNN train step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload yelp|amazon|powerlaw]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload yelp|amazon|powerlaw] [--full] [--dump-outputs DIR]
 
 A "step" is one mini-batch through the whole hot path: label-aware scoring,
 train-pos sort, choose + aggregate, dense tail, loss, backward, Adam - the
@@ -26,8 +26,17 @@ bracket each.  Those events give the `roofline` object (dominant call = select_r
 gather_train_kernel: selection, gather, the next step's score pass, the deferred Adam update; bytes:
 algorithmic_bytes()).  N>1: the destination-node partitioned path (pc-gnn_amd/dist.py), weak scaling.
 
-Prints ONE JSON line (rank 0) with `roofline` and `cpu_baseline` (the oracle port timed
-on the host cores on the event-bracketed batches of the same run; rank 0, N=1 only).
+Prints ONE JSON line (rank 0): `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall time of the timed
+region / --steps) and the run's configuration.  A plain run does only that: set-up, warm-up, the timed steps, the outputs
+(--dump-outputs) and the line.  --full adds what takes work of its own after the clock has stopped: `roofline` (with the
+post-region brackets), `epoch_report`, `verified` (the selection lists checked against the oracle) and `cpu_baseline` (the
+oracle port timed on the host cores on the event-bracketed batches of the same run; rank 0, N=1 only).  The timed region is the
+same in both: its event brackets are part of it either way.
+
+--dump-outputs DIR: right after the timed region (before anything --full adds), what the timed path computed in its last step -
+the trained parameters (`param.<state-dict name>.npy`, or the flat parameter buffer `theta.npy` on the partitioned path), the
+last batch's loss (`loss.npy`, fused engines: also its per-row losses `row_loss.npy`) - as float32 .npy files (rank 0).  Inputs
+are seeded (--seed): the same arguments give the same graph, initial weights and batches.
 """
 import argparse
 import json
@@ -79,6 +88,11 @@ def parse():
                     "(the timed region itself brackets one batch every --event-every groups of epochs); 0 = none")
     ap.add_argument("--verify-batches", type=int, default=1, help="batches whose chosen sets are checked after the clock stops "
                     "(count law on every row, the oracle's sets on a strided sample); 0 = skip")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: roofline "
+                    "(+ --post-brackets), epoch_report (--report-epochs), verified (--verify-batches), cpu_baseline (--cpu-batches); "
+                    "those options only act with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step "
+                    "(parameters, loss) to DIR/<name>.npy")
     ap.add_argument("--engine", default=None, choices=["graph", "fused", "torch", "dp"],
                     help="graph: fused HIP step replayed from a hipGraph (default at 1 GPU); fused: same kernels "
                          "launched eagerly (default at N>1, gradient all-reduce in between); torch: torch dense tail")
@@ -266,6 +280,80 @@ def verify_lists(w, tr, cfg, ids, sets, cnt_h, s0_dev, stride):
                    "data part read back), against the scores that launch selected by (copied before it)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64 kept, anything else as float64)."""
+    host = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
+        host[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def step_outputs(tr, last_loss):
+    """What a caller of the timed path holds after its last step: the trained parameters (every deferred update applied) and
+    the last batch's loss - fused engines: from the engine's per-row loss buffer; torch engine: the loss it returned."""
+    out = {}
+    if tr.fused is not None:
+        fz = tr.fused
+        out["loss"] = fz.last_loss().reshape(1)
+        out["row_loss"] = fz.row_loss[:fz._lastB]
+    else:
+        out["loss"] = last_loss.detach().reshape(1)
+    for name, p in tr.model.named_parameters():
+        if p.requires_grad:
+            out["param." + name] = p.detach()
+    return out
+
+
+def partitioned_roofline(args, d, prof):
+    """--full, N > 1 (or --force-partitioned): the `roofline` object of rank 0's step graph from the windows it ran step by step"""
+    # roofline of this path's one launch per step - the captured graph (score pass over the rank's table, plan, train-pos
+    # sort, select, look-up, gather, dense step, slab sum) - on rank 0: the select + gather bytes of algorithmic_bytes()
+    # plus the score pass's table stream
+    ms, ab = [], []
+    g = d.g
+    for e0, e1, ids_l, cnt in prof:
+        ms.append(e0.elapsed_time(e1))
+        ids_h = ids_l.cpu().numpy().astype(np.int64)
+        # (SURVEY 8(d)'s U x F: the feature rows of the batch's unique nodes - centres and every neighbour, counted from this
+        #  rank's CSR rows by global id - read once for scoring; not the whole extended table the rank's score pass streams)
+        glob = [ids_h + d.part.lo] + [idx[ip[v]:ip[v + 1]] for ip, idx in d.csr_host for v in np.unique(ids_h)]
+        U = int(np.unique(np.concatenate(glob)).size)
+        ab.append(algorithmic_bytes(g, ids_h, cnt.view(g.R, -1).cpu().numpy()) + U * (4 * g.feat_dim + 4))
+    avg_ms = float(np.mean(ms)) if ms else float("nan")
+    achieved = float(np.mean(ab)) / (avg_ms * 1e-3) / 1e9 if ms else float("nan")
+    # HBM-side bytes of the step graph's kernels from two PMC passes of this command at world size 1 (profiles/pmc_traffic.json)
+    traffic, traffic_commit = None, None
+    try:
+        # (collected at world size 1: a rank's step graph does the same work at any world size but for the share of remote rows)
+        tkey = f"{args.workload}_partitioned_w1" if (args.batch_size in (0, None, 1024) and args.emb == 64 and args.workload == "yelp") else None
+        entry = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json"))).get(tkey, {}) if tkey else {}
+        traffic, traffic_commit = entry.get("choose_agg_bytes_per_launch"), entry.get("commit")
+    except Exception:
+        traffic, traffic_commit = None, None
+    roofline = {"bound": "hbm", "kernel": "the step graph of rank 0: front (Adam from the all-reduced gradient || train-pos keys || score "
+                                          "pass over owned + train-pos + halo rows), select_rows (sorts the keys), gather_chunks_dist "
+                                          "(translates node ids to table rows as it reads the lists), dense_step (transposed activations, "
+                                          "no slabs), wgrad (weight-gradient GEMMs over the batch)"
+                                          + (", the gradient all-reduce (captured in the graph)" if d.collectives_in_graph else "")
+                                          + ": one launch per step; bytes = select + gather + U x F scored rows (U = the batch's unique nodes)",
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "traffic_note": (f"profiles/pmc_traffic.json: two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of the world-size-1 step graph's "
+                                 f"kernels at commit {traffic_commit} (rank 0's step graph at world size 1)") if traffic is not None else
+                                "no PMC pass of this partitioned configuration has been collected (profiles/): null",
+                "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": float(np.mean(ab)) if ab else None,
+                "launches_timed": len(ms)}
+    return roofline
+
+
 def run_partitioned(args, w, B, lr, wd, dev, dist, world, rank):
     """N > 1: destination-node partition, RCCL all-to-all of remote neighbour rows (once per window of steps) +
     gradient all-reduce (pc-gnn_amd/dist.py).  Weak scaling: every rank trains batches of B centres it owns."""
@@ -327,6 +415,8 @@ def _run_partitioned(args, w, B, d, dev, dist, world, rank, W, gloo):
     if os.environ.get("PCG_BENCH_DEBUG"):
         print(f"[debug] enqueue {ta - t0:.4f} flush {tb - ta:.4f} sync {tc - tb:.4f} barrier {t0 + elapsed - tc:.4f}", file=sys.stderr)
     d.check()                               # raises on every rank if any rank's exchange / lists went over capacity
+    if args.dump_outputs and rank == 0:     # the flat parameter buffer (every update applied) and the last step's per-row losses
+        dump_outputs(args.dump_outputs, {"theta": d.theta, "row_loss": d.row_loss})
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     fr, seen = d.feature_rows, d.halo.max_seen
     # rows a step's exchange moves per rank: the fixed-pitch buffers (what the all-to-alls carry) and the rows really asked for
@@ -345,42 +435,7 @@ def _run_partitioned(args, w, B, d, dev, dist, world, rank, W, gloo):
     nodes_total = args.steps * B * world
     if rank == 0:
         hr, rm, en = (float(x) / world for x in stats.tolist())
-        # roofline of this path's one launch per step - the captured graph (score pass over the rank's table, plan, train-pos
-        # sort, select, look-up, gather, dense step, slab sum) - on rank 0: the select + gather bytes of algorithmic_bytes()
-        # plus the score pass's table stream
-        ms, ab = [], []
-        g = d.g
-        for e0, e1, ids_l, cnt in prof:
-            ms.append(e0.elapsed_time(e1))
-            ids_h = ids_l.cpu().numpy().astype(np.int64)
-            # (SURVEY 8(d)'s U x F: the feature rows of the batch's unique nodes - centres and every neighbour, counted from this
-            #  rank's CSR rows by global id - read once for scoring; not the whole extended table the rank's score pass streams)
-            glob = [ids_h + d.part.lo] + [idx[ip[v]:ip[v + 1]] for ip, idx in d.csr_host for v in np.unique(ids_h)]
-            U = int(np.unique(np.concatenate(glob)).size)
-            ab.append(algorithmic_bytes(g, ids_h, cnt.view(g.R, -1).cpu().numpy()) + U * (4 * g.feat_dim + 4))
-        avg_ms = float(np.mean(ms)) if ms else float("nan")
-        achieved = float(np.mean(ab)) / (avg_ms * 1e-3) / 1e9 if ms else float("nan")
-        # HBM-side bytes of the step graph's kernels from two PMC passes of this command at world size 1 (profiles/pmc_traffic.json)
-        traffic, traffic_commit = None, None
-        try:
-            # (collected at world size 1: a rank's step graph does the same work at any world size but for the share of remote rows)
-            tkey = f"{args.workload}_partitioned_w1" if (args.batch_size in (0, None, 1024) and args.emb == 64 and args.workload == "yelp") else None
-            entry = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json"))).get(tkey, {}) if tkey else {}
-            traffic, traffic_commit = entry.get("choose_agg_bytes_per_launch"), entry.get("commit")
-        except Exception:
-            traffic, traffic_commit = None, None
-        roofline = {"bound": "hbm", "kernel": "the step graph of rank 0: front (Adam from the all-reduced gradient || train-pos keys || score "
-                                              "pass over owned + train-pos + halo rows), select_rows (sorts the keys), gather_chunks_dist "
-                                              "(translates node ids to table rows as it reads the lists), dense_step (transposed activations, "
-                                              "no slabs), wgrad (weight-gradient GEMMs over the batch)"
-                                              + (", the gradient all-reduce (captured in the graph)" if d.collectives_in_graph else "")
-                                              + ": one launch per step; bytes = select + gather + U x F scored rows (U = the batch's unique nodes)",
-                    "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                    "traffic_note": (f"profiles/pmc_traffic.json: two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of the world-size-1 step graph's "
-                                     f"kernels at commit {traffic_commit} (rank 0's step graph at world size 1)") if traffic is not None else
-                                    "no PMC pass of this partitioned configuration has been collected (profiles/): null",
-                    "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": float(np.mean(ab)) if ab else None,
-                    "launches_timed": len(ms)}
+        roofline = partitioned_roofline(args, d, prof) if args.full else None
         out = {
             "metric": "sampled-nodes/sec", "value": nodes_total / elapsed, "unit": "nodes/s",
             "n_gpus": world, "steps": args.steps, "warmup": warmup, "warmup_requested": args.warmup,
@@ -402,8 +457,9 @@ def _run_partitioned(args, w, B, d, dev, dist, world, rank, W, gloo):
                        "feature_rows_per_rank_max": {"owned+train_pos+halo": int(mem[0].item()), "halo_capacity": int(mem[2].item()),
                                                      "halo_pitch": int(mem[4].item()), "rows_from_one_owner_max_seen": int(mem[3].item()),
                                                      "halo_rows_max_seen": int(mem[1].item()), "unpartitioned_table": int(n_nodes)}},
-            "roofline": roofline,
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         print(json.dumps(out), flush=True)
 
 
@@ -435,6 +491,46 @@ def dry_run(world, rank):
     if rank == 0:
         print(json.dumps({"dry_run": True, "n_gpus": world, "ranks_seen": int(t.item())}))
     dist.destroy_process_group()
+
+
+def single_roofline(args, tr, w, B, default_b, events, post_ev, used_ev, post_used):
+    """--full, one process per GPU (not partitioned): the `roofline` object from the event-bracketed launches of the timed region
+    and of the post-region brackets; also hands back the bracketed batches (the CPU baseline's sample)."""
+    n_in_region = len(events)
+    events = list(events) + list(post_ev)
+    used_ev = list(used_ev) + list(post_used)
+    kern_ms = [a.elapsed_time(b) for a, b in events]
+    batches_host = [i.cpu().numpy().astype(np.int64) for i, _ in used_ev]   # the event-bracketed batches: the CPU sample
+    # (the score rider's term is SURVEY 8(d)'s U x F - the unique_nodes of the bracketed batch, counted from the host CSR -
+    #  whether the engine scores the whole table or only the rows the next batch marks)
+    riders = None
+    if tr.fused is not None:
+        riders = dict(csr=w.csr, n_nodes=w.n, n_pos=tr.graph.n_pos, n_params=tr.fused.n_params)
+    abytes = [algorithmic_bytes(tr.graph, i.cpu().numpy().astype(np.int64), c.cpu().numpy(), riders) for i, c in used_ev]
+    avg_ms = float(np.mean(kern_ms))
+    achieved = float(np.mean(abytes)) / (avg_ms * 1e-3) / 1e9
+    traffic, traffic_commit = None, None
+    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(tpath):
+        try:
+            # the PMC passes were run on one batch size per workload: yelp 1024, amazon 256 (their defaults)
+            tkey = (f"powerlaw_{args.nodes}_{args.edges}_b{B}" if args.workload == "powerlaw"
+                    else args.workload if B == default_b else f"{args.workload}_b{B}")
+            entry = json.load(open(tpath)).get(tkey, {})
+            traffic, traffic_commit = entry.get("choose_agg_bytes_per_launch"), entry.get("commit")
+        except Exception:
+            traffic, traffic_commit = None, None
+    roofline = {"bound": "hbm", "kernel": "pcg_choose_gather_train: select_rows (sorts the train positives, steps the label classifier for this batch) + gather_train_kernel (gather || the other parameters' deferred Adam update || the NEXT step's score pass and train-pos keys); the plan is made per epoch beside the sampler, multi-chunk sums are finished in the dense kernel's prologue; bytes = select + gather + U x F feature rows scored + optimizer state (algorithmic_bytes)", "achieved": achieved,
+                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "traffic_from": ("profiles/pmc_traffic.json: two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of this command at commit "
+                                 f"{traffic_commit}") if traffic is not None else None,
+                "avg_launch_ms": avg_ms, "min_launch_ms": float(np.min(kern_ms)), "max_launch_ms": float(np.max(kern_ms)),
+                "algorithmic_bytes_per_launch": float(np.mean(abytes)),
+                "launches_timed": len(kern_ms), "launches_timed_inside_the_timed_region": n_in_region,
+                "launches_how": "HIP events around the call's two kernels; the timed region brackets the first batch of its "
+                                "second group of epochs (its only one, if there is but one) and of every --event-every-th after it, --post-brackets further epochs "
+                                "after the clock has stopped add one bracket each (same launches, same graphs around them)"}
+    return roofline, batches_host
 
 
 def main():
@@ -506,6 +602,7 @@ def main():
             loss = tr.model.loss(ids, labels)
             if dist is not None:
                 loss = loss / world
+            state["loss"] = loss
             loss.backward()
             if dist is not None:
                 flat = torch.cat([p.grad.reshape(-1) for p in params])
@@ -520,7 +617,7 @@ def main():
         else:
             tr.fused.train_step(ids, tr.labels_i32[ids.long()], allreduce=allreduce)
 
-    state = {"epoch": 0, "ids": None, "b": 0}
+    state = {"epoch": 0, "ids": None, "b": 0, "loss": None}
     nb = tr.batches_per_epoch()
     epoch_graphs = engine == "graph" and dist is None and not args.no_epoch_graphs   # ids/labels of whole epochs in static buffers, 1 launch per group of epochs
 
@@ -619,9 +716,11 @@ def main():
     if tr.fused is not None:
         tr.fused.check()
         status_clean = True
-    report = epoch_report(tr, args.report_epochs) if (epoch_graphs and args.report_epochs > 0 and rank == 0) else None
+    if args.dump_outputs and rank == 0:               # before anything --full runs moves the state on
+        dump_outputs(args.dump_outputs, step_outputs(tr, state["loss"]))
+    report = epoch_report(tr, args.report_epochs) if (args.full and epoch_graphs and args.report_epochs > 0 and rank == 0) else None
     post_ev, post_used, verified = [], [], None
-    if epoch_graphs and rank == 0 and (args.post_brackets > 0 or args.verify_batches > 0):
+    if args.full and epoch_graphs and rank == 0 and (args.post_brackets > 0 or args.verify_batches > 0):
         post_ev, post_used, verified = post_region_brackets(w, tr, cfg, args.post_brackets, args.verify_batches > 0)
 
     nodes_local = counted["nodes"]
@@ -633,30 +732,6 @@ def main():
     elapsed, nodes_total = float(t.item()), float(n.item())
 
     if rank == 0:
-        n_in_region = len(events)
-        events = list(events) + list(post_ev)
-        used_ev = list(used_ev) + list(post_used)
-        kern_ms = [a.elapsed_time(b) for a, b in events]
-        batches_host = [i.cpu().numpy().astype(np.int64) for i, _ in used_ev]   # the event-bracketed batches: the CPU sample
-        # (the score rider's term is SURVEY 8(d)'s U x F - the unique_nodes of the bracketed batch, counted from the host CSR -
-        #  whether the engine scores the whole table or only the rows the next batch marks)
-        riders = None
-        if tr.fused is not None:
-            riders = dict(csr=w.csr, n_nodes=w.n, n_pos=tr.graph.n_pos, n_params=tr.fused.n_params)
-        abytes = [algorithmic_bytes(tr.graph, i.cpu().numpy().astype(np.int64), c.cpu().numpy(), riders) for i, c in used_ev]
-        avg_ms = float(np.mean(kern_ms))
-        achieved = float(np.mean(abytes)) / (avg_ms * 1e-3) / 1e9
-        traffic, traffic_commit = None, None
-        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tpath):
-            try:
-                # the PMC passes were run on one batch size per workload: yelp 1024, amazon 256 (their defaults)
-                tkey = (f"powerlaw_{args.nodes}_{args.edges}_b{B}" if args.workload == "powerlaw"
-                        else args.workload if B == default_b else f"{args.workload}_b{B}")
-                entry = json.load(open(tpath)).get(tkey, {})
-                traffic, traffic_commit = entry.get("choose_agg_bytes_per_launch"), entry.get("commit")
-            except Exception:
-                traffic, traffic_commit = None, None
         out = {
             "metric": "sampled-nodes/sec", "value": nodes_total / elapsed, "unit": "nodes/s",
             "n_gpus": world, "steps": args.steps, "warmup": warmup, "warmup_requested": args.warmup,
@@ -673,31 +748,23 @@ def main():
                        "global_batch": B * world, "parallelism": "single" if world == 1 else f"dp{world}-replicated-graph",
                        "engine": engine, "epochs_per_launch": K if epoch_graphs else None,
                        "nodes_processed": int(nodes_total)},
-            "roofline": {"bound": "hbm", "kernel": "pcg_choose_gather_train: select_rows (sorts the train positives, steps the label classifier for this batch) + gather_train_kernel (gather || the other parameters' deferred Adam update || the NEXT step's score pass and train-pos keys); the plan is made per epoch beside the sampler, multi-chunk sums are finished in the dense kernel's prologue; bytes = select + gather + U x F feature rows scored + optimizer state (algorithmic_bytes)", "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_from": ("profiles/pmc_traffic.json: two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of this command at commit "
-                                          f"{traffic_commit}") if traffic is not None else None,
-                         "avg_launch_ms": avg_ms, "min_launch_ms": float(np.min(kern_ms)), "max_launch_ms": float(np.max(kern_ms)),
-                         "algorithmic_bytes_per_launch": float(np.mean(abytes)),
-                         "launches_timed": len(kern_ms), "launches_timed_inside_the_timed_region": n_in_region,
-                         "launches_how": "HIP events around the call's two kernels; the timed region brackets the first batch of its "
-                                         "second group of epochs (its only one, if there is but one) and of every --event-every-th after it, --post-brackets further epochs "
-                                         "after the clock has stopped add one bracket each (same launches, same graphs around them)"},
         }
-        if report is not None:
-            out["epoch_report"] = report
-        if verified is not None:
-            out["verified"] = verified
-        if world == 1 and args.cpu_batches > 0:
-            # the CPU sample: the event-bracketed batches of the run, topped up with further epochs of the same sampler (same
-            # weights, same batch size) when a short run has bracketed fewer than --cpu-batches
-            ep = 1 << 20
-            while len(batches_host) < args.cpu_batches:
-                extra = tr.start_epoch(ep).cpu().numpy().astype(np.int64)
-                batches_host += [extra[i:i + B] for i in range(0, len(extra), B)]
-                ep += 1
-            out["cpu_baseline"] = cpu_baseline(w, tr, cfg, batches_host, args.cpu_batches)
-            out["speedup_vs_cpu_port"] = out["value"] / out["cpu_baseline"]["value"]
+        if args.full:
+            out["roofline"], batches_host = single_roofline(args, tr, w, B, default_b, events, post_ev, used_ev, post_used)
+            if report is not None:
+                out["epoch_report"] = report
+            if verified is not None:
+                out["verified"] = verified
+            if world == 1 and args.cpu_batches > 0:
+                # the CPU sample: the event-bracketed batches of the run, topped up with further epochs of the same sampler (same
+                # weights, same batch size) when a short run has bracketed fewer than --cpu-batches
+                ep = 1 << 20
+                while len(batches_host) < args.cpu_batches:
+                    extra = tr.start_epoch(ep).cpu().numpy().astype(np.int64)
+                    batches_host += [extra[i:i + B] for i in range(0, len(extra), B)]
+                    ep += 1
+                out["cpu_baseline"] = cpu_baseline(w, tr, cfg, batches_host, args.cpu_batches)
+                out["speedup_vs_cpu_port"] = out["value"] / out["cpu_baseline"]["value"]
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -221,6 +221,36 @@ def test_bench_algorithmic_bytes_counts_the_riders_once():
     assert by_csr == bench.algorithmic_bytes(g, ids, counts, dict(table_rows=4, n_pos=7, n_params=50))
 
 
+def test_bench_options_and_dump_outputs(tmp_path, monkeypatch):
+    """bench.py: --full and --dump-outputs are off by default; dump_outputs writes one DIR/<name>.npy per array (float32 / float64
+    kept, anything else as float64) and refuses more than 64 MB in all before it writes anything."""
+    import importlib.util
+    import os
+    import sys
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    a = bench.parse()
+    assert a.steps == 7 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path / "o")])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path / "o")
+
+    w = torch.arange(6, dtype=torch.float32).view(2, 3)
+    bench.dump_outputs(str(tmp_path / "o"), {"param.w": w, "loss": np.array([0.25]), "counts": np.array([1, 2], dtype=np.int32)})
+    assert sorted(os.listdir(tmp_path / "o")) == ["counts.npy", "loss.npy", "param.w.npy"]
+    got = np.load(tmp_path / "o" / "param.w.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, w.numpy())
+    assert np.load(tmp_path / "o" / "loss.npy").dtype == np.float64
+    c = np.load(tmp_path / "o" / "counts.npy")
+    assert c.dtype == np.float64 and c.tolist() == [1.0, 2.0]
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((64 << 20) // 4 + 1, dtype=np.float32)})
+    assert not (tmp_path / "big").exists()
+
+
 def test_relabel_by_degree_is_the_same_graph():
     """synth.relabel_by_degree (bench.py --relabel-by-degree, a diagnostic): the graph renumbered by descending total degree is
     isomorphic to the original - same edges under the permutation, rows ascending in the new ids, features / labels / training
