@@ -283,6 +283,40 @@ int pcg_choose_gather_train(const pcg_graph_desc *g, const int32_t *nodes, const
                             const float *slabs, const int32_t *step_counter, float lambda_1, float inv_count, double lr, double beta1,
                             double beta2, double eps, double weight_decay, int32_t score_next, const uint8_t *next_touched,
                             const float *acts, int32_t act_ld, float *wg_scratch, int32_t keys_sorted, void *stream);
+/* The same two launches one at a time, for the pipelined step (pcg_dense_select_train): part 1 = the select launch only (clf_out,
+ * if not NULL, gets a copy of the classifier's in-value [2 * feat_dim + 2] beside theta's - the dense tiles of a fused launch
+ * read it from there), part 2 = the gather launch only (+ the sort of the next step's keys where that is a launch of its own).
+ * Arguments otherwise as pcg_choose_gather_train's; the weight-gradient workgroups always ride in the gather launch. */
+int pcg_choose_train_part(int32_t part, const pcg_graph_desc *g, const int32_t *nodes, const int32_t *labels, int32_t B, float *s0,
+                          uint64_t *pos_keys, const double *thresholds, const double *rho, int32_t add_self, float *agg,
+                          int32_t agg_stride, int32_t *cnt, void *workspace, const void *plan, int64_t list_capacity,
+                          uint32_t *status, uint32_t *sync_words, float *theta, float *m, float *v, int32_t emb, float *clf_next,
+                          const float *slabs, const int32_t *step_counter, float lambda_1, float inv_count, double lr, double beta1,
+                          double beta2, double eps, double weight_decay, int32_t score_next, const uint8_t *next_touched,
+                          const float *acts, int32_t act_ld, float *wg_scratch, int32_t keys_sorted, float *clf_out, void *stream);
+/* The pipelined training step.  Batch t + 1's selection needs nothing batch t's dense tiles compute, so a sequence of steps
+ * runs as
+ *     pcg_choose_train_part(1, batch 0, clf_out = slot 0)
+ *     for t:  pcg_choose_train_part(2, batch t)                   gather || Adam of t - 1 || scores + keys of t + 1
+ *             pcg_dense_select_train(batch t, batch t + 1)        dense tiles of t || select of t + 1 (classifier step, key sort)
+ *     last:   pcg_choose_train_part(2, last), pcg_train_dense(adam_clf = 3, last)
+ * and leaves bit for bit what pcg_choose_gather_train + pcg_train_dense(adam_clf = 3) per step leave.  The fused launch: batch
+ * t's tiles as pcg_train_dense(adam_clf = 3) (no key sort; the step is counted by the select half's classifier workgroup; the
+ * label classifier read from clf_in = the slot batch t's select filled), batch t + 1's select as pcg_choose_train_part(1) with
+ * unsorted keys (sorted inside the launch) and clf_out = the other slot.  cnt / next_cnt: two different buffers.
+ * PCG_E_UNSUPPORTED where pcg_dense_select_blocks(g, emb, B) is 0. */
+int pcg_dense_select_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
+                           const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt, const void *plan,
+                           float inv_count, const float *clf_in, float *logits, float *center, float *row_loss, float *acts,
+                           int32_t act_ld, const int32_t *next_ids, const int32_t *next_labels, int32_t next_B, int32_t *next_cnt,
+                           const void *next_plan, float next_inv_count, float *clf_out, float *s0, uint64_t *pos_keys,
+                           const double *thresholds, const double *rho, int32_t add_self, void *workspace, int64_t list_capacity,
+                           uint32_t *status, uint32_t *sync_words, float *clf_next, const float *slabs, int32_t *step_counter,
+                           float lambda_1, double lr, double beta1, double beta2, double eps, double weight_decay, void *stream);
+/* select workgroups of the fused launch for a dense batch of B rows (on the current device), or 0: that batch's steps keep three
+ * launches (more than PCG_PIPE_MAX_TILES = 128 tiles of 16 rows by default, rows beyond the select kernel's LDS keys, feature
+ * rows of more than 256 floats, a dense shape that does not fit). */
+int32_t pcg_dense_select_blocks(const pcg_graph_desc *g, int32_t emb, int32_t B);
 int32_t pcg_sync_words_count(void);                 /* uint32 words of a `sync_words` buffer (zero-initialised ONCE by the caller; the
                                                         kernels leave every word but [1], [2] zero between launches) */
 int pcg_aggregate_lists_planned(const float *X, int32_t feat_dim, int32_t feat_stride, int64_t table_rows, int32_t n_rows,

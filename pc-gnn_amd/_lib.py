@@ -65,6 +65,13 @@ PROTOTYPES = {
     "pcg_choose_gather_train": (C.c_int, [_G, _P, _P, _I32, _P, _P, C.POINTER(_F64), C.POINTER(_F64), _I32, _P, _I32, _P, _P, _P,
                                           _I64, _P, _P, _P, _P, _P, _I32, _P, _P, _P, C.c_float, C.c_float, _F64, _F64, _F64, _F64,
                                           _F64, _I32, _P, _P, _I32, _P, _I32, _P]),
+    "pcg_choose_train_part": (C.c_int, [_I32, _G, _P, _P, _I32, _P, _P, C.POINTER(_F64), C.POINTER(_F64), _I32, _P, _I32, _P, _P, _P,
+                                        _I64, _P, _P, _P, _P, _P, _I32, _P, _P, _P, C.c_float, C.c_float, _F64, _F64, _F64, _F64,
+                                        _F64, _I32, _P, _P, _I32, _P, _I32, _P, _P]),
+    "pcg_dense_select_train": (C.c_int, [_G, _P, _P, _P, _I32, _P, _P, _I32, _P, _I32, _P, _P, C.c_float, _P, _P, _P, _P, _P, _I32,
+                                         _P, _P, _I32, _P, _P, C.c_float, _P, _P, _P, C.POINTER(_F64), C.POINTER(_F64), _I32, _P,
+                                         _I64, _P, _P, _P, _P, _P, C.c_float, _F64, _F64, _F64, _F64, _F64, _P]),
+    "pcg_dense_select_blocks": (_I32, [_G, _I32, _I32]),
     "pcg_choose_plan_bytes": (_I64, [_G, _I32, _I64]),
     "pcg_choose_data_bytes": (_I64, [_G, _I32, _I64]),
     "pcg_plan_batches": (C.c_int, [_G, _P, _P, _I32, _I32, C.POINTER(_F64), C.POINTER(_F64), _I32, _I32, _P, _I64, _I64, _P, _P,

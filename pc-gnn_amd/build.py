@@ -2,6 +2,7 @@
 
     python -m pcgnn_amd.build        # or:  __graft_entry__.build()
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -31,7 +32,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     if not os.path.exists(hipcc):
         raise RuntimeError("hipcc not found - cannot build libpcgnn_hip.so")
     os.makedirs(LIBDIR, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "choose.h"), os.path.join(HERE, "..", "include", "pcgnn.h")]
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "pcgnn.h")]
     objs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

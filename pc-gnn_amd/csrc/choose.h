@@ -104,9 +104,11 @@ static inline CarveSizes carve(const pcg_graph_desc *g, int32_t B, int64_t list_
     sz.plan_bytes = off;
     off = 0;
     base = data_base;
+    // (the list first: its place in the data part does not depend on the batch size, so the list a select launch writes for one
+    //  batch never overlaps the partial sums another batch size's dense tiles read beside it - the pipelined step)
+    p = take(4 * list_capacity);                   if (w) w->list = reinterpret_cast<int32_t *>(p);
     p = take(4 * chunk_cap * g->feat_stride);      if (w) w->partial = reinterpret_cast<float *>(p);
     p = take(4 * rows);                            if (w) w->row_ticket = reinterpret_cast<uint32_t *>(p);
-    p = take(4 * list_capacity);                   if (w) w->list = reinterpret_cast<int32_t *>(p);
     p = take(4 * scratch_cap);                     if (w) w->key_scratch = reinterpret_cast<uint32_t *>(p);
     sz.data_bytes = off;
     if (w) {
@@ -153,6 +155,11 @@ struct ClfStep {
     float *part;
     int64_t part_stride;
     uint32_t *ticket;          // device word, zero between launches
+    // the pipelined step (dense_select_kernel): this step's select runs BESIDE the dense tiles of the step before, so
+    float *clf_out;            // non-null: theta_clf's in-value is also stored here - the dense tiles of THIS step read it from
+                               //   here, because the next step's select overwrites theta_clf while they run
+    int32_t *count_step;       // non-null: the dense launch of the step before has not counted itself yet (t = step_counter + 2)
+                               //   and the workgroup that applies Adam counts it (+1) once it has read the count
 };
 
 struct ChooseArgs {
@@ -211,6 +218,10 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
 
 // select.hip
 int launch_select_rows(const ChooseArgs &a, hipStream_t st);
+// select.hip: the pipelined step's fused launch - the dense tiles of one batch (dense.h) beside the selection of the next
+struct DenseArgs;
+int dense_select_blocks(const pcg_graph_desc &g, int emb, int B);
+int launch_dense_select(const DenseArgs &d, const ChooseArgs &a, int n_sel, hipStream_t st);
 // sort.hip: the one-launch bucket sort over raw keys (RANK_MAX < n_pos <= 131072)
 int launch_bk_onepass(const uint64_t *raw, int n_pos, uint64_t *keys, int cap, uint32_t *status, hipStream_t st);
 

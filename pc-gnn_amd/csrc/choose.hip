@@ -13,6 +13,7 @@
 #include <stddef.h>
 
 #include "choose.h"
+#include "dense.h"
 
 namespace pcg {
 
@@ -733,6 +734,8 @@ static int choose_args(pcg::ChooseArgs &a, const pcg_graph_desc *g, const int32_
     a.n_sort = a.sort_cap = a.sort_slices = a.sort_slice_len = 0;
     a.pending_clear = nullptr;
     a.clf.clf_next = nullptr;
+    a.clf.clf_out = nullptr;
+    a.clf.count_step = nullptr;
     a.n_wg_units = 0;
     pcg::carve1(g, B, list_capacity, static_cast<unsigned char *>(workspace), &a.w,
                 static_cast<unsigned char *>(const_cast<void *>(plan)));
@@ -1094,19 +1097,19 @@ int pcg_choose_gather_planned(const pcg_graph_desc *g, const int32_t *nodes, con
                                     agg, agg_stride, status, stream);
 }
 
-/* select + gather of a TRAINING step whose label classifier is stepped on its own (ClfStep / SideJob in choose.h): two launches,
- *   select_rows         [+ one workgroup: the classifier's forward / loss / Adam for THIS batch: clf_next <- the updated classifier]
- *   gather_train_kernel [+ the previous step's deferred Adam update of every other parameter || (score_next) the NEXT step's
- *                          score pass and unsorted train-pos keys with clf_next]
- * followed by pcg_train_dense(adam_clf = 2).  s0 / pos_keys: read by the select launch (this step's scores; unsorted keys in the
- * scratch half), rewritten by the gather launch for the next step. */
-int pcg_choose_gather_train(const pcg_graph_desc *g, const int32_t *nodes, const int32_t *labels, int32_t B, float *s0,
-                            uint64_t *pos_keys, const double *thresholds, const double *rho, int32_t add_self, float *agg,
-                            int32_t agg_stride, int32_t *cnt, void *workspace, const void *plan, int64_t list_capacity,
-                            uint32_t *status, uint32_t *sync_words, float *theta, float *m, float *v, int32_t emb, float *clf_next,
-                            const float *slabs, const int32_t *step_counter, float lambda_1, float inv_count, double lr, double beta1,
-                            double beta2, double eps, double weight_decay, int32_t score_next, const uint8_t *next_touched,
-                            const float *acts, int32_t act_ld, float *wg_scratch, int32_t keys_sorted, void *stream) {
+// pcg_choose_gather_train's two launches, set up once: the select launch's arguments (a) and the gather launch's riders (sd)
+struct TrainParts {
+    pcg::ChooseArgs a;
+    pcg::SideJob sd;
+    bool rank, one_launch;
+    int64_t cap;
+};
+#define PCG_TRAIN_PARAMS const pcg_graph_desc *g, const int32_t *nodes, const int32_t *labels, int32_t B, float *s0, uint64_t *pos_keys, const double *thresholds, const double *rho, int32_t add_self, float *agg, int32_t agg_stride, int32_t *cnt, void *workspace, const void *plan, int64_t list_capacity, uint32_t *status, uint32_t *sync_words, float *theta, float *m, float *v, int32_t emb, float *clf_next, const float *slabs, const int32_t *step_counter, float lambda_1, float inv_count, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t score_next, const uint8_t *next_touched, const float *acts, int32_t act_ld, float *wg_scratch, int32_t keys_sorted
+#define PCG_TRAIN_ARGS g, nodes, labels, B, s0, pos_keys, thresholds, rho, add_self, agg, agg_stride, cnt, workspace, plan, list_capacity, status, sync_words, theta, m, v, emb, clf_next, slabs, step_counter, lambda_1, inv_count, lr, beta1, beta2, eps, weight_decay, score_next, next_touched, acts, act_ld, wg_scratch, keys_sorted
+
+// wgrad_in_select: the A/B option PCG_WGRAD_IN_SELECT may move the weight-gradient workgroups into the select launch - only
+// when one call makes both launches (the split calls keep them in the gather launch)
+static int train_parts(TrainParts &t, bool wgrad_in_select, PCG_TRAIN_PARAMS) {
     if (!g || B < 0) return PCG_E_ARG;
     if (B == 0) return PCG_OK;
     if (!g->X || !agg || !s0 || !sync_words || !theta || !m || !v || !clf_next || !slabs || !step_counter || !labels) return PCG_E_ARG;
@@ -1116,13 +1119,13 @@ int pcg_choose_gather_train(const pcg_graph_desc *g, const int32_t *nodes, const
     const int64_t n_params = pcg_dense_n_params(g->feat_dim, emb, g->n_rel);
     const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, emb, g->n_rel, 3, 0);
     if (n_params < 0 || o_clf < 0) return PCG_E_ARG;
-    pcg::ChooseArgs a;
+    pcg::ChooseArgs &a = t.a;
     int rc = choose_args(a, g, nodes, labels, B, s0, nullptr, pos_keys, thresholds, rho, 1, add_self, cnt, workspace, list_capacity,
                          status, false, plan);
     if (rc != PCG_OK) return rc;
     if (!cnt) return PCG_E_ARG;
-    const bool rank = g->n_pos > 0 && g->n_pos <= pcg::RANK_MAX;
-    const int64_t cap = g->n_pos > 0 ? pcg_pos_sort_capacity(g->n_pos) / 2 : 0;
+    const bool rank = t.rank = g->n_pos > 0 && g->n_pos <= pcg::RANK_MAX;
+    const int64_t cap = t.cap = g->n_pos > 0 ? pcg_pos_sort_capacity(g->n_pos) / 2 : 0;
     // keys_sorted: pos_keys' first half holds THIS step's keys sorted already (the previous step's pcg_train_dense(sort_keys), or
     // pcg_pos_sort behind pcg_step_scores): no in-kernel sort, no row waits, a hub row's window search runs beside its key pass
     if (rank && !keys_sorted) {                        // the select kernel sorts the unsorted keys itself
@@ -1148,7 +1151,6 @@ int pcg_choose_gather_train(const pcg_graph_desc *g, const int32_t *nodes, const
     a.clf.part = const_cast<float *>(slabs) + o_clf;
     a.clf.part_stride = n_params;
     a.clf.ticket = sync_words;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     // the deferred update's weight-gradient workgroups (acts): in the gather launch (where they cost ~3 us of its ~10) - or, an
     // option that measured slower, as the first units of the select launch
     pcg::WgradArgs wga = {};
@@ -1177,14 +1179,12 @@ int pcg_choose_gather_train(const pcg_graph_desc *g, const int32_t *nodes, const
             const char *e = getenv("PCG_WGRAD_IN_SELECT");
             in_select = e ? atoi(e) : 0;
         }
-        if (in_select && wga.kparts == 1 && wg_tiles % 2 == 0 && wg_tiles / 2 <= 96 && g->feat_stride <= 256) {
+        if (in_select && wgrad_in_select && wga.kparts == 1 && wg_tiles % 2 == 0 && wg_tiles / 2 <= 96 && g->feat_stride <= 256) {
             a.wg = wga;
             a.n_wg_units = wg_tiles / 2;
         }
     }
-    rc = pcg::launch_select(a, st, true);
-    if (rc != PCG_OK) return rc;
-    pcg::SideJob sd;
+    pcg::SideJob &sd = t.sd;
     sd.ad.theta = theta; sd.ad.m = m; sd.ad.v = v;
     sd.ad.slabs = slabs;
     sd.ad.n_params = n_params;
@@ -1212,18 +1212,98 @@ int pcg_choose_gather_train(const pcg_graph_desc *g, const int32_t *nodes, const
     sd.s0 = s0;
     sd.touched = next_touched;
     // (the one-launch bucket sort - 16384 < n_pos <= 131072 - works on raw keys formed here too)
-    const bool one_launch = pcg_pos_sort_one_launch(g->n_pos) != 0;
+    const bool one_launch = t.one_launch = pcg_pos_sort_one_launch(g->n_pos) != 0;
     sd.raw_keys = (score_next && (rank || one_launch) && g->train_pos) ? pos_keys + cap : nullptr;
     const int rows_per_block = 4 * (PCG_WAVE / pcg::lanes_per_row(g->feat_stride));
     int n_key = sd.raw_keys ? (g->n_pos + rows_per_block - 1) / rows_per_block : 0;
     sd.n_key_blocks = n_key > 256 ? 256 : n_key;
     sd.n_score_blocks = score_next ? (int)pcg::score_table_blocks(g->n_nodes, g->feat_stride) : 0;
     sd.zero_word = sync_words + 3;
-    rc = pcg::launch_gather_train(g->X, g->feat_dim, g->feat_stride, g->n_nodes, cnt, g, B, a.w, agg, agg_stride, status, sd, st);
+    return PCG_OK;
+}
+
+// parts: 1 = the select launch, 2 = the gather launch (+ the sort of the next step's keys where that is a launch of its own), 3 = both
+static int train_launch(int parts, float *clf_out, PCG_TRAIN_PARAMS, void *stream) {
+    if (!g || B < 0) return PCG_E_ARG;
+    if (B == 0) return PCG_OK;
+    TrainParts t;
+    int rc = train_parts(t, parts == 3, PCG_TRAIN_ARGS);
     if (rc != PCG_OK) return rc;
-    if (score_next && one_launch) return pcg::launch_bk_onepass(pos_keys + cap, g->n_pos, pos_keys, (int)cap, status, st);
+    t.a.clf.clf_out = clf_out;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (parts & 1) {
+        rc = pcg::launch_select(t.a, st, true);
+        if (rc != PCG_OK) return rc;
+    }
+    if (!(parts & 2)) return PCG_OK;
+    rc = pcg::launch_gather_train(g->X, g->feat_dim, g->feat_stride, g->n_nodes, cnt, g, B, t.a.w, agg, agg_stride, status, t.sd, st);
+    if (rc != PCG_OK) return rc;
+    if (score_next && t.one_launch) return pcg::launch_bk_onepass(pos_keys + t.cap, g->n_pos, pos_keys, (int)t.cap, status, st);
     if (score_next && g->n_pos > pcg::RANK_MAX) return pcg_pos_sort(g, s0, pos_keys, stream);
     return PCG_OK;
+}
+
+/* select + gather of a TRAINING step whose label classifier is stepped on its own (ClfStep / SideJob in choose.h): two launches,
+ *   select_rows         [+ one workgroup: the classifier's forward / loss / Adam for THIS batch: clf_next <- the updated classifier]
+ *   gather_train_kernel [+ the previous step's deferred Adam update of every other parameter || (score_next) the NEXT step's
+ *                          score pass and unsorted train-pos keys with clf_next]
+ * followed by pcg_train_dense(adam_clf = 2).  s0 / pos_keys: read by the select launch (this step's scores; unsorted keys in the
+ * scratch half), rewritten by the gather launch for the next step. */
+int pcg_choose_gather_train(PCG_TRAIN_PARAMS, void *stream) {
+    return train_launch(3, nullptr, PCG_TRAIN_ARGS, stream);
+}
+
+int pcg_choose_train_part(int32_t part, PCG_TRAIN_PARAMS, float *clf_out, void *stream) {
+    if (part != 1 && part != 2) return PCG_E_ARG;
+    return train_launch(part, clf_out, PCG_TRAIN_ARGS, stream);
+}
+
+int32_t pcg_dense_select_blocks(const pcg_graph_desc *g, int32_t emb, int32_t B) {
+    return g ? pcg::dense_select_blocks(*g, emb, B) : 0;
+}
+
+int pcg_dense_select_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
+                           const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt, const void *plan,
+                           float inv_count, const float *clf_in, float *logits, float *center, float *row_loss, float *acts,
+                           int32_t act_ld, const int32_t *next_ids, const int32_t *next_labels, int32_t next_B, int32_t *next_cnt,
+                           const void *next_plan, float next_inv_count, float *clf_out, float *s0, uint64_t *pos_keys,
+                           const double *thresholds, const double *rho, int32_t add_self, void *workspace, int64_t list_capacity,
+                           uint32_t *status, uint32_t *sync_words, float *clf_next, const float *slabs, int32_t *step_counter,
+                           float lambda_1, double lr, double beta1, double beta2, double eps, double weight_decay, void *stream) {
+    if (!g || B < 1 || next_B < 1 || !clf_in || !clf_out || !acts || !cnt || !next_cnt || !workspace || !sync_words || !step_counter)
+        return PCG_E_ARG;
+    if (list_capacity < 1 || list_capacity >= (1ll << 31)) return PCG_E_ARG;
+    const int n_sel = pcg::dense_select_blocks(*g, emb, B);
+    if (n_sel <= 0) return PCG_E_UNSUPPORTED;
+    // batch t + 1's select launch as pcg_choose_train_part(1) sets it up, its train-pos keys unsorted (it sorts them itself)
+    TrainParts t;
+    int rc = train_parts(t, false, g, next_ids, next_labels, next_B, s0, pos_keys, thresholds, rho, add_self, const_cast<float *>(agg),
+                         agg_stride, next_cnt, workspace, next_plan, list_capacity, status, sync_words, theta, m, v, emb, clf_next, slabs,
+                         step_counter, lambda_1, next_inv_count, lr, beta1, beta2, eps, weight_decay, 1, nullptr, nullptr, 0, nullptr, 0);
+    if (rc != PCG_OK) return rc;
+    t.a.clf.clf_out = clf_out;
+    t.a.clf.count_step = step_counter;
+    // batch t's tiles as pcg_train_dense(adam_clf = 3) sets them up - without the riding key sort, without counting the step,
+    // with the classifier the select launch of batch t left in clf_in
+    pcg::DenseExtra x;
+    pcg::Workspace w;
+    pcg::carve1(g, B, list_capacity, static_cast<unsigned char *>(workspace), &w, static_cast<unsigned char *>(const_cast<void *>(plan)));
+    x.chunk_begin = w.chunk_begin;
+    x.partial = w.partial;
+    x.cnt = cnt;
+    x.partial_stride = g->feat_stride;
+    x.pending = sync_words + 1;
+    x.acts = acts;
+    x.act_ld = act_ld;
+    pcg::DenseArgs d;
+    int n_sort_blocks = 0;
+    rc = pcg::dense_args(d, n_sort_blocks, g, theta, emb, ids, labels, B, agg, agg_stride, lambda_1, inv_count, logits, center, nullptr,
+                         row_loss, const_cast<float *>(slabs), nullptr, x);
+    if (rc != PCG_OK) return rc;
+    d.W_clf = clf_in;
+    d.b_clf = clf_in + 2 * g->feat_dim;
+    d.stamps = nullptr;
+    return pcg::launch_dense_select(d, t.a, n_sel, static_cast<hipStream_t>(stream));
 }
 
 int pcg_choose_aggregate_planned(const pcg_graph_desc *g, const int32_t *nodes, const int32_t *labels, int32_t B,

@@ -24,6 +24,7 @@
 #include <stdlib.h>
 
 #include "choose.h"
+#include "dense.h"
 
 namespace pcg {
 
@@ -1034,9 +1035,10 @@ constexpr int SORT_TILE = 4096;          // keys per LDS tile of the in-kernel t
 // keys at their ranks (write-through), puts accumulators and ticket back to zero and counts the group in.  A few hundred
 // compares per lane instead of the thousands a whole-range rank sort by ceil(P / 64) workgroups costs while the other
 // workgroups of its CU compete for the same SIMDs: the keys are sorted ~4 us into the launch instead of ~9.
-template <int TILE>
+template <int TILE, int NW = SEL_NW>
 __device__ __forceinline__ void sort_share(const ChooseArgs &a, int w, uint64_t *sh, int *part, int tid) {
-    constexpr int PER = TILE / (SEL_NW * PCG_WAVE);
+    static_assert(TILE % (NW * PCG_WAVE) == 0, "every thread loads the same number of keys of a tile");
+    constexpr int PER = TILE / (NW * PCG_WAVE);
     const int lane = tid & (PCG_WAVE - 1), wave = tid >> 6;
     const int P = a.g.n_pos;
     const int group = w % a.n_sort, slice = w / a.n_sort;
@@ -1051,14 +1053,14 @@ __device__ __forceinline__ void sort_share(const ChooseArgs &a, int w, uint64_t 
         uint64_t kt[PER];
 #pragma unroll
         for (int u = 0; u < PER; ++u) {                                    // (unconditional loads: index clamped, pad = all ones)
-            const int t = tid + u * SEL_NW * PCG_WAVE;
+            const int t = tid + u * NW * PCG_WAVE;
             kt[u] = raw[t0 + (t < nt ? t : nt - 1)] | (t < nt ? 0ull : ~0ull);
         }
         __syncthreads();
 #pragma unroll
-        for (int u = 0; u < PER; ++u) sh[tid + u * SEL_NW * PCG_WAVE] = kt[u];
+        for (int u = 0; u < PER; ++u) sh[tid + u * NW * PCG_WAVE] = kt[u];
         __syncthreads();
-        const int chunk = (((nt + SEL_NW - 1) / SEL_NW) + 7) & ~7;
+        const int chunk = (((nt + NW - 1) / NW) + 7) & ~7;
         const int j0 = wave * chunk;
         const int nt8 = (nt + 7) & ~7;
         const int j1 = j0 + chunk < nt8 ? j0 + chunk : nt8;
@@ -1077,7 +1079,7 @@ __device__ __forceinline__ void sort_share(const ChooseArgs &a, int w, uint64_t 
     if (wave == 0) {
         int cnt = 0;
 #pragma unroll
-        for (int x = 0; x < SEL_NW; ++x) cnt += part[x * PCG_WAVE + lane];
+        for (int x = 0; x < NW; ++x) cnt += part[x * PCG_WAVE + lane];
         uint32_t ticket = 0;
         if (a.sort_slices > 1) {                                           // (one slice: the count is the rank)
             if (i < P) __hip_atomic_fetch_add(a.rank_acc + i, (uint32_t)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1144,7 +1146,9 @@ __device__ __forceinline__ void clf_step_body(const ClfStep c, const float *__re
     const bool mine = tid < NC;
     const int ic = mine ? tid : 0;
     const float p_old = c.clf_next[ic], m_old = c.m[ic], v_old = c.v[ic];
-    const float t = (float)(c.step_counter[0] + 1);             // this step's dense launch counts it; it has not run yet
+    // this step's dense launch counts it; it has not run yet (count_step: nor has the one of the step before - it runs beside
+    // this launch, which counts for it below)
+    const float t = (float)(c.step_counter[0] + (c.count_step ? 2 : 1));
     constexpr int NPRE = 2;                                     // ids / labels per thread of a block: RB <= NPRE * NT
     int nb = B < RB ? B : RB;
     int id_pre[NPRE], y_pre[NPRE];
@@ -1158,6 +1162,7 @@ __device__ __forceinline__ void clf_step_body(const ClfStep c, const float *__re
         const float w = i == tid ? p_old : c.clf_next[i];
         wl[i] = w;
         if (cw == 0) c.theta_clf[i] = w;                        // what this step's dense kernel computes the loss term with
+        if (cw == 0 && c.clf_out) c.clf_out[i] = w;
     }
 #pragma unroll
     for (int q = 0; q < NPRE; ++q) {
@@ -1307,23 +1312,25 @@ __device__ __forceinline__ void clf_step_body(const ClfStep c, const float *__re
         const float denom = sqrtf(vi) / sqrtf(bc2) + c.h.eps;
         c.clf_next[i] = p - (c.h.lr / bc1) * (mi / denom);
     }
+    // (every workgroup of the step has read the count: the last one in is the only one that uses it)
+    if (c.count_step && tid == 0) __hip_atomic_fetch_add(c.count_step, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();                                             // (the LDS is the row paths' again)
 }
 
-// CLF: the launch carries the label classifier's step (training: pcg_choose_gather_train): 1 = feature rows of up to 256 floats
-// (one float4 chunk per lane: the datasets' 128-B rows), 2 = wider rows.  Instantiation 0 holds none of that code - nor the
-// few bytes of scratch it spills under the row paths' register budget -, so every other caller's launch is the row paths' alone.
-template <int CLF>
-__global__ void __launch_bounds__(SEL_NW *PCG_WAVE) __attribute__((amdgpu_waves_per_eu(6, 8))) select_rows(const ChooseArgs a) {
-    extern __shared__ __align__(16) unsigned char smem[];
+// The body of one select workgroup of NW waves (8: select_rows; 16: dense_select_kernel): blk of nblk workgroups that share
+// the selection, smem = its dynamic LDS (select_smem_bytes(key_cap, NW); key_cap >= NW * WAVE_AREA).  The label classifier's
+// step runs on SEL_NW waves whatever NW is (its sums keep their order); the other paths use all of them.
+template <int CLF, int NW = SEL_NW>
+__device__ __forceinline__ void select_rows_body(const ChooseArgs &a, int blk, int nblk, unsigned char *smem) {
+    static_assert(NW == SEL_NW || NW == 2 * SEL_NW, "8 or 16 waves");
     uint32_t *lds = reinterpret_cast<uint32_t *>(smem);
     uint32_t *hist = lds + a.key_cap;
-    uint32_t *cand = hist + HIST_WG;
-    int *red = reinterpret_cast<int *>(cand + PCG_WAVE);                   // 2 * SEL_NW + 2 + 4 ints, then 2 claim slots
-    int *claim = red + 2 * SEL_NW + 6;
+    uint32_t *cand = hist + 4 * NW * PCG_WAVE;
+    int *red = reinterpret_cast<int *>(cand + PCG_WAVE);                   // 2 * NW + 2 + 4 ints, then 2 claim slots
+    int *claim = red + 2 * NW + 6;
     // per-relation neighbour arrays in LDS: a per-lane relation index (four short rows per wave) then costs one ds_read
     // instead of a waterfall over the kernel arguments
-    const int32_t **t_indices = reinterpret_cast<const int32_t **>(red + 2 * SEL_NW + 8);
+    const int32_t **t_indices = reinterpret_cast<const int32_t **>(red + 2 * NW + 8);
     int *sortw = reinterpret_cast<int *>(t_indices + PCG_MAX_REL);         // 4 + KIDX_MAX words: wait_sorted_keys
     if (threadIdx.x < PCG_MAX_REL) t_indices[threadIdx.x] = a.g.indices[threadIdx.x < (unsigned)a.g.n_rel ? threadIdx.x : 0];
     const bool leader = threadIdx.x == 0;
@@ -1335,10 +1342,10 @@ __global__ void __launch_bounds__(SEL_NW *PCG_WAVE) __attribute__((amdgpu_waves_
     // the items can be spread over more workgroups (more CUs' load paths) than eight per workgroup would use
     // (training: workgroup 0 does the label classifier's step and nothing else; the row workgroups are the others)
     const int clf_wg = (CLF && a.clf.clf_next) ? a.clf.n_wg : 0;
-    const int grid = (int)gridDim.x - clf_wg, bid = (int)blockIdx.x - clf_wg;
+    const int grid = nblk - clf_wg, bid = blk - clf_wg;
     const int avail = grid - n_wg > grid / 4 ? grid - n_wg : grid / 4;
     int bs = (n_items + avail - 1) / avail;
-    bs = bs < 1 ? 1 : (bs > SEL_NW ? SEL_NW : bs);
+    bs = bs < 1 ? 1 : (bs > NW ? NW : bs);
     const int n_units = n_wg + (n_items + bs - 1) / bs;
     const bool pull = n_units > grid;                                      // otherwise unit = workgroup: no atomics at all
     const int shard = (bid < 0 ? 0 : bid) % SEL_SHARDS;
@@ -1351,10 +1358,11 @@ __global__ void __launch_bounds__(SEL_NW *PCG_WAVE) __attribute__((amdgpu_waves_
         __builtin_amdgcn_s_setprio(3);
         if (a.stamps && leader) a.stamps[(size_t)a.g.n_rel * a.B * 8 + 2] = wall_clock64();
         // this workgroup's slice of the batch: whole multiples of 64 rows (every workgroup has some: n_wg <= ceil(B / 1024))
-        const int cw = (int)blockIdx.x;
+        const int cw = blk;
         const int per = ((a.B + a.clf.n_wg - 1) / a.clf.n_wg + PCG_WAVE - 1) & ~(PCG_WAVE - 1);
         const int r0 = cw * per < a.B ? cw * per : a.B, r1 = r0 + per < a.B ? r0 + per : a.B;
         unsigned long long *cst = (a.stamps && cw == 0) ? a.stamps + (size_t)a.g.n_rel * a.B * 8 + 8 : nullptr;
+        if ((int)threadIdx.x >= SEL_NW * PCG_WAVE) return;          // (a wave that has ended is not waited for at a barrier)
         if constexpr (CLF == 2) clf_step_body<2, 2>(a.clf, a.g.X, a.g.feat_dim, a.g.feat_stride, a.nodes + r0, a.labels + r0, r1 - r0, lds, (int)threadIdx.x, cst, cw);
         else if constexpr (CLF == 1) clf_step_body<1, 3>(a.clf, a.g.X, a.g.feat_dim, a.g.feat_stride, a.nodes + r0, a.labels + r0, r1 - r0, lds, (int)threadIdx.x, cst, cw);
         if (a.stamps && leader) a.stamps[(size_t)a.g.n_rel * a.B * 8 + 3] = wall_clock64();
@@ -1364,7 +1372,7 @@ __global__ void __launch_bounds__(SEL_NW *PCG_WAVE) __attribute__((amdgpu_waves_
     int u = bid;
     // The previous step's weight gradients (GEMMs over its batch) + Adam, two tiles per workgroup, before its rows (CLF launches
     // of small batches: choose.h).  Nothing in this launch reads what they write (the dense launch, two launches on, does).
-    if (CLF && a.n_wg_units > 0) {
+    if (CLF && NW == SEL_NW && a.n_wg_units > 0) {          // (the launches with NW = 16 leave them to the gather launch)
         if (u < a.n_wg_units) {
             float(*wred)[256] = reinterpret_cast<float(*)[256]>(lds + ((int)threadIdx.x >> 8) * 1024);
             const int n_tiles = wgrad_tiles(a.wg.F, a.wg.E, a.wg.R, 0);
@@ -1382,8 +1390,8 @@ __global__ void __launch_bounds__(SEL_NW *PCG_WAVE) __attribute__((amdgpu_waves_
         if (u < helpers) {
             if (a.stamps && leader && u == 0) a.stamps[(size_t)a.g.n_rel * a.B * 8 + 4] = wall_clock64();
             __builtin_amdgcn_s_setprio(3);                                 // (the other workgroups of this CU are busy with their rows)
-            if (a.sort_slice_len <= 512) sort_share<512>(a, u, reinterpret_cast<uint64_t *>(lds), reinterpret_cast<int *>(hist), (int)threadIdx.x);
-            else sort_share<SORT_TILE>(a, u, reinterpret_cast<uint64_t *>(lds), reinterpret_cast<int *>(hist), (int)threadIdx.x);
+            if (a.sort_slice_len <= 512 * NW / SEL_NW) sort_share<512 * NW / SEL_NW, NW>(a, u, reinterpret_cast<uint64_t *>(lds), reinterpret_cast<int *>(hist), (int)threadIdx.x);
+            else sort_share<SORT_TILE, NW>(a, u, reinterpret_cast<uint64_t *>(lds), reinterpret_cast<int *>(hist), (int)threadIdx.x);
             __builtin_amdgcn_s_setprio(0);
         }
         // the sorting workgroups start late: they take the LAST of the first `grid` units (short rows), the others move up -
@@ -1411,7 +1419,7 @@ __global__ void __launch_bounds__(SEL_NW *PCG_WAVE) __attribute__((amdgpu_waves_
             // (a workgroup row is the launch's long pole and shares its CU with two workgroups of short rows: it goes first)
             static_assert(true, "");
             if (PCG_WG_ROW_PRIO) __builtin_amdgcn_s_setprio(PCG_WG_ROW_PRIO);
-            if (d <= a.key_cap) select_wg_row<true>(a, row, lds, hist, cand, red, tid, keys_ok, sortw, nullptr, a.key_cap);      // (longer rows: select_long_rows)
+            if (d <= a.key_cap) select_wg_row<true, NW>(a, row, lds, hist, cand, red, tid, keys_ok, sortw, nullptr, a.key_cap);      // (longer rows: select_long_rows)
             if (PCG_WG_ROW_PRIO) __builtin_amdgcn_s_setprio(0);
         } else {
             const int j = wave < bs ? (u - n_wg) * bs + wave : n_items;
@@ -1437,6 +1445,15 @@ __global__ void __launch_bounds__(SEL_NW *PCG_WAVE) __attribute__((amdgpu_waves_
             atomicExch(a.w.heads + 15, 0u);
         }
     }
+}
+
+// CLF: the launch carries the label classifier's step (training: pcg_choose_gather_train): 1 = feature rows of up to 256 floats
+// (one float4 chunk per lane: the datasets' 128-B rows), 2 = wider rows.  Instantiation 0 holds none of that code - nor the
+// few bytes of scratch it spills under the row paths' register budget -, so every other caller's launch is the row paths' alone.
+template <int CLF>
+__global__ void __launch_bounds__(SEL_NW *PCG_WAVE) __attribute__((amdgpu_waves_per_eu(6, 8))) select_rows(const ChooseArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    select_rows_body<CLF>(a, (int)blockIdx.x, (int)gridDim.x, smem);
 }
 
 // Rows beyond the LDS key capacity (> WG_KEYCAP neighbours), in a launch of their own: the multi-pass selection over keys kept
@@ -1485,9 +1502,32 @@ __global__ void __launch_bounds__(LONG_NW *PCG_WAVE) select_long_rows(const Choo
     }
 }
 
-static size_t select_smem_bytes(int key_cap) {
-    return sizeof(uint32_t) * (key_cap + HIST_WG + PCG_WAVE) + sizeof(int) * (2 * SEL_NW + 8) + sizeof(void *) * PCG_MAX_REL +   // (claim[2] = red[22..23])
+static size_t select_smem_bytes(int key_cap, int nw = SEL_NW) {
+    return sizeof(uint32_t) * (key_cap + 4 * nw * PCG_WAVE + PCG_WAVE) + sizeof(int) * (2 * nw + 8) + sizeof(void *) * PCG_MAX_REL +   // (claim[2] = red[2 nw + 6 ..])
            sizeof(int) * (4 + KIDX_MAX);                                                                                            // sortw
+}
+
+// how the in-kernel train-pos sort is shared by row_blocks workgroups (a.n_sort key groups): slices per key group, keys per
+// slice (>= 128)
+static int select_sort_shape(ChooseArgs &as, int row_blocks) {
+    const ChooseArgs &a = as;
+    if (a.n_sort > 0) {
+        if (a.n_sort > row_blocks) return PCG_E_ARG;
+        // (PCG_SORT_SLICES: tuning knob.  More slices = fewer compares per workgroup, but accumulator atomics and a ticket hop,
+        //  and more workgroups that start on their rows late; measured on the YelpChi-like batch: see DESIGN.md)
+        static int knob = -1;
+        if (knob < 0) {
+            const char *e = getenv("PCG_SORT_SLICES");
+            knob = e ? atoi(e) : 0;
+        }
+        int slices = knob > 0 ? knob : 3;   // (measured, batch 4096: power-law 2 M / 8000 keys 1: 142.1, 2: 140.2, 3: 133.3, 4: 136.8, 6: 143.0 us per step; emb 128 / 2670 keys 2: 93.4, 3: 93.5, 4: 94.1, 6: 95.4)
+        if (slices > row_blocks / a.n_sort) slices = row_blocks / a.n_sort;
+        const int most = (a.g.n_pos + 127) / 128;
+        slices = slices > most ? most : slices;
+        as.sort_slices = slices < 1 ? 1 : slices;
+        as.sort_slice_len = (a.g.n_pos + as.sort_slices - 1) / as.sort_slices;
+    }
+    return PCG_OK;
 }
 
 int launch_select_rows(const ChooseArgs &a, hipStream_t st) {
@@ -1529,22 +1569,8 @@ int launch_select_rows(const ChooseArgs &a, hipStream_t st) {
         }
     }
     const int row_blocks = nblk - (a.clf.clf_next ? a.clf.n_wg : 0);      // (training: one of the workgroups steps the label classifier)
-    if (a.n_sort > 0) {                      // how the sort is shared: slices per key group, keys per slice (>= 128)
-        if (a.n_sort > row_blocks) return PCG_E_ARG;
-        // (PCG_SORT_SLICES: tuning knob.  More slices = fewer compares per workgroup, but accumulator atomics and a ticket hop,
-        //  and more workgroups that start on their rows late; measured on the YelpChi-like batch: see DESIGN.md)
-        static int knob = -1;
-        if (knob < 0) {
-            const char *e = getenv("PCG_SORT_SLICES");
-            knob = e ? atoi(e) : 0;
-        }
-        int slices = knob > 0 ? knob : 3;   // (measured, batch 4096: power-law 2 M / 8000 keys 1: 142.1, 2: 140.2, 3: 133.3, 4: 136.8, 6: 143.0 us per step; emb 128 / 2670 keys 2: 93.4, 3: 93.5, 4: 94.1, 6: 95.4)
-        if (slices > row_blocks / a.n_sort) slices = row_blocks / a.n_sort;
-        const int most = (a.g.n_pos + 127) / 128;
-        slices = slices > most ? most : slices;
-        as.sort_slices = slices < 1 ? 1 : slices;
-        as.sort_slice_len = (a.g.n_pos + as.sort_slices - 1) / as.sort_slices;
-    }
+    const int rc = select_sort_shape(as, row_blocks);
+    if (rc != PCG_OK) return rc;
     if (a.clf.clf_next && a.g.feat_stride > 256) hipLaunchKernelGGL(select_rows<2>, dim3(nblk), dim3(SEL_NW * PCG_WAVE), smem, st, as);
     else if (a.clf.clf_next) hipLaunchKernelGGL(select_rows<1>, dim3(nblk), dim3(SEL_NW * PCG_WAVE), smem, st, as);
     else hipLaunchKernelGGL(select_rows<0>, dim3(nblk), dim3(SEL_NW * PCG_WAVE), smem, st, as);
@@ -1572,6 +1598,96 @@ int launch_select_rows(const ChooseArgs &a, hipStream_t st) {
         hipLaunchKernelGGL(select_long_rows, dim3((int)nb), dim3(LONG_NW * PCG_WAVE), long_smem, st, al, per_wg);
         PCG_LAUNCH_CHECK();
     }
+    return PCG_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The pipelined training step's second launch: the dense tiles of batch t beside the selection of batch t + 1.
+// The selection of t + 1 needs nothing the dense tiles of t compute (its scores and unsorted train-pos keys come from the
+// gather launch of t, its classifier step reads clf_next, the ids and the labels), and the dense launch alone keeps only
+// n_tiles of the chip's CUs busy.  One launch, one shape - the dense one (1024 threads, its LDS: one workgroup per CU):
+//   workgroups 0 .. n_tiles - 1: dense_tile_body of batch t;
+//   the others (n_sel, about n_CU - n_tiles): select_rows_body<1, 16> of batch t + 1 - its classifier workgroup(s) (on 8 of
+//   their waves, so that its sums keep select_rows' order), the in-kernel train-pos sort and the rows on all 16 waves, each
+//   wave with select_rows' LDS area (key area 16 * WAVE_AREA words, 4096 histogram bins: ~99 KB, under the dense LDS).
+// What the two halves share, and why it is no race (the host passes):
+//   cnt          the select half writes batch t + 1's counts, the tiles read batch t's: two buffers (the engine's step parity);
+//   classifier   the select half copies its in-value to theta's classifier AND to clf_out (ClfStep::clf_out); the tiles read
+//                theirs from where the select of batch t left a copy (DenseArgs::W_clf / b_clf = clf_in), not from theta;
+//   step count   the tiles do not count (DenseArgs::step_counter = null); the classifier's Adam reads the count + 2 and counts
+//                for them afterwards (ClfStep::count_step) - the only reader of the count inside the launch;
+//   sync words   the tiles write pending ([1], [2]) only; the select half uses [0] (classifier ticket), [3 ..] (sort);
+//   keys         the tiles do not sort (DenseArgs::sort_raw = null); the select half sorts batch t + 1's keys itself;
+//   workspace    the select half writes the selection list (data part) and its own plan slot; the tiles read the partial sums
+//                (data part) and batch t's plan slot.  The list comes first in the data part (carve): its place does not
+//                depend on the batch size, so it never overlaps the partial sums of another batch size.
+template <bool WLDS, int F_, int E_, int R_>
+__global__ void __launch_bounds__(DENSE_THREADS) dense_select_kernel(const DenseArgs d, const ChooseArgs s) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int n_dense = d.n_tile_blocks;
+    if ((int)blockIdx.x < n_dense) {
+        dense_tile_body<WLDS, F_, E_, R_>(d, (int)blockIdx.x, reinterpret_cast<float *>(smem));
+        return;
+    }
+    select_rows_body<1, DENSE_WAVES>(s, (int)blockIdx.x - n_dense, (int)gridDim.x - n_dense, smem);
+}
+
+// Select workgroups of the fused launch for a dense batch of B rows, or 0: the step keeps its three launches.  The selection
+// needs the chip's other CUs: at most PCG_PIPE_MAX_TILES (default 128) tiles.  Not for rows beyond the select kernel's LDS keys
+// (their launch of its own), nor feature rows of more than 256 floats (the classifier step's wide variant).
+int dense_select_blocks(const pcg_graph_desc &g, int emb, int B) {
+    static int max_tiles = -1, n_cu = 0;
+    if (max_tiles < 0) {
+        const char *e = getenv("PCG_PIPE_MAX_TILES");
+        max_tiles = e ? atoi(e) : 128;
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            n_cu = 0;
+    }
+    if (B < 1 || emb < 16 || emb % 16 != 0 || g.n_rel < 1 || g.n_rel > PCG_MAX_REL) return 0;
+    const int n_tiles = (B + TB - 1) / TB;
+    if (n_tiles > max_tiles || g.feat_stride > 256 || g.max_degree > WG_KEYCAP) return 0;
+    if (dense_smem_bytes(g.feat_dim, emb, g.n_rel, dense_wlds(g.feat_dim, emb, g.n_rel)) > 160 * 1024) return 0;
+    int n_sel = n_cu - n_tiles;
+    n_sel = (n_sel > SEL_BLOCKS ? SEL_BLOCKS : n_sel) / SEL_SHARDS * SEL_SHARDS;
+    const int n_sort = g.n_pos > 0 && g.n_pos <= RANK_MAX ? (g.n_pos + PCG_WAVE - 1) / PCG_WAVE : 0;
+    if (n_sel < 64 || n_sel - 8 < n_sort) return 0;
+    return n_sel;
+}
+
+int launch_dense_select(const DenseArgs &d, const ChooseArgs &a, int n_sel, hipStream_t st) {
+    if (!a.clf.clf_next || a.g.feat_stride > 256 || a.g.max_degree > WG_KEYCAP || d.sort_raw || d.n_split != 1 || n_sel < 1)
+        return PCG_E_ARG;
+    ChooseArgs as = a;
+    as.key_cap = DENSE_WAVES * WAVE_AREA;
+    const int rc = select_sort_shape(as, n_sel - a.clf.n_wg);
+    if (rc != PCG_OK) return rc;
+    const int F = d.feat_dim, E = d.emb, R = d.n_rel;
+    const bool wlds = dense_wlds(F, E, R);
+    const size_t dsm = dense_smem_bytes(F, E, R, wlds), ssm = select_smem_bytes(DENSE_WAVES * WAVE_AREA, DENSE_WAVES);
+    typedef void (*kern_t)(const DenseArgs, const ChooseArgs);
+    kern_t kern;
+    if (R == 3 && F == 32 && E == 64 && wlds) kern = dense_select_kernel<true, 32, 64, 3>;
+    else if (R == 3 && F == 25 && E == 64 && wlds) kern = dense_select_kernel<true, 25, 64, 3>;
+    else if (R == 3 && F == 32 && E == 128 && !wlds) kern = dense_select_kernel<false, 32, 128, 3>;
+    else if (R == 3 && F == 25 && E == 128 && !wlds) kern = dense_select_kernel<false, 25, 128, 3>;
+    else kern = wlds ? dense_select_kernel<true, 0, 0, 0> : dense_select_kernel<false, 0, 0, 0>;
+    static kern_t attr_done[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool seen = false;
+    for (kern_t k : attr_done) seen = seen || k == kern;
+    if (!seen) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
+            hipSuccess)
+            return PCG_E_LAUNCH;
+        for (kern_t &k : attr_done)
+            if (!k) {
+                k = kern;
+                break;
+            }
+    }
+    hipLaunchKernelGGL(kern, dim3(d.n_tile_blocks + n_sel), dim3(DENSE_THREADS), dsm > ssm ? dsm : ssm, st, d, as);
+    PCG_LAUNCH_CHECK();
     return PCG_OK;
 }
 

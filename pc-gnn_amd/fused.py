@@ -54,7 +54,8 @@ def default_list_capacity(g: DeviceGraph, B: int, max_list_bytes: int = 8 << 30)
 
 class FusedPCGNN:
     def __init__(self, model: PCALayer, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8,
-                 max_batch: int = 1024, global_batch_scale: int = 1, list_capacity: Optional[int] = None):
+                 max_batch: int = 1024, global_batch_scale: int = 1, list_capacity: Optional[int] = None,
+                 pipeline: Optional[bool] = None):
         lib = _lib.load()
         self.lib = lib
         self.model = model
@@ -114,6 +115,11 @@ class FusedPCGNN:
         self.touched_on = (env == "1") if env in ("0", "1") else g.n_nodes * g.X.stride(0) * 4 >= (512 << 20)
         self._touch_stride = int(lib.pcg_touched_bytes(g.n_nodes)) if self.touched_on else 0
         self._list_capacity_arg = list_capacity  # entries of the selection list (None: worst case of the graph)
+        # Pipelined steps (epoch_run): batch t + 1's selection runs in ONE launch with batch t's dense tiles, on the CUs they leave
+        # idle - two launches per step instead of three (pcg_dense_select_train; batches of up to 128 tiles, whole-table scoring).
+        # pipeline=None: on unless PCG_PIPELINE=0 (A/B runs)
+        env = os.environ.get("PCG_PIPELINE")
+        self.pipeline = bool(pipeline) if pipeline is not None else env != "0"
         self.status = torch.zeros(1, dtype=torch.int32, device=self.dev)   # ONE device status word
         self._graphs = {}
         self._ep_graphs = {}
@@ -149,7 +155,12 @@ class FusedPCGNN:
         self._plans = {}                                                        # batch size -> a single plan slot (calls outside an epoch)
         self._touch_one = None                                                  # ... and their byte map of touched rows
         self.agg = torch.empty(g.R, B, g.feat_dim, dtype=torch.float32, device=dev)
-        self.cnt = torch.empty(g.R, B, dtype=torch.int32, device=dev)
+        # two count buffers: a pipelined step's fused launch selects batch t + 1 (its counts into one) while batch t's dense tiles
+        # read the other; every other step uses the first
+        self.cnt2 = torch.empty(2, g.R, B, dtype=torch.int32, device=dev)
+        self.cnt = self.cnt2[0]
+        self.clf_slots = torch.empty(2, 2 * self.F + 2, dtype=torch.float32, device=dev)   # the classifier each step's dense tiles read
+        self._pipe_blocks = int(lib.pcg_dense_select_blocks(g.desc_ref(), self.E, B))
         self.logits = torch.empty(B, 2, dtype=torch.float32, device=dev)
         self.center = torch.empty(B, 2, dtype=torch.float32, device=dev)
         self.row_loss = torch.zeros(B, dtype=torch.float32, device=dev)
@@ -301,7 +312,7 @@ class FusedPCGNN:
         self.last_counts = cnt
         return agg, cnt
 
-    def _enqueue_tail(self, ids, labels, B, agg, plan: int, train: bool, combined=None, adam_clf: Optional[bool] = None):
+    def _enqueue_tail(self, ids, labels, B, agg, plan: int, train: bool, combined=None, adam_clf: Optional[bool] = None, cnt=None):
         """dense tail reading the gather's partial sums (no combine launch); training: the gradient slabs are left pending
         (adam_clf 3, the default: no slabs at all - the kernel leaves its transposed activations and the next step's gather launch
         or flush() runs the weight-gradient GEMMs + Adam; 2: the same with per-tile gradient slabs; either way the label
@@ -309,7 +320,7 @@ class FusedPCGNN:
         reduces / all-reduces them itself; 1: the label classifier's Adam by the kernel's last workgroup (the four-launch step of
         pcg_step_scores_train); 4: transposed activations only, nothing marked as waiting (gradients())."""
         g = self.g
-        cnt = self.cnt.view(-1)[:g.R * B]
+        cnt = self.cnt.view(-1)[:g.R * B] if cnt is None else cnt
         b1, b2 = self.betas
         adam_clf = (3 if train else 0) if adam_clf is None else int(adam_clf)
         _lib.check(self.lib.pcg_train_dense(
@@ -322,6 +333,59 @@ class FusedPCGNN:
             _p(self.keys) if (adam_clf == 3 and self.presort and self._fresh) else None, self._stream()), "pcg_train_dense")
         if adam_clf == 1:                           # (the four-launch step updates theta's classifier in place)
             self.clf_next.copy_(self.theta[self.n_rest:])
+
+    def _pipelines(self, batches) -> bool:
+        """whether a sequence of training steps over these (lo, B) batches runs pipelined (_enqueue_pipelined)"""
+        return (self.pipeline and not self.touched_on and len(batches) >= 2 and self._pipe_blocks > 0
+                and max(B for _, B in batches) <= self.maxB)
+
+    def _train_args(self, ids, labels, B, plan: int, cnt, keys_sorted: int):
+        """pcg_choose_gather_train's arguments (without the stream) for a whole-table engine's step that scores the next one"""
+        g = self.g
+        agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
+        b1, b2 = self.betas
+        return (g.desc_ref(), _p(ids), _p(labels), B, _p(self.s0), _p(self.keys) if g.n_pos else None, self._thr, self._rhos, 0,
+                _p(agg), agg.stride(-2), _p(cnt), _p(self.data), C.c_void_p(plan), self.list_capacity, _p(self.status), _p(self.sync),
+                _p(self.theta), _p(self.m), _p(self.v), self.E, _p(self.clf_next), _p(self.slabs), _p(self.step_counter),
+                self.lambda_1, 1.0 / (B * self.scale), self.lr, b1, b2, self.eps, self.wd, 1, None, _p(self.acts), self.act_ld,
+                _p(self.wg_scratch), keys_sorted)
+
+    def _enqueue_pipelined(self, steps):
+        """Consecutive training steps [(ids, labels, B, plan)] (deferred Adam, as train_step(defer=True) each), pipelined:
+            select(0)
+            per step t:  gather(t) [|| Adam of t - 1 || scores + keys of t + 1]
+                         dense(t) || select(t + 1)      one launch (pcg_dense_select_train); the last step: dense(t) alone
+        Bit for bit what the three-launch steps leave.  The selection of t + 1 writes the other count buffer and the other
+        classifier slot than the dense tiles of t read; it sorts its train-pos keys itself."""
+        g, lib = self.g, self.lib
+        if not self._fresh:
+            self._enqueue_refresh()
+        R, F = g.R, g.feat_dim
+        b1, b2 = self.betas
+        st = self._stream()
+        cnt = lambda p, B: self.cnt2[p].view(-1)[:R * B]
+        ids, lab, B, plan = steps[0]
+        _lib.check(lib.pcg_choose_train_part(1, *self._train_args(ids, lab, B, plan, cnt(0, B), 1 if self.presort else 0),
+                                             _p(self.clf_slots[0]), st), "pcg_choose_train_part")
+        p = 0
+        for t, (ids, lab, B, plan) in enumerate(steps):
+            _lib.check(lib.pcg_choose_train_part(2, *self._train_args(ids, lab, B, plan, cnt(p, B), 0), None, st), "pcg_choose_train_part")
+            agg = self.agg.view(-1)[:R * B * F].view(R, B, F)
+            if t + 1 == len(steps):
+                self._fresh = True
+                self._enqueue_tail(ids, lab, B, agg, plan, True, cnt=cnt(p, B))
+                break
+            nids, nlab, nB, nplan = steps[t + 1]
+            _lib.check(lib.pcg_dense_select_train(
+                g.desc_ref(), _p(self.theta), _p(self.m), _p(self.v), self.E, _p(ids), _p(lab), B, _p(agg), agg.stride(1),
+                _p(cnt(p, B)), C.c_void_p(plan), 1.0 / (B * self.scale), _p(self.clf_slots[p]), _p(self.logits), _p(self.center),
+                _p(self.row_loss), _p(self.acts), self.act_ld, _p(nids), _p(nlab), nB, _p(cnt(p ^ 1, nB)), C.c_void_p(nplan),
+                1.0 / (nB * self.scale), _p(self.clf_slots[p ^ 1]), _p(self.s0), _p(self.keys) if g.n_pos else None, self._thr,
+                self._rhos, 0, _p(self.data), self.list_capacity, _p(self.status), _p(self.sync), _p(self.clf_next), _p(self.slabs),
+                _p(self.step_counter), self.lambda_1, self.lr, b1, b2, self.eps, self.wd, st), "pcg_dense_select_train")
+            p ^= 1
+        self.last_counts = self.cnt2[p].view(-1)[:R * B].view(R, B)
+        self._fresh = True
 
     def flush(self):
         """Apply a deferred Adam update now (no-op on the device if none is pending).  Enqueued, not synchronised."""
@@ -684,10 +748,15 @@ class FusedPCGNN:
             st = self._ep_sets[cur]
             nxt = self._ep_sets[cur ^ 1]
             def run():
-                for b in range(first_step, n_steps):
-                    lo, B = batches[b]
-                    self.train_step(st["ids"][lo:lo + B], st["lab"][lo:lo + B], defer=True, plan=self._ep_plan(b, cur),
-                                    touched=self._ep_touch(b, cur), next_touched=self._ep_next_touch(b, cur))
+                if self._pipelines(batches[first_step:n_steps]):
+                    self._lastB = batches[n_steps - 1][1]
+                    self._enqueue_pipelined([(st["ids"][lo:lo + B], st["lab"][lo:lo + B], B, self._ep_plan(b, cur))
+                                             for b, (lo, B) in enumerate(batches) if first_step <= b < n_steps])
+                else:
+                    for b in range(first_step, n_steps):
+                        lo, B = batches[b]
+                        self.train_step(st["ids"][lo:lo + B], st["lab"][lo:lo + B], defer=True, plan=self._ep_plan(b, cur),
+                                        touched=self._ep_touch(b, cur), next_touched=self._ep_next_touch(b, cur))
                 if flush:
                     self.flush()
             def warm_run():                      # (the warm-up leaves the staged ids - and the epoch counter - as they are)
