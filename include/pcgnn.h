@@ -479,6 +479,24 @@ int pcg_train_dense(const pcg_graph_desc *g, float *theta, float *m, float *v, i
                     uint32_t *sync_words, double lr, double beta1, double beta2, double eps, double weight_decay,
                     int32_t adam_clf, float *acts, int32_t act_ld, uint64_t *sort_keys, void *stream);
 int32_t pcg_dense_sorts_keys(int32_t B, int32_t n_pos);   /* 1: the launch above (adam_clf = 3, sort_keys) sorts n_pos keys at batch B */
+/* Whole-set inference (test mode, forward only): gnn logits of nodes ids[0 .. n) -> out_logits [n][2] and, if out_center is not
+ * NULL, the label-aware (centre) logits -> out_center [n][2].  ONE call enqueues everything: one score pass of theta's label
+ * classifier over the whole table into the caller's s0 [n_nodes], then per chunk of chunk_rows ids (the last one may be shorter):
+ * plan -> select -> gather (the launches of pcg_plan_epochs and pcg_choose_gather_planned: two to three) -> one persistent
+ * forward-only dense launch (pcg_infer_blocks(chunk_rows) workgroups, each staging the weights once and running tile after tile).
+ * thresholds: host, [n_rel]; no rho (no minority picks in test mode).  workspace: pcg_infer_workspace_bytes(g, emb, chunk_rows,
+ * list_capacity) bytes, no initial contents required, not shared with a concurrent call; list_capacity must cover the largest
+ * chunk's sum of pcg_sel_capacity_row(deg, threshold, rho, 0, n_pos, 0) over its rows and relations, else PCG_ST_SEL_OVERFLOW is
+ * set in *status and that chunk selects nothing.
+ * Parity: every logit is bit for bit what pcg_train_dense (labels = NULL, adam_clf = 0) writes for the same row after
+ * pcg_score_table + pcg_plan_batches + pcg_choose_gather_planned in test mode with the same theta, whatever the batch or chunk
+ * the row is in and whatever its position there (a row's selection list, gather chunks and dense sums are laid out per row,
+ * the dense phases are dense_step_kernel's, with the same MFMA chains, K order, K-split and fma order). */
+int64_t pcg_infer_workspace_bytes(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity);
+int pcg_infer_set(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *ids, int32_t n, int32_t chunk_rows,
+                  float *s0, const double *thresholds, void *workspace, int64_t list_capacity, float *out_logits, float *out_center,
+                  uint32_t *status, void *stream);
+int32_t pcg_infer_blocks(int32_t chunk_rows);   /* workgroups of the dense launch of a chunk of chunk_rows ids (host helper) */
 int pcg_step_front_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, float *s0,
                          uint64_t *pos_keys, const int32_t *nodes, const int32_t *labels, int32_t B,
                          const double *thresholds, const double *rho, int32_t add_self, void *workspace,

@@ -192,7 +192,11 @@ __device__ __forceinline__ float row16_sum(float p) {
 // then an immediate and the index arithmetic folds away - with run-time shapes the kernel issues ~1400 vector and ~750
 // scalar instructions per wave, most of them address arithmetic, and that issue time (not the matrix cores, 14 % busy,
 // nor the LDS, 20 % busy) is what it is bound by.  0: run-time shape (any F, E % 16 == 0, R <= 8).
-template <bool WLDS, int F_, int E_, int R_>
+// INFER: the forward phases only, for a workgroup that may run tile after tile (infer_dense_kernel, infer.hip): the K-split
+// partial tiles of `combined` go where the backward's dcomb / dh_r arrays are (the W_intra copy stays live for the next tile),
+// and STAGE_W = false skips the weights' LDS copy (the workgroup's first tile made it).  The training launches set neither:
+// their code is what it was before these flags existed.
+template <bool WLDS, int F_, int E_, int R_, bool INFER = false, bool STAGE_W = true>
 __device__ __forceinline__ void dense_tile_body(const DenseArgs &a, int bid, float *sm) {
     // bid: this workgroup's index among the tiles' workgroups (a.n_tile_blocks of them); sm: the launch's dynamic LDS
     const int F = F_ > 0 ? F_ : a.feat_dim, E = E_ > 0 ? E_ : a.emb, R = R_ > 0 ? R_ : a.n_rel;
@@ -212,6 +216,7 @@ __device__ __forceinline__ void dense_tile_body(const DenseArgs &a, int bid, flo
     float *s_dcl = s_dlog + TB * 2;                 // [TB][2] d loss / d centre scores (already times lambda_1)
     float *s_wc = s_dcl + TB * 2;                   // [2][E] W_cls, [2][F] W_clf, [2] b_clf
     int *s_flag = reinterpret_cast<int *>(s_wc + 2 * E + 2 * F + 4);   // [4] "this workgroup's classifier gradient arrived last"
+    if constexpr (WLDS && INFER) s_part = s_dcomb;  // (host-checked: kparts * TB * E <= (1 + R) * TB * ldE)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int S = a.n_split, tile_id = bid / S, sp = bid % S;
@@ -291,7 +296,7 @@ __device__ __forceinline__ void dense_tile_body(const DenseArgs &a, int bid, flo
                 v_agg[u] = acc / (float)a.cnt[agg_row[u]];
             }
         }
-        if constexpr (WLDS) {
+        if constexpr (WLDS && STAGE_W) {
             // the weight matrices as one list of rows [W_inter | W_intra[0] | ...] (contiguous in theta); thread -> (row, 16-B column chunk)
             const int c4 = E >> 2;
             const int cc = (tid % c4) * 4, r0 = tid / c4, rstep = DENSE_THREADS / c4;   // DENSE_THREADS % c4 == 0 (host-checked)
@@ -460,6 +465,7 @@ __device__ __forceinline__ void dense_tile_body(const DenseArgs &a, int bid, flo
     }
     __syncthreads();
     DENSE_STAMP(4);
+    if constexpr (INFER) return;
     if (!train) return;
 
     float *slab = acts_mode ? nullptr : a.slabs + (size_t)tile_id * a.n_params;

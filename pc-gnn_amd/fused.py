@@ -33,6 +33,7 @@ import ctypes as C
 import os
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -52,10 +53,46 @@ def default_list_capacity(g: DeviceGraph, B: int, max_list_bytes: int = 8 << 30)
     return int(max(cap, 1)), cap < worst
 
 
+def infer_row_caps(deg_host, thresholds, ids: Optional[np.ndarray] = None) -> np.ndarray:
+    """List entries a test-mode selection of each id can need, summed over the relations (pcg_sel_capacity_row with no minority
+    picks and no self, vectorised); ids=None: every node 0 .. n - 1, straight from the degree arrays."""
+    total = None
+    for r, deg in enumerate(deg_host):
+        d = (deg if ids is None else deg[ids]).astype(np.int64)
+        k = np.ceil(d * float(thresholds[r])).astype(np.int64)
+        cap = np.where(d > k + 1, k, d)
+        total = cap if total is None else total + cap
+    return total if total is not None else np.zeros(0, np.int64)
+
+
+def infer_chunks(caps: np.ndarray, chunk: int):
+    """Chunks [lo, hi) of `chunk` consecutive ids (the last one may be shorter) and the selection-list capacity that covers the
+    largest of them exactly (>= 1)."""
+    n = len(caps)
+    chunk = max(int(chunk), 1)
+    bounds = [(lo, min(lo + chunk, n)) for lo in range(0, n, chunk)]
+    if n == 0:
+        return bounds, 1
+    sums = np.add.reduceat(np.asarray(caps, dtype=np.int64), np.arange(0, n, chunk))
+    return bounds, max(int(sums.max()), 1)
+
+
+def default_infer_chunk(caps: np.ndarray, workspace_bytes, max_bytes: int, min_chunk: int = 16384) -> int:
+    """The whole set in one chunk if its workspace (workspace_bytes(chunk, list_capacity)) stays within max_bytes; else halved
+    until it does, down to min_chunk rows (never fewer, whatever the bound)."""
+    c = max(len(caps), 1)
+    while c > min_chunk:
+        nbytes = workspace_bytes(c, infer_chunks(caps, c)[1])
+        if 0 <= nbytes <= max_bytes:
+            break
+        c = max(min_chunk, (c + 1) // 2)
+    return c
+
+
 class FusedPCGNN:
     def __init__(self, model: PCALayer, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8,
                  max_batch: int = 1024, global_batch_scale: int = 1, list_capacity: Optional[int] = None,
-                 pipeline: Optional[bool] = None):
+                 pipeline: Optional[bool] = None, infer_workspace_bytes: int = 1 << 30):
         lib = _lib.load()
         self.lib = lib
         self.model = model
@@ -130,6 +167,13 @@ class FusedPCGNN:
         self.last_counts = None
         thr, rhos = ops._host_arrays(g, self.thresholds, self.rho)
         self._thr, self._rhos = thr, rhos
+        # infer(): a workspace of its own (score table, plan slots, data part, aggregates, counts, status word), grown on demand;
+        # its default chunk keeps the workspace within infer_workspace_bytes
+        self.infer_workspace_bytes = int(infer_workspace_bytes)
+        self._inf = {}
+        # utils.test / test_f1 evaluate through infer() - unless the caller bounded the selection list (list_capacity): infer()
+        # sizes its own list exactly, so such an engine keeps the per-batch predict loop, whose batches report an overflow
+        self.eval_by_infer = list_capacity is None
 
     # ------------------------------------------------------------------
     def _alloc(self, B: int):
@@ -855,6 +899,10 @@ class FusedPCGNN:
         if st == 0:
             return
         self.status.zero_()
+        self._raise_status(st)
+
+    @staticmethod
+    def _raise_status(st: int):
         what = []
         if st & _lib.PCG_ST_SEL_OVERFLOW:
             what.append("selection list overflow: a batch needed more list entries than the workspace holds - raise "
@@ -916,3 +964,53 @@ class FusedPCGNN:
         self._enqueue_tail(ids, None, B, agg, plan, False, combined=comb)
         res = (self.logits[:B].clone(), self.center[:B].clone())
         return res + (comb,) if want_combined else res
+
+    def infer(self, ids=None, chunk: Optional[int] = None, want_center: bool = False):
+        """Test-mode logits of a whole node set in one call (pcg_infer_set): ONE score pass, then per chunk of ids plan ->
+        select -> gather -> a persistent forward-only dense launch.  ids: node ids (any order, duplicates allowed; a device
+        tensor, numpy array or list), None = every node 0 .. n_nodes - 1.  Returns the gnn logits [n, 2] (+ the label-aware
+        logits [n, 2] if want_center): bit for bit what ``predict(ids[b:b + B], None, False)`` returns batch by batch, for any
+        B and any chunk.  chunk: ids per chunk (default: all of them, or fewer - never under 16384 - if the workspace would
+        exceed infer_workspace_bytes).  The training engine is left alone: its score table, keys, plans, captured graphs and
+        buffer sizes are untouched (a deferred update is applied first, as predict does).  Synchronises once (the status word)."""
+        g, lib = self.g, self.lib
+        self.flush()
+        if ids is None:
+            n = g.n_nodes
+            ids_dev = self._inf.get("all_ids")
+            if ids_dev is None or ids_dev.numel() != n:
+                ids_dev = self._inf["all_ids"] = torch.arange(n, dtype=torch.int32, device=self.dev)
+            caps = infer_row_caps(g.deg_host, self.thresholds)
+        else:
+            ids_host = (ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)).reshape(-1).astype(np.int64)
+            n = int(ids_host.size)
+            if n and (ids_host.min() < 0 or ids_host.max() >= g.n_nodes):
+                raise ValueError(f"infer: ids outside 0 .. {g.n_nodes - 1}")
+            ids_dev = ops._i32(ids, self.dev).view(-1) if torch.is_tensor(ids) else \
+                torch.from_numpy(ids_host.astype(np.int32)).to(self.dev)
+            caps = infer_row_caps(g.deg_host, self.thresholds, ids_host)
+        logits = torch.empty(n, 2, dtype=torch.float32, device=self.dev)
+        center = torch.empty(n, 2, dtype=torch.float32, device=self.dev) if want_center else None
+        if n == 0:
+            return (logits, center) if want_center else logits
+        ws_bytes = lambda c, cap: int(lib.pcg_infer_workspace_bytes(g.desc_ref(), self.E, c, cap))
+        chunk = default_infer_chunk(caps, ws_bytes, self.infer_workspace_bytes) if chunk is None else int(chunk)
+        chunk = max(1, min(chunk, n))
+        _, cap = infer_chunks(caps, chunk)
+        nbytes = ws_bytes(chunk, cap)
+        if nbytes < 0:
+            raise _lib.PcgnnLibraryError(f"pcg_infer_workspace_bytes rejected chunk {chunk} / list capacity {cap} ({nbytes})")
+        inf = self._inf
+        if inf.get("ws") is None or inf["ws"].numel() < nbytes:
+            inf["ws"] = None
+            inf["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        if inf.get("s0") is None:
+            inf["s0"] = torch.empty(g.n_nodes, dtype=torch.float32, device=self.dev)
+            inf["status"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        _lib.check(lib.pcg_infer_set(g.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk, _p(inf["s0"]), self._thr,
+                                     _p(inf["ws"]), cap, _p(logits), _p(center), _p(inf["status"]), self._stream()), "pcg_infer_set")
+        st = int(inf["status"].item())
+        if st:
+            inf["status"].zero_()
+            self._raise_status(st)
+        return (logits, center) if want_center else logits

@@ -4,7 +4,8 @@ training / evaluation loop touches them: ``test`` (:280-333), ``pos_neg_split`` 
 
 ``test`` keeps the reference's signature and return value; predictions stay on the device for the
 whole pass and come back in ONE copy (the reference copies every batch, :305), and the
-degenerate empty trailing batch its ``int(len/B)+1`` produces is not run.  Metrics are computed
+degenerate empty trailing batch its ``int(len/B)+1`` produces is not run.  A fused engine's pass is
+one ``FusedPCGNN.infer`` call (``predict_proba``).  Metrics are computed
 with numpy restatements of the sklearn functions the reference calls (checked against sklearn in
 the tests), so evaluation does not depend on sklearn being installed.
 """
@@ -55,26 +56,40 @@ def roc_auc(y_true, score) -> float:
     return float((ranks[y].sum() - n1 * (n1 + 1) / 2.0) / (n1 * n0))
 
 
+def predict_proba(test_nodes, model, batch_size: int, labels=None) -> np.ndarray:
+    """Test-mode class probabilities [n, 2] of ``test_nodes`` (sigmoid of the gnn logits, utils.py:305), on the host.
+    A FusedPCGNN runs its whole-set pass (``infer``: one call, one score pass) - test-mode results do not depend on how the
+    nodes are batched, so this is bit for bit the per-batch ``predict`` loop - unless it was given a selection-list capacity of
+    its own (``eval_by_infer`` False): then it is evaluated batch by batch under that capacity, as before.  ``batch_size``
+    batches those and the other models (``to_prob``, ``labels`` passed along)."""
+    nodes = np.asarray(test_nodes)
+    if len(nodes) == 0:
+        return np.zeros((0, 2), np.float32)
+    with torch.no_grad():
+        if getattr(model, "eval_by_infer", False):
+            ids = torch.as_tensor(nodes, dtype=torch.int32, device=model.dev)
+            return torch.sigmoid(model.infer(ids)).float().cpu().numpy()
+        fused = hasattr(model, "predict")                                   # FusedPCGNN: ids go to the device ONCE, batches are views
+        ids_dev = torch.as_tensor(nodes, dtype=torch.int32, device=model.dev) if fused else None
+        outs = []
+        for start in range(0, len(nodes), batch_size):                      # :298-303 (no empty trailing batch)
+            if fused:
+                outs.append(torch.sigmoid(model.predict(ids_dev[start:start + batch_size], None, False)[0]))
+            else:
+                blab = None if labels is None else np.asarray(labels)[start:start + batch_size]
+                outs.append(model.to_prob(nodes[start:start + batch_size].tolist(), blab, train_flag=False)[0])   # :305
+    return torch.cat(outs).float().cpu().numpy()
+
+
 def test(test_nodes, labels, model, batch_size: int, result=None, epoch: Optional[int] = None,
          epoch_best: Optional[int] = None, flag: Optional[str] = None,
          print_line: Optional[bool] = True) -> Tuple[float, float, float, float]:
     """Evaluate ``model`` (PCALayer / GCN / GraphSage mirror, or a FusedPCGNN) on ``test_nodes``:
     batched ``to_prob(..., train_flag=False)`` -> argmax / positive-class confidence -> metrics.
-    Returns (auc, recall, f1_macro, precision) like the reference (utils.py:333)."""
-    nodes = np.asarray(test_nodes)
+    Returns (auc, recall, f1_macro, precision) like the reference (utils.py:333).  Test-mode results do not depend on the
+    batching: a FusedPCGNN evaluates the whole set in one pass (predict_proba); ``batch_size`` batches the other models."""
     labels = np.asarray(labels)
-    outs = []
-    fused = hasattr(model, "predict")                                       # FusedPCGNN: ids go to the device ONCE, batches are views
-    ids_dev = torch.as_tensor(nodes, dtype=torch.int32, device=model.dev) if fused else None
-    with torch.no_grad():
-        for start in range(0, len(nodes), batch_size):                      # :298-303 (no empty trailing batch)
-            batch = nodes[start:start + batch_size]
-            blab = labels[start:start + batch_size]
-            if fused:
-                outs.append(torch.sigmoid(model.predict(ids_dev[start:start + batch_size], None, False)[0]))
-            else:
-                outs.append(model.to_prob(batch.tolist(), blab, train_flag=False)[0])   # :305
-    prob = torch.cat(outs).float().cpu().numpy() if outs else np.zeros((0, 2), np.float32)
+    prob = predict_proba(test_nodes, model, batch_size, labels)
     if hasattr(model, "check"):
         model.check()          # a batch that overflowed its selection list must not pass for a prediction
     pred = prob.argmax(axis=1)                                               # :306
@@ -120,19 +135,9 @@ def get_best_f1(labels, probs, thresholds=None) -> Tuple[float, float]:
 def test_f1(test_nodes, labels, model, batch_size: int, flag: str = "valid", valid_thresh: Optional[float] = None):
     """The "(f1)" evaluation (src/utils(f1).py:280-332): F1-macro at the best validation threshold (flag "valid":
     searched here and returned; otherwise ``valid_thresh`` is applied), the other metrics from the argmax prediction.
-    Returns (auc, recall, f1_macro, precision, threshold) like the reference."""
-    nodes = np.asarray(test_nodes)
+    Returns (auc, recall, f1_macro, precision, threshold) like the reference.  Probabilities as ``test`` (predict_proba)."""
     y = np.asarray(labels)
-    outs = []
-    with torch.no_grad():
-        for start in range(0, len(nodes), batch_size):
-            batch = nodes[start:start + batch_size]
-            if hasattr(model, "predict"):
-                ids = torch.as_tensor(batch, dtype=torch.int32, device=model.dev)
-                outs.append(torch.sigmoid(model.predict(ids, None, False)[0]))
-            else:
-                outs.append(model.to_prob(batch.tolist(), y[start:start + batch_size], train_flag=False)[0])
-    prob = torch.cat(outs).float().cpu().numpy() if outs else np.zeros((0, 2), np.float32)
+    prob = predict_proba(test_nodes, model, batch_size, y)
     if hasattr(model, "check"):
         model.check()
     threshold = None

@@ -1,0 +1,50 @@
+"""CPU checks of FusedPCGNN.infer's host-side planner: per-id list capacities (the exact pcg_sel_capacity_row sums of a test-mode
+selection) and chunk bounds."""
+from types import SimpleNamespace
+
+import numpy as np
+
+
+def graph(seed=0, n=500, R=3):
+    rs = np.random.RandomState(seed)
+    deg = [np.concatenate([rs.randint(0, 40, size=n - 3), [0, 1, 5000]]).astype(np.int64) for _ in range(R)]
+    return SimpleNamespace(R=R, deg_host=deg, n_pos=17)
+
+
+def test_row_caps_are_the_exact_sel_capacity_sums():
+    from pcgnn_amd import ops
+    from pcgnn_amd.fused import infer_row_caps
+    g = graph()
+    thr = [0.2, 0.5, 0.8]
+    rs = np.random.RandomState(1)
+    ids = rs.randint(0, 500, size=777)                                  # (any order, duplicates)
+    want = ops.sel_capacity(g, ids, None, thr, 0.5, train_flag=False).sum(axis=0)
+    assert np.array_equal(infer_row_caps(g.deg_host, thr, ids), want)
+    # ids=None: every node, straight from the degree arrays
+    want_all = ops.sel_capacity(g, np.arange(500), None, thr, 0.5, train_flag=False).sum(axis=0)
+    assert np.array_equal(infer_row_caps(g.deg_host, thr), want_all)
+
+
+def test_chunks_cover_every_id_once_and_capacity_is_the_largest_chunk():
+    from pcgnn_amd.fused import infer_chunks
+    rs = np.random.RandomState(2)
+    caps = rs.randint(0, 100, size=1001).astype(np.int64)
+    for chunk in (1, 16, 333, 1000, 1001, 5000):
+        bounds, cap = infer_chunks(caps, chunk)
+        covered = np.concatenate([np.arange(lo, hi) for lo, hi in bounds])
+        assert np.array_equal(covered, np.arange(len(caps)))
+        assert all(hi - lo == chunk for lo, hi in bounds[:-1]) and 0 < bounds[-1][1] - bounds[-1][0] <= chunk
+        assert cap == max(int(caps[lo:hi].sum()) for lo, hi in bounds)
+    assert infer_chunks(np.zeros(0, np.int64), 16) == ([], 1)
+    assert infer_chunks(np.zeros(5, np.int64), 16)[1] == 1               # (a capacity of at least one entry)
+
+
+def test_default_chunk_keeps_the_workspace_within_its_bound():
+    from pcgnn_amd.fused import default_infer_chunk
+    caps = np.full(100_000, 10, np.int64)
+    ws = lambda c, cap: 100 * c + 4 * cap                               # (a workspace that grows with the chunk)
+    assert default_infer_chunk(caps, ws, 1 << 40) == 100_000            # whole set: one chunk
+    c = default_infer_chunk(caps, ws, 3_000_000)
+    assert 16384 <= c < 100_000 and ws(c, 10 * c) <= 3_000_000
+    assert default_infer_chunk(caps, ws, 10) == 16384                   # never under 16384 rows
+    assert default_infer_chunk(caps[:1000], ws, 10) == 1000             # (a set smaller than that: one chunk)
