@@ -497,6 +497,26 @@ int pcg_infer_set(const pcg_graph_desc *g, const float *theta, int32_t emb, cons
                   float *s0, const double *thresholds, void *workspace, int64_t list_capacity, float *out_logits, float *out_center,
                   uint32_t *status, void *stream);
 int32_t pcg_infer_blocks(int32_t chunk_rows);   /* workgroups of the dense launch of a chunk of chunk_rows ids (host helper) */
+/* Partitioned whole-set inference (pc-gnn_amd/dist.py, DistributedPCGNN.infer): the device work of ONE chunk of a rank's ids,
+ * after the chunk's halo exchange (pcg_halo_collect on the inference halo's own table / counts / request list halo_ids, two
+ * all-to-alls, pcg_halo_serve) has filled halo_X [halo_cap][feat_stride].  g is the rank's table [owned | train-pos | ...]
+ * (hi - lo owned rows, g->n_pos replicated train-pos rows; CSR rows with global neighbour ids); ids [B] are local rows of owned
+ * nodes.  Launches: a front (the halo rows' scores -> s0[halo_ids[i]], and when `first` is set also rows [0, n_table_rows) ->
+ * s0[row_gid[row]]; s0 is indexed by global node id; the look-back words of the plan slot zeroed) -> plan (test mode) ->
+ * select (centre b's score s0[ids[b] + lo]; lists of global ids) -> gather (ids translated with the inference table - owned:
+ * id - lo, train-pos: pos_idx, fetched: halo_X row - multi-chunk rows left as partial sums) -> infer_dense_kernel.
+ * out_logits / out_center [B][2] (out_center may be NULL).  workspace: pcg_infer_dist_workspace_bytes(g, emb, chunk_rows,
+ * list_capacity), B <= chunk_rows; list_capacity must cover the chunk's sum of test-mode row capacities (else
+ * PCG_ST_SEL_OVERFLOW in *status); an id in none of owned / train-pos / fetched sets bit 4 of counts[128].  B == 0: nothing.
+ * Parity: every logit is bit for bit pcg_infer_set's for the same node on the whole graph with the same theta (scores are the
+ * row's own arithmetic; lists, gather chunks and dense sums are laid out per row; the translation changes addresses only). */
+int64_t pcg_infer_dist_workspace_bytes(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity);
+int pcg_infer_chunk_dist(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *ids, int32_t B, int32_t first,
+                         const int32_t *row_gid, int64_t n_table_rows, const float *halo_X, const int32_t *halo_ids, int32_t halo_cap,
+                         int32_t lo, int32_t hi, const int32_t *pos_ids, const int32_t *pos_idx, const uint32_t *table,
+                         int64_t table_slots, uint32_t *counts, float *s0, const double *thresholds, void *workspace,
+                         int32_t chunk_rows, int64_t list_capacity, float *out_logits, float *out_center, uint32_t *status,
+                         void *stream);
 int pcg_step_front_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, float *s0,
                          uint64_t *pos_keys, const int32_t *nodes, const int32_t *labels, int32_t B,
                          const double *thresholds, const double *rho, int32_t add_self, void *workspace,

@@ -63,8 +63,12 @@ __device__ __forceinline__ void store_row(float *out, const float4 (&acc)[NACC],
 }
 
 // workgroup `block` of `n_blocks` (256 threads each)
-template <int NACC, bool MAP = false>
-__device__ __forceinline__ void gather_chunks_body(const AggArgs &a, uint32_t block, uint32_t n_blocks) {
+// HALO_X (partitioned inference, pcg_infer_chunk_dist; needs MAP): translated rows >= a.hm.halo_base are read from halo_X (row
+// - halo_base, stride feat_stride) instead of a.X - the inference halo lives in a buffer of its own.  The training
+// instantiations leave it false: their code is what it was before the flag existed.
+template <int NACC, bool MAP = false, bool HALO_X = false>
+__device__ __forceinline__ void gather_chunks_body(const AggArgs &a, uint32_t block, uint32_t n_blocks,
+                                                   const float *__restrict__ halo_X = nullptr) {
     const int lane = lane_id();
     const RowGeom q = row_geom(a.feat_stride, lane);
     const uint32_t nwaves = n_blocks * (blockDim.x >> 6);
@@ -111,6 +115,11 @@ __device__ __forceinline__ void gather_chunks_body(const AggArgs &a, uint32_t bl
                 bad |= beyond;
                 ids[u] |= beyond ? (int)0x80000000 : 0;
                 const float *rowp = a.X + (size_t)(ids[u] >= 0 ? ids[u] : 0) * a.feat_stride;
+                if constexpr (HALO_X) {            // (a select between two addresses: the load stays unconditional)
+                    // (from the clamped row: a hole's id has the sign bit set, and id - halo_base would wrap around)
+                    const int hr = (ids[u] >= 0 ? ids[u] : 0) - a.hm.halo_base;
+                    rowp = hr >= 0 ? halo_X + (size_t)hr * a.feat_stride : rowp;
+                }
 #pragma unroll
                 for (int x = 0; x < NACC; ++x) {
                     const int c4 = x * q.lpr + q.sub;
@@ -178,6 +187,13 @@ __global__ void __launch_bounds__(256) gather_chunks_dist(const AggArgs a, const
     if (sc.dst && blockIdx.x == 0)
         for (int i = (int)threadIdx.x; i < 3 * sc.n; i += 256) sc.dst[i] = sc.src[i / sc.n][i % sc.n];
     gather_chunks_body<NACC, true>(a, blockIdx.x, gridDim.x);
+}
+
+// The gather of a partitioned rank's INFERENCE chunk (pcg_infer_chunk_dist): node ids translated with the inference halo's
+// hash table, fetched rows read from the inference halo buffer
+template <int NACC>
+__global__ void __launch_bounds__(256) gather_chunks_infer(const AggArgs a, const float *__restrict__ halo_X) {
+    gather_chunks_body<NACC, true, true>(a, blockIdx.x, gridDim.x, halo_X);
 }
 
 // The gather launch of a TRAINING step, with what else fits beside it (SideJob, choose.h): workgroups
@@ -334,6 +350,25 @@ int launch_gather_train(const float *X, int32_t feat_dim, int32_t feat_stride, i
         hipLaunchKernelGGL(gather_train_kernel<1>, dim3(gb + extra), dim3(256), 0, st, a, side, gb, g->n_nodes, g->train_pos, g->n_pos);
     else
         hipLaunchKernelGGL(gather_train_kernel<2>, dim3(gb + extra), dim3(256), 0, st, a, side, gb, g->n_nodes, g->train_pos, g->n_pos);
+    PCG_LAUNCH_CHECK();
+    return PCG_OK;
+}
+
+// (declared in infer.hip) lists of node ids -> rows of [ owned | train-pos ] in X or of the inference halo (hm: its hash table,
+// halo_base = n_local + n_pos, halo_cap rows at halo_X); multi-chunk rows left as partial sums for the dense launch
+int launch_gather_infer(const float *X, int32_t feat_dim, int32_t feat_stride, int32_t n_rows, const int32_t *cnt, const Workspace &w,
+                        float *agg, int32_t agg_stride, uint32_t *status, const HaloMap &hm, const float *halo_X, hipStream_t st) {
+    if (!X || !cnt || !agg || !halo_X || n_rows < 1 || !hm.keys) return PCG_E_ARG;
+    if (feat_stride % 4 != 0 || feat_stride < feat_dim || agg_stride < feat_dim) return PCG_E_ARG;
+    if (feat_stride > 512) return PCG_E_UNSUPPORTED;
+    if (((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(halo_X)) & 15u) != 0) return PCG_E_ARG;
+    AggArgs a;
+    // (table_rows: every row number a translation can produce - the halo's rows are addressed in halo_X)
+    fill_agg_args(a, X, feat_dim, feat_stride, (int64_t)hm.halo_base + hm.halo_cap, n_rows, cnt, w, PCG_NORM_COUNT, agg, agg_stride,
+                  status);
+    a.hm = hm;
+    if (feat_stride <= 256) hipLaunchKernelGGL(gather_chunks_infer<1>, dim3(GATHER_BLOCKS), dim3(256), 0, st, a, halo_X);
+    else hipLaunchKernelGGL(gather_chunks_infer<2>, dim3(GATHER_BLOCKS), dim3(256), 0, st, a, halo_X);
     PCG_LAUNCH_CHECK();
     return PCG_OK;
 }

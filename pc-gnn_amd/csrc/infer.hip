@@ -14,6 +14,7 @@
 // lands in.  So the chunked pass leaves bit for bit what pcg_train_dense (forward only, labels NULL) leaves batch by batch.
 // Reference lines replaced: src/utils.py:298-305 (the batched evaluation loop), src/model.py:34-39 (PCALayer.forward).
 #include "dense.h"
+#include "halo_map.h"
 
 namespace pcg {
 
@@ -138,6 +139,60 @@ static int infer_carve(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows,
     return PCG_OK;
 }
 
+// ---- partitioned inference (pcg_infer_chunk_dist, pc-gnn_amd/dist.py) ------------------------------------------------------
+// gather.hip
+int launch_gather_infer(const float *X, int32_t feat_dim, int32_t feat_stride, int32_t n_rows, const int32_t *cnt, const Workspace &w,
+                        float *agg, int32_t agg_stride, uint32_t *status, const HaloMap &hm, const float *halo_X, hipStream_t st);
+
+// A chunk's front: workgroups [0, n_tab) score the rank's table rows [0, n_tab_rows) (owned | train-pos: the first chunk of a
+// call only) -> s0[tab_ids[row]]; [n_tab, n_tab + n_halo) score the inference halo rows -> s0[halo_ids[row]] (-1: unused slot,
+// skipped); the rest zero the look-back words of the chunk's plan slot.  score_table_body throughout: a row's score has the
+// bits pcg_score_table gives it on one GPU (the arithmetic is the row's alone: its lanes, fma chain and butterfly).
+__global__ void __launch_bounds__(256) infer_front_dist_kernel(const float *__restrict__ X, const float *__restrict__ halo_X,
+                                                               int feat_dim, int stride, const float *__restrict__ W,
+                                                               const float *__restrict__ bias, const int32_t *__restrict__ tab_ids,
+                                                               int64_t n_tab_rows, const int32_t *__restrict__ halo_ids,
+                                                               int64_t n_halo_rows, float *__restrict__ s0, int n_tab, int n_halo,
+                                                               const ZeroRegions z) {
+    int b = (int)blockIdx.x;
+    if (b < n_tab) {
+        score_table_body(X, feat_dim, stride, W, bias, 0, n_tab_rows, s0, b, n_tab, tab_ids);
+        return;
+    }
+    b -= n_tab;
+    if (b < n_halo) {
+        score_table_body(halo_X, feat_dim, stride, W, bias, 0, n_halo_rows, s0, b, n_halo, halo_ids);
+        return;
+    }
+    b -= n_halo;
+    const int64_t w0 = (int64_t)b * INFER_ZERO_WORDS;
+    for (int64_t i = w0 + threadIdx.x; i < w0 + INFER_ZERO_WORDS; i += blockDim.x) {
+        int64_t j = i;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (j >= 0 && j < z.n[k]) z.p[k][j] = 0u;
+            j -= z.n[k];
+        }
+    }
+}
+
+// the call's workspace: [plan slot (chunk_rows) | data part | agg [R][chunk][F] | cnt [R][chunk] | centre logits [chunk][2]];
+// a chunk of fewer rows carves its own layout inside the same bytes (every part grows with the rows)
+static int infer_dist_carve(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity, InferCarve &c) {
+    if (!g || chunk_rows < 1 || list_capacity < 1 || list_capacity >= (1ll << 31)) return PCG_E_ARG;
+    if (emb < 16 || emb % 16 != 0 || g->n_rel < 1 || g->n_rel > PCG_MAX_REL || g->feat_dim < 1) return PCG_E_UNSUPPORTED;
+    if ((int64_t)g->n_rel * chunk_rows >= (1ll << 31)) return PCG_E_ARG;
+    const CarveSizes sz = carve(g, chunk_rows, list_capacity, nullptr, nullptr, nullptr);
+    const int64_t R = g->n_rel, B = chunk_rows, F = g->feat_dim;
+    c.plan_bytes = sz.plan_bytes;
+    c.data = sz.plan_bytes;
+    c.agg = c.data + align256(sz.data_bytes);
+    c.cnt = c.agg + align256(4 * R * B * F);
+    c.center = c.cnt + align256(4 * R * B);
+    c.total = c.center + align256(8 * B);
+    return PCG_OK;
+}
+
 }  // namespace pcg
 
 extern "C" {
@@ -219,6 +274,88 @@ int pcg_infer_set(const pcg_graph_desc *g, const float *theta, int32_t emb, cons
         if (rc != PCG_OK) return rc;
     }
     return PCG_OK;
+}
+
+int64_t pcg_infer_dist_workspace_bytes(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity) {
+    pcg::InferCarve c;
+    const int rc = pcg::infer_dist_carve(g, emb, chunk_rows, list_capacity, c);
+    return rc != PCG_OK ? rc : c.total;
+}
+
+int pcg_infer_chunk_dist(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *ids, int32_t B, int32_t first,
+                         const int32_t *row_gid, int64_t n_table_rows, const float *halo_X, const int32_t *halo_ids, int32_t halo_cap,
+                         int32_t lo, int32_t hi, const int32_t *pos_ids, const int32_t *pos_idx, const uint32_t *table,
+                         int64_t table_slots, uint32_t *counts, float *s0, const double *thresholds, void *workspace,
+                         int32_t chunk_rows, int64_t list_capacity, float *out_logits, float *out_center, uint32_t *status,
+                         void *stream) {
+    if (!g || !g->X || !theta || !ids || B < 0 || B > chunk_rows || !row_gid || !halo_X || !halo_ids || halo_cap < 1 || !table ||
+        !counts || !s0 || !thresholds || !workspace || !out_logits || !status)
+        return PCG_E_ARG;
+    if (g->feat_dim < 1 || g->feat_stride < g->feat_dim || g->feat_stride % 4 != 0 || g->feat_stride > 512) return PCG_E_UNSUPPORTED;
+    if (((reinterpret_cast<uintptr_t>(g->X) | reinterpret_cast<uintptr_t>(halo_X)) & 15u) != 0) return PCG_E_ARG;
+    const int64_t n_local = (int64_t)hi - lo, halo_base = n_local + g->n_pos;
+    if (lo < 0 || n_local < 0 || n_table_rows < 0 || n_table_rows > g->n_nodes || halo_base > g->n_nodes) return PCG_E_ARG;
+    if (table_slots < 1024 || (table_slots & (table_slots - 1)) != 0 || (g->n_pos > 0 && (!pos_ids || !pos_idx))) return PCG_E_ARG;
+    pcg::InferCarve c;
+    int rc = pcg::infer_dist_carve(g, emb, chunk_rows, list_capacity, c);
+    if (rc != PCG_OK) return rc;
+    const int F = g->feat_dim, E = emb, R = g->n_rel;
+    if (pcg::dense_smem_bytes(F, E, R, pcg::infer_wlds(F, E, R)) > 160 * 1024) return PCG_E_UNSUPPORTED;
+    if (B == 0) return PCG_OK;
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    unsigned char *plan = ws, *data = ws + c.data;
+    float *agg = reinterpret_cast<float *>(ws + c.agg);
+    int32_t *cnt = reinterpret_cast<int32_t *>(ws + c.cnt);
+    float *center_scratch = reinterpret_cast<float *>(ws + c.center);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    pcg::Workspace w;
+    pcg::carve1(g, B, list_capacity, data, &w, plan);
+
+    // front: halo scores (+ the table's on the first chunk) || the look-back words of this chunk's plan layout
+    pcg::ZeroRegions z = {};
+    z.p[0] = w.counters;                                          // counters | heads: contiguous (256 + 512 bytes)
+    z.n[0] = (reinterpret_cast<unsigned char *>(w.heads) - reinterpret_cast<unsigned char *>(w.counters) + 4 * 8 * 16) / 4;
+    z.p[1] = reinterpret_cast<uint32_t *>(w.plan_totals);
+    z.n[1] = 64 * ((int64_t)R * B / 256 + 2) / 4;
+    const int n_zero = (int)((z.n[0] + z.n[1] + pcg::INFER_ZERO_WORDS - 1) / pcg::INFER_ZERO_WORDS);
+    const int64_t tab_rows = first ? n_table_rows : 0;
+    const int n_tab = tab_rows > 0 ? (int)pcg::score_table_blocks(tab_rows, g->feat_stride) : 0;
+    const int n_halo = (int)pcg::score_table_blocks(halo_cap, g->feat_stride);
+    hipLaunchKernelGGL(pcg::infer_front_dist_kernel, dim3(n_tab + n_halo + n_zero), dim3(256), 0, st, g->X, halo_X, g->feat_dim,
+                       g->feat_stride, theta + pcg::off_clf(F, E, R), theta + pcg::off_bias(F, E, R), row_gid, tab_rows, halo_ids,
+                       (int64_t)halo_cap, s0, n_tab, n_halo, z);
+    PCG_LAUNCH_CHECK();
+    // plan (test mode) -> select (centre scores by global id: s0[ids[b] + lo]; lists of global ids)
+    rc = pcg_plan_epochs(g, ids, nullptr, B, 1, B, thresholds, nullptr, 0, 0, plan, c.plan_bytes, list_capacity, status, nullptr,
+                         stream);
+    if (rc != PCG_OK) return rc;
+    rc = pcg_choose_select_planned(g, ids, nullptr, B, s0, nullptr, nullptr, thresholds, nullptr, 0, 0, cnt, data, plan,
+                                   list_capacity, status, nullptr, lo, stream);
+    if (rc != PCG_OK) return rc;
+    // gather: ids -> owned / train-pos rows of g->X, fetched rows of the inference halo (its own hash table)
+    pcg::HaloMap hm;
+    hm.keys = table;
+    hm.vals = table + table_slots;
+    hm.mask = (uint32_t)(table_slots - 1);
+    hm.lo = lo; hm.hi = hi; hm.n_local = (int32_t)n_local;
+    hm.pos_ids = pos_ids; hm.pos_idx = pos_idx; hm.n_pos = g->n_pos;
+    hm.halo_cap = halo_cap; hm.halo_base = (int32_t)halo_base;
+    hm.overflow = counts + 128;
+    rc = pcg::launch_gather_infer(g->X, F, g->feat_stride, R * B, cnt, w, agg, F, status, hm, halo_X, st);
+    if (rc != PCG_OK) return rc;
+    // dense: the centres are local table rows
+    pcg::DenseExtra x;
+    x.chunk_begin = w.chunk_begin;
+    x.partial = w.partial;
+    x.cnt = cnt;
+    x.partial_stride = g->feat_stride;
+    pcg::DenseArgs a;
+    int n_sort_blocks = 0;
+    rc = pcg::dense_args(a, n_sort_blocks, g, theta, emb, ids, nullptr, B, agg, F, 0.f, 1.f, out_logits,
+                         out_center ? out_center : center_scratch, nullptr, nullptr, nullptr, nullptr, x);
+    if (rc != PCG_OK) return rc;
+    a.stamps = nullptr;
+    return pcg::launch_infer_dense(a, B, st);
 }
 
 }  // extern "C"

@@ -133,6 +133,96 @@ def expected_halo_rows(deg_rel_train_local: Sequence[np.ndarray], weights: np.nd
     return int(min(n_remote, math.ceil(distinct * margin + 1024)))
 
 
+def infer_remote_pairs(csr_host, bounds, rank: int, pos_sorted: np.ndarray, ids: np.ndarray):
+    """What a list of ids (local rows; any order, duplicates allowed) asks of the other ranks: the distinct (position in ids,
+    neighbour id) pairs of every remote, non-train-pos neighbour over all relations of csr_host (this rank's rows, global
+    neighbour ids), ordered by position (then id).  Train positives are replicated (never fetched).  Returns (pos, nbr)."""
+    bounds = np.asarray(bounds, dtype=np.int64)
+    lo, hi = int(bounds[rank]), int(bounds[rank + 1])
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    pos_sorted = np.asarray(pos_sorted, dtype=np.int64).reshape(-1)
+    keys = []
+    if lo == 0 and hi == int(bounds[-1]):                     # (one rank owns everything: nothing is remote)
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    for indptr, idx in csr_host:
+        beg = np.asarray(indptr, dtype=np.int64)[ids]
+        deg = np.asarray(indptr, dtype=np.int64)[ids + 1] - beg
+        tot = int(deg.sum())
+        if tot == 0:
+            continue
+        at = np.repeat(np.arange(ids.size, dtype=np.int64), deg)
+        off = np.arange(tot, dtype=np.int64) - np.repeat(np.cumsum(deg) - deg, deg)
+        nb = np.asarray(idx)[np.repeat(beg, deg) + off].astype(np.int64)
+        keep = (nb < lo) | (nb >= hi)
+        if pos_sorted.size:
+            j = np.minimum(np.searchsorted(pos_sorted, nb), pos_sorted.size - 1)
+            keep &= pos_sorted[j] != nb
+        keys.append(at[keep] * int(bounds[-1]) + nb[keep])
+    if not keys:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    u = np.unique(np.concatenate(keys))
+    return u // int(bounds[-1]), u % int(bounds[-1])
+
+
+def infer_pitch(pairs, bounds, budget_rows: int) -> int:
+    """Inference halo rows per owner: what the whole id set asks of its busiest owner, at most budget_rows - but never less
+    than the most one row asks of one owner (a chunk holds at least one row); >= 1."""
+    pos, nbr = pairs
+    if nbr.size == 0:
+        return 1
+    bounds = np.asarray(bounds, dtype=np.int64)
+    world = bounds.size - 1
+    own = np.searchsorted(bounds[1:-1], nbr, side="right")
+    row_most = int(np.unique(pos * world + own, return_counts=True)[1].max())
+    set_most = int(np.bincount(np.searchsorted(bounds[1:-1], np.unique(nbr), side="right"), minlength=world).max())
+    return max(row_most, min(int(budget_rows), set_most), 1)
+
+
+def plan_infer_chunks(csr_host, bounds, rank: int, pos_sorted: np.ndarray, ids: np.ndarray, pitch: int, max_rows: int,
+                      thresholds, pairs=None):
+    """Cut ids (local rows, in their given order) into chunks [a, b) of at most max_rows ids whose distinct remote, non-train-pos
+    neighbours number at most `pitch` per owner (so the chunk's halo exchange cannot overflow; pitch >= infer_pitch's single-row
+    demand), each as long as both allow.  Returns (chunks, list_capacity): the selection-list capacity that covers the largest
+    chunk's test-mode lists exactly (fused.infer_row_caps; >= 1)."""
+    from .fused import infer_row_caps
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    n = ids.size
+    if n == 0:
+        return [], 1
+    max_rows, pitch = max(int(max_rows), 1), int(pitch)
+    bounds = np.asarray(bounds, dtype=np.int64)
+    pos, nbr = infer_remote_pairs(csr_host, bounds, rank, pos_sorted, ids) if pairs is None else pairs
+    own = np.searchsorted(bounds[1:-1], nbr, side="right")
+    # previous position that asks for the same id (-1: none) - a pair is new to a chunk starting at s iff prev < s
+    prev = np.full(nbr.size, -1, np.int64)
+    if nbr.size:
+        o = np.lexsort((pos, nbr))
+        same = nbr[o][1:] == nbr[o][:-1]
+        prev[o[1:][same]] = pos[o][:-1][same]
+    row_first = np.searchsorted(pos, np.arange(n + 1))       # pairs of position i: [row_first[i], row_first[i + 1])
+    chunks, a = [], 0
+    while a < n:
+        b = min(a + max_rows, n)
+        sel = np.arange(row_first[a], row_first[b])
+        sel = sel[prev[sel] < a]
+        if sel.size:
+            o = own[sel]
+            order = np.argsort(o, kind="stable")
+            so = o[order]
+            start = np.searchsorted(so, so, side="left")
+            rank_in = np.empty(sel.size, np.int64)
+            rank_in[order] = np.arange(sel.size) - start
+            over = sel[rank_in >= pitch]
+            if over.size:
+                b = int(pos[over.min()])
+                assert b > a, "pitch below one row's demand"
+        chunks.append((a, b))
+        a = b
+    caps = infer_row_caps([np.diff(np.asarray(ip)) for ip, _ in csr_host], thresholds, ids)
+    cap = max(int(max(caps[a:b].sum() for a, b in chunks)), 1)
+    return chunks, cap
+
+
 class HaloExchange:
     """The halo exchange of a WINDOW of steps, on any device / backend (plain ``torch`` + ``torch.distributed``).
 
@@ -148,14 +238,16 @@ class HaloExchange:
     device tensors)."""
 
     def __init__(self, part: Partition, X_ext: torch.Tensor, train_pos: Sequence[int], pitch: Optional[int] = None, group=None,
-                 stage_host: bool = False, req_out: Optional[torch.Tensor] = None):
+                 stage_host: bool = False, req_out: Optional[torch.Tensor] = None, halo: Optional[torch.Tensor] = None):
+        """halo: a buffer of its own for the halo region (rows numbered from halo_base all the same; X_ext then needs only the
+        owned and train-pos rows) - the inference halo of DistributedPCGNN.infer"""
         self.part, self.X_ext, self.P = part, X_ext, len(train_pos)
         self.group, self.stage_host = group, stage_host
         dev = X_ext.device
         tp = torch.as_tensor(np.asarray(list(train_pos), dtype=np.int64), device=dev)
         self.pos_ids, self.pos_idx = torch.sort(tp) if self.P else (tp, tp)
         self.halo_base = part.n_local + self.P
-        self.halo_cap = X_ext.shape[0] - self.halo_base
+        self.halo_cap = X_ext.shape[0] - self.halo_base if halo is None else int(halo.shape[0])
         self.peers = max(part.world - 1, 1)
         self.pitch = int(pitch) if pitch is not None else self.halo_cap // self.peers
         assert self.pitch >= 1 and self.halo_cap == self.peers * self.pitch, "the halo region is (world - 1) x pitch rows"
@@ -169,7 +261,7 @@ class HaloExchange:
         self.req_out.fill_(-1)
         self.req_in = torch.full((self.halo_cap,), -1, dtype=torch.int32, device=dev)
         self.rows_out = torch.zeros(self.halo_cap, X_ext.shape[1], dtype=torch.float32, device=dev)
-        self.halo_rows = X_ext[self.halo_base:self.halo_base + self.halo_cap]
+        self.halo_rows = X_ext[self.halo_base:self.halo_base + self.halo_cap] if halo is None else halo
         self._uniq = torch.zeros(0, dtype=torch.int64, device=dev)
         self._slot = torch.zeros(0, dtype=torch.int64, device=dev)
 
@@ -273,8 +365,9 @@ class HaloExchangeHip(HaloExchange):
     """The same exchange with the list / CSR work done by HIP kernels (pcg_halo_collect: hash-table de-duplication sized by
     the halo capacity; pcg_halo_serve; pcg_halo_lookup).  No host synchronisation anywhere."""
 
-    def __init__(self, part, X_ext, train_pos, pitch: int, group=None, stage_host=False, req_out: Optional[torch.Tensor] = None):
-        super().__init__(part, X_ext, train_pos, pitch, group, stage_host, req_out)
+    def __init__(self, part, X_ext, train_pos, pitch: int, group=None, stage_host=False, req_out: Optional[torch.Tensor] = None,
+                 halo: Optional[torch.Tensor] = None):
+        super().__init__(part, X_ext, train_pos, pitch, group, stage_host, req_out, halo)
         from . import _lib, ops
         self._lib, self._ops = _lib, ops
         dev = X_ext.device
@@ -283,12 +376,14 @@ class HaloExchangeHip(HaloExchange):
         self.bounds_dev = part.bounds(dev).to(torch.int32)
         self.pos_ids32, self.pos_idx32 = self.pos_ids.to(torch.int32), self.pos_idx.to(torch.int32)
 
-    def collect(self, graph, centres: torch.Tensor):
+    def collect(self, graph, centres: torch.Tensor, n: Optional[int] = None):
+        """n: centres to walk (default: all of them; 0 with a one-element tensor - an empty tensor has no address - resets the
+        table and the request list only)"""
         lib, ops, part = self._lib.load(), self._ops, self.part
         _p = ops._p
         centres = centres.to(torch.int32).contiguous()
         self._lib.check(lib.pcg_halo_collect(
-            graph.desc_ref(), _p(centres), centres.numel(), part.lo, part.hi, part.n_local, _p(self.pos_ids32), self.P,
+            graph.desc_ref(), _p(centres), centres.numel() if n is None else int(n), part.lo, part.hi, part.n_local, _p(self.pos_ids32), self.P,
             _p(self.bounds_dev), part.world, _p(self.table), self.slots, _p(self.counts), _p(self.req_out), self.halo_cap,
             self.halo_base, self.pitch, part.rank, ops._stream(self.X_ext.device)), "pcg_halo_collect")
 
@@ -314,10 +409,13 @@ class DistributedPCGNN:
     """The step driver of one rank of a node-partitioned run (HIP kernels + RCCL)."""
 
     def __init__(self, w, model_cfg: dict, device, group=None, stage_host: bool = False, halo_rows: Optional[int] = None,
-                 halo_pitch: Optional[int] = None, balanced: bool = True, window: int = 8):
+                 halo_pitch: Optional[int] = None, balanced: bool = True, window: int = 8, infer_workspace_bytes: int = 1 << 30,
+                 infer_halo_bytes: int = 256 << 20):
         """window: steps per halo prefetch (begin_window) the default capacities are sized for;
         halo_rows: distinct remote rows a window is expected to need (default: from window x batch centres' neighbourhoods);
-        halo_pitch: rows reserved per owner (default: from halo_rows); the halo region is (world - 1) x halo_pitch rows."""
+        halo_pitch: rows reserved per owner (default: from halo_rows); the halo region is (world - 1) x halo_pitch rows.
+        infer_workspace_bytes / infer_halo_bytes: what infer()'s default chunk keeps its workspace within / its default halo
+        pitch keeps the inference halo (its serve and row buffers) within."""
         from . import _lib, ops
         from .graph import DeviceGraph
         from .sampler import PickSampler
@@ -459,6 +557,10 @@ class DistributedPCGNN:
         # launch and nothing else - no eager collective, no second host call per step.  Probed once (a captured all-reduce of
         # eight floats, replayed and checked) and only used if every rank's probe passed; PCG_DIST_GRAPH_COLLECTIVES=0 turns it off.
         self.collectives_in_graph = self._probe_collective_capture()
+        # infer(): buffers of its own (halo exchange, score vector, workspace, status word), grown on demand; the training state
+        # is never touched by it
+        self.infer_workspace_bytes, self.infer_halo_bytes = int(infer_workspace_bytes), int(infer_halo_bytes)
+        self._inf = {}
         import os
         # a whole window as ONE graph (train_window): on by default at world size 1 - where its all-to-alls are copies -, opt-in
         # (PCG_DIST_WINDOW_GRAPH=1) beyond: there they are grouped send / receive pairs, a capture path that no one-GPU box can
@@ -808,6 +910,182 @@ class DistributedPCGNN:
             if lists:
                 what.append(f"selection list (status {lists}) - raise the list capacity")
             raise RuntimeError("partitioned step over capacity on some rank: " + "; ".join(what))
+
+    # -- whole-set inference ------------------------------------------------------------------------
+    def infer(self, ids_local=None, chunk: Optional[int] = None, want_center: bool = False, halo_rows: Optional[int] = None):
+        """COLLECTIVE.  Test-mode logits of this rank's ids: the gnn logits [n, 2] (+ the label-aware logits [n, 2] if
+        want_center), bit for bit what FusedPCGNN.infer gives the same global ids on the whole graph with the same theta.
+        ids_local: local rows of owned nodes (any order, duplicates allowed, may be empty; a device tensor, numpy array or
+        list), None = every owned node.  The ids are cut into chunks (plan_infer_chunks) whose remote demand fits the inference
+        halo - (world - 1) x pitch rows of its own, pitch from halo_rows (default: infer_halo_bytes) and never below what one
+        row asks of one owner; chunk: ids per chunk at most (default: all, or fewer if the workspace would exceed
+        infer_workspace_bytes).  Every rank runs the same number of chunks with the same pitch (agreed), each one halo exchange
+        (collect, two all-to-alls, serve) + pcg_infer_chunk_dist.  A pending update is applied first (flush); nothing else of the
+        training state - scores, keys, halo, plans, lists, captured graphs - is touched.  Synchronises once; if any rank's
+        lists or halo went over capacity, every rank raises."""
+        g, part, lib, _p = self.g, self.part, self.lib, self.ops._p
+        self.flush()
+        inf = self._inf
+        if ids_local is None:
+            ids_host = inf.get("all_host")
+            if ids_host is None:
+                ids_host = inf["all_host"] = np.arange(part.n_local, dtype=np.int64)
+                inf["all_dev"] = torch.arange(part.n_local, dtype=torch.int32, device=self.dev)
+            ids_dev = inf["all_dev"]
+        else:
+            ids_host = (ids_local.detach().cpu().numpy() if torch.is_tensor(ids_local) else np.asarray(ids_local)).reshape(-1)
+            ids_host = ids_host.astype(np.int64)
+            if ids_host.size and (ids_host.min() < 0 or ids_host.max() >= part.n_local):
+                raise ValueError(f"infer: ids_local outside 0 .. {part.n_local - 1}")
+            ids_dev = torch.from_numpy(ids_host.astype(np.int32)).to(self.dev)
+        n = int(ids_host.size)
+        # the halo pitch: the same on every rank (equal-split all-to-alls)
+        if ids_local is None:
+            pairs = inf.get("all_pairs")
+            if pairs is None:
+                pairs = inf["all_pairs"] = infer_remote_pairs(self.csr_host, part.bounds_host, part.rank, self._pos_sorted(), ids_host)
+        else:
+            pairs = infer_remote_pairs(self.csr_host, part.bounds_host, part.rank, self._pos_sorted(), ids_host)
+        peers = max(self.world - 1, 1)
+        row_bytes = 2 * 4 * g.X.shape[1]                         # serve buffer + halo buffer
+        budget = int(halo_rows) if halo_rows is not None else self.infer_halo_bytes // row_bytes
+        # (0: no rank's ids name a remote node - at world size 1 always -: no exchange at all, an empty halo)
+        pitch = self._agree_max(infer_pitch(pairs, part.bounds_host, max(budget // peers, 1)) if pairs[1].size else 0)
+        exchange = pitch > 0
+        pitch = max(pitch, 1)
+        # the chunks (cached for the owned set: its rows never change) and how many every rank runs
+        from .fused import default_infer_chunk, infer_row_caps
+        ws_bytes = lambda c, cap: int(lib.pcg_infer_dist_workspace_bytes(g.desc_ref(), self.E, c, cap))
+        if chunk is None:
+            caps = infer_row_caps([np.diff(ip) for ip, _ in self.csr_host], self.thresholds, ids_host)
+            chunk = default_infer_chunk(caps, ws_bytes, self.infer_workspace_bytes)
+        key = ("plan", pitch, int(chunk))
+        plan = inf.get(key) if ids_local is None else None
+        if plan is None:
+            plan = plan_infer_chunks(self.csr_host, part.bounds_host, part.rank, self._pos_sorted(), ids_host, pitch, int(chunk),
+                                     self.thresholds, pairs)
+            if ids_local is None:
+                inf[key] = plan
+        chunks, cap = plan
+        n_chunks = self._agree_max(len(chunks))
+        logits = torch.empty(n, 2, dtype=torch.float32, device=self.dev)
+        center = torch.empty(n, 2, dtype=torch.float32, device=self.dev) if want_center else None
+        h = self._infer_halo(pitch)
+        rows = max([b - a for a, b in chunks], default=1)
+        nbytes = ws_bytes(rows, cap)
+        if nbytes < 0:
+            raise self._libmod.PcgnnLibraryError(f"pcg_infer_dist_workspace_bytes rejected chunk {rows} / list capacity {cap} ({nbytes})")
+        if inf.get("ws") is None or inf["ws"].numel() < nbytes:
+            inf["ws"] = None
+            inf["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        if inf.get("s0") is None:
+            inf["s0"] = torch.zeros(self.s0_full.numel(), dtype=torch.float32, device=self.dev)
+            inf["status"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
+            inf["none"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        st = self.ops._stream(self.dev)
+        if not exchange:
+            h.collect(g, inf["none"], 0)                    # (an empty table: every id is owned or a train positive)
+        for k in range(n_chunks):
+            a, b = chunks[k] if k < len(chunks) else (n, n)
+            cid = ids_dev[a:b] if b > a else None
+            if exchange:
+                if cid is None:                             # a rank out of chunks takes part in the exchange with nothing
+                    h.collect(g, inf["none"], 0)
+                else:
+                    h.collect(g, cid)
+                h.exchange_ids()
+                h.serve(g)
+                h.exchange_rows()
+            if cid is None:
+                continue
+            self._libmod.check(lib.pcg_infer_chunk_dist(
+                g.desc_ref(), _p(self.theta), self.E, _p(cid), b - a, 1 if k == 0 else 0, _p(self.row_gid), part.n_local + g.n_pos,
+                _p(h.halo_rows), _p(h.req_out), h.halo_cap, part.lo, part.hi, _p(h.pos_ids32), _p(h.pos_idx32), _p(h.table), h.slots,
+                _p(h.counts), _p(inf["s0"]), self._thr, _p(inf["ws"]), rows, cap, _p(logits[a:b]),
+                _p(center[a:b]) if center is not None else None, _p(inf["status"]), st), "pcg_infer_chunk_dist")
+        halo, lists = self._agree_flags(h.overflow_word, inf["status"])
+        if halo or lists:
+            what = []
+            if halo:
+                what.append(f"inference halo (flags {halo}, pitch {pitch})")
+            if lists:
+                what.append(f"selection list (status {lists}, capacity {cap})")
+            raise RuntimeError("partitioned inference over capacity on some rank: " + "; ".join(what))
+        return (logits, center) if want_center else logits
+
+    def infer_all(self, want_center: bool = False):
+        """COLLECTIVE.  The test-mode logits of EVERY node of the graph, in global id order, on every rank (infer(None) on each
+        rank, then an all-gather of the owned slices; staged through the host with stage_host)."""
+        res = self.infer(None, want_center=want_center)
+        mine = torch.cat(res, 1) if want_center else res
+        if self.world == 1:
+            out = mine
+        else:
+            part = self.part
+            buf = torch.zeros(part.n_max, mine.shape[1], dtype=torch.float32, device="cpu" if self.stage_host else self.dev)
+            buf[:part.n_local].copy_(mine)
+            got = [torch.empty_like(buf) for _ in range(self.world)]
+            dist.all_gather(got, buf, group=self.group)
+            sizes = np.diff(part.bounds_host)
+            out = torch.cat([t[:int(sz)] for t, sz in zip(got, sizes)]).to(self.dev)
+        return (out[:, :2].contiguous(), out[:, 2:].contiguous()) if want_center else out
+
+    def infer_global(self, ids, want_center: bool = False):
+        """COLLECTIVE (every rank passes the same ids).  Test-mode logits [n, 2] of any global node ids (any order, duplicates
+        allowed), on every rank: each rank infers the ids it owns, the results are all-gathered.  What utils.test evaluates a
+        partitioned model with."""
+        part = self.part
+        gid = (ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)).reshape(-1).astype(np.int64)
+        if gid.size and (gid.min() < 0 or gid.max() >= part.n_nodes):
+            raise ValueError(f"infer_global: ids outside 0 .. {part.n_nodes - 1}")
+        mask = (gid >= part.lo) & (gid < part.hi)
+        res = self.infer(gid[mask] - part.lo, want_center=want_center)
+        mine = torch.cat(res, 1) if want_center else res
+        if self.world == 1:
+            out = mine
+        else:
+            full = torch.zeros(gid.size, mine.shape[1], dtype=torch.float32, device="cpu" if self.stage_host else self.dev)
+            full[torch.from_numpy(np.nonzero(mask)[0]).to(full.device)] = mine.to(full.device)
+            got = [torch.empty_like(full) for _ in range(self.world)]
+            dist.all_gather(got, full, group=self.group)
+            owner = torch.from_numpy(part.owner(gid)).to(full.device)
+            out = torch.stack(got)[owner, torch.arange(gid.size, device=full.device)].to(self.dev)
+        return (out[:, :2].contiguous(), out[:, 2:].contiguous()) if want_center else out
+
+    def _pos_sorted(self) -> np.ndarray:
+        return self.halo.pos_ids.cpu().numpy() if self.halo.P else np.zeros(0, np.int64)
+
+    def _infer_halo(self, pitch: int) -> "HaloExchangeHip":
+        """the inference halo exchange for `pitch` rows per owner: request list, hash table, counts, serve buffer and halo rows
+        of its own (the training window's halo is left alone)"""
+        h = self._inf.get("halo")
+        if h is None or h.pitch != pitch:
+            self._inf["halo"] = None
+            cap = max(self.world - 1, 1) * pitch
+            buf = torch.zeros(cap, self.g.X.shape[1], dtype=torch.float32, device=self.dev)
+            P = self.g.n_pos                               # (the train-pos ids in the order of their replicated rows)
+            pos = self.row_gid[self.part.n_local:self.part.n_local + P].cpu().tolist()
+            h = self._inf["halo"] = HaloExchangeHip(self.part, self.g.X, pos, pitch, self.group, self.stage_host, halo=buf)
+        return h
+
+    def _agree_flags(self, overflow_word: torch.Tensor, status: torch.Tensor):
+        """COLLECTIVE.  (halo overflow word, status word) OR-ed over the ranks - every bit travels as a 0/1 entry, MAX = OR, as in
+        check() -; both words are zeroed.  One host read."""
+        words = torch.stack([overflow_word[0], status[0]]).to(torch.int64)
+        bits = torch.arange(16, device=words.device, dtype=torch.int64)
+        flags = (words[:, None] >> bits[None, :]) & 1
+        if self.world > 1:
+            if self.stage_host:
+                c = flags.cpu()
+                dist.all_reduce(c, op=dist.ReduceOp.MAX, group=self.group)
+                flags = c
+            else:
+                dist.all_reduce(flags, op=dist.ReduceOp.MAX, group=self.group)
+        flags = (flags.to(bits.device) << bits[None, :]).sum(1)
+        halo, lists = (int(x) for x in flags.cpu().tolist())
+        overflow_word.zero_()
+        status.zero_()
+        return halo, lists
 
     def profile_select(self, every: int = 10):
         """Start collecting (start event, end event, ids, |set| counts) of the steps of every `every`-th window (train_window;

@@ -5,7 +5,8 @@ training / evaluation loop touches them: ``test`` (:280-333), ``pos_neg_split`` 
 ``test`` keeps the reference's signature and return value; predictions stay on the device for the
 whole pass and come back in ONE copy (the reference copies every batch, :305), and the
 degenerate empty trailing batch its ``int(len/B)+1`` produces is not run.  A fused engine's pass is
-one ``FusedPCGNN.infer`` call (``predict_proba``).  Metrics are computed
+one ``FusedPCGNN.infer`` call (``predict_proba``); a partitioned model's (``DistributedPCGNN``) is a
+collective ``infer_global`` call on every rank, with global test node ids.  Metrics are computed
 with numpy restatements of the sklearn functions the reference calls (checked against sklearn in
 the tests), so evaluation does not depend on sklearn being installed.
 """
@@ -61,11 +62,15 @@ def predict_proba(test_nodes, model, batch_size: int, labels=None) -> np.ndarray
     A FusedPCGNN runs its whole-set pass (``infer``: one call, one score pass) - test-mode results do not depend on how the
     nodes are batched, so this is bit for bit the per-batch ``predict`` loop - unless it was given a selection-list capacity of
     its own (``eval_by_infer`` False): then it is evaluated batch by batch under that capacity, as before.  ``batch_size``
-    batches those and the other models (``to_prob``, ``labels`` passed along)."""
+    batches those and the other models (``to_prob``, ``labels`` passed along).  A DistributedPCGNN: COLLECTIVE - every rank
+    passes the same global node ids and gets every one's probabilities (``infer_global``)."""
     nodes = np.asarray(test_nodes)
     if len(nodes) == 0:
         return np.zeros((0, 2), np.float32)
+    from .dist import DistributedPCGNN
     with torch.no_grad():
+        if isinstance(model, DistributedPCGNN):
+            return torch.sigmoid(model.infer_global(nodes)).float().cpu().numpy()
         if getattr(model, "eval_by_infer", False):
             ids = torch.as_tensor(nodes, dtype=torch.int32, device=model.dev)
             return torch.sigmoid(model.infer(ids)).float().cpu().numpy()
