@@ -50,8 +50,9 @@ enum {
     PCG_ST_SEL_OVERFLOW = 1,  /* sel_indices capacity too small; nothing was written past it */
     PCG_ST_LIST_ID_RANGE = 2, /* a selection-list entry named no row of the table handed to the gather; it was skipped (a hole) */
     PCG_ST_SYNC_TIMEOUT = 4,  /* a bounded in-kernel wait (the select kernel's wait for its own train-pos sort) ran out */
-    PCG_ST_SORT_OVERFLOW = 8  /* the one-launch bucket sort of the train positives met a bucket of more than 4096 keys (eight times
+    PCG_ST_SORT_OVERFLOW = 8, /* the one-launch bucket sort of the train positives met a bucket of more than 4096 keys (eight times
                                  the mean): its surplus keys were dropped - minority picks of that step may be wrong */
+    PCG_ST_EVAL_INPUT = 16    /* pcg_eval_counts met a label outside {0, 1} or a NaN probability: its counts describe no valid input */
 };
 
 enum { PCG_NORM_COUNT = 0, PCG_NORM_SQRT_COUNT = 1 };
@@ -614,6 +615,24 @@ int pcg_halo_lookup(const pcg_graph_desc *g, int32_t B, void *workspace, const v
 /* gather rows: out[i, :feat_dim] = X[ids[i], :feat_dim]  (self_feats, layers.py:273-277) */
 int pcg_gather_rows(const pcg_graph_desc *g, const int32_t *ids, int32_t n_ids,
                     float *out, int32_t out_stride, void *stream);
+
+/* ---- evaluation counts ---------------------------------------------------------
+ * Everything the reported metrics (src/utils.py:306-323, src/utils(f1).py:334-350) are functions of, as integers, from the
+ * class probabilities of an evaluation pass, without leaving the device:
+ *   prob [n, 2] f32 (sigmoid of the gnn logits), labels [n] i32 in {0, 1}, thresholds [n_thresholds] f64 ascending (device),
+ *   n <= 2^31 - 1, 1 <= n_thresholds <= 1024;
+ *   out [8 + 2 T] u64 = tp, fp, fn, tn (of the argmax prediction: 1 iff p1 > p0), n1, n0, 2U, 0, tp_t[T], npred_t[T]
+ *   with tp_t = #{y = 1, (double)p1 > thresholds[t]}, npred_t = #{(double)p1 > thresholds[t]} and
+ *   2U = sum over (positive i, negative j) of 2 [p1_i > p1_j] + [p1_i == p1_j]   (auc = (2U / 2) / (n1 n0), average ranks for ties;
+ *   -0.0 == +0.0).
+ * Launches: zero | count pass | finish | LSD radix sort of the smaller class's keys (one launch up to 65536 keys, three per
+ * 8-bit pass above) | rank pass.  Integer sums only: the output is the same bits on every run.  workspace:
+ * pcg_eval_workspace_bytes(n, n_thresholds) bytes, 256-byte aligned, contents irrelevant on entry (the call zeroes its counters
+ * itself, on the stream: capturable).  A label outside {0, 1} (counted as 1) or a NaN probability sets PCG_ST_EVAL_INPUT in *status.
+ * n == 0: out is all zeros. */
+int64_t pcg_eval_workspace_bytes(int64_t n, int32_t n_thresholds);
+int pcg_eval_counts(const float *prob, const int32_t *labels, int64_t n, const double *thresholds, int32_t n_thresholds,
+                    void *workspace, uint64_t *out, uint32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1052,6 +1052,18 @@ class DistributedPCGNN:
             out = torch.stack(got)[owner, torch.arange(gid.size, device=full.device)].to(self.dev)
         return (out[:, :2].contiguous(), out[:, 2:].contiguous()) if want_center else out
 
+    def evaluate(self, global_ids, labels, thresholds=None) -> dict:
+        """COLLECTIVE (every rank passes the same ids and labels).  The evaluation metrics of any global node ids from
+        device-side counts: ``infer_global`` (its result is on the device on every rank) -> sigmoid -> pcg_eval_counts ->
+        ``utils.metrics_from_counts``, the same call on every rank - every value ``==`` the host path of ``utils.test``."""
+        from . import ops, utils as U
+        with torch.no_grad():
+            prob = torch.sigmoid(self.infer_global(global_ids)).float()
+        lab = ops._i32(labels, self.dev).view(-1)
+        if lab.numel() != prob.shape[0]:
+            raise ValueError(f"evaluate: {lab.numel()} labels for {prob.shape[0]} ids")
+        return U.device_metrics(prob, lab, thresholds)
+
     def _pos_sorted(self) -> np.ndarray:
         return self.halo.pos_ids.cpu().numpy() if self.halo.P else np.zeros(0, np.int64)
 

@@ -1014,3 +1014,30 @@ class FusedPCGNN:
             inf["status"].zero_()
             self._raise_status(st)
         return (logits, center) if want_center else logits
+
+    def evaluate(self, ids, labels, thresholds=None, chunk: Optional[int] = None) -> dict:
+        """The evaluation metrics of a node set without its probabilities leaving the device: ``infer`` -> sigmoid (torch, so
+        the scores are the very float32 values ``utils.predict_proba`` hands the host) -> the integer counts (pcg_eval_counts)
+        -> ``utils.metrics_from_counts``: every value ``==`` what ``utils.test`` / ``test_f1`` compute on the host.  ids as
+        ``infer`` (None = every node); labels: the ids' labels (host sequence or tensor) - they go to the device once and are
+        kept for the next pass over the same labels object / the same values; thresholds: None = linspace(0.01, 0.99, 100)."""
+        from . import utils as U
+        lab = self._eval_labels(labels)
+        with torch.no_grad():
+            prob = torch.sigmoid(self.infer(ids, chunk=chunk)).float()
+        if lab.numel() != prob.shape[0]:
+            raise ValueError(f"evaluate: {lab.numel()} labels for {prob.shape[0]} ids")
+        return U.device_metrics(prob, lab, thresholds)
+
+    def _eval_labels(self, labels) -> torch.Tensor:
+        if torch.is_tensor(labels):
+            return ops._i32(labels, self.dev).view(-1)
+        host = np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)
+        cache = self._inf.setdefault("eval_labels", {})
+        key = host.size                                  # (one set per size: train-time validation and the final test alternate)
+        hit = cache.get(key)
+        if hit is None or not np.array_equal(hit[0], host):
+            if len(cache) >= 4:
+                cache.clear()
+            hit = cache[key] = (host.copy(), torch.from_numpy(host).to(self.dev))
+        return hit[1]

@@ -161,7 +161,8 @@ def _csr_of(adj, n):
 class ModelHandler(object):
     """``ModelHandler(config).train() -> (auc_test, recall_test, f1_macro_test)`` with the reference's config keys
     (generate_exp_config.ipynb:50-66): data_name, model (PCGNN | SAGE | GCN), seed, train_ratio, test_ratio, emb_size, rho,
-    alpha, lr, weight_decay, batch_size, epochs, valid_epochs, patience (+ exp_num, kept for bookkeeping).
+    alpha, lr, weight_decay, batch_size, epochs, valid_epochs, patience (+ exp_num, kept for bookkeeping; + the optional
+    ``eval_on_device``: validation / test metrics from the counts formed on the device, ``utils.test(on_device=True)``).
 
     The reference reads its datasets from files that exist nowhere offline (``load_data``, src/utils.py:66-207), so the
     graph is handed in: ``dataset = (homo, relation_list, feat_data, labels)`` - exactly what ``load_data`` returns
@@ -262,6 +263,7 @@ class ModelHandler(object):
         labels_dev = torch.from_numpy(np.asarray(ds["labels"]).astype(np.int32)).to(dev)
         auc_best, f1_mac_best, epoch_best = 1e-10, 1e-10, 0                                              # :125
         saved = False
+        on_device = bool(getattr(args, "eval_on_device", False))        # (optional key: metrics from device-side counts, utils.test)
         if engine is not None:
             sampler = PickSampler(idx_train, y_train, ds["homo_deg"][np.asarray(idx_train)], dev, seed=args.seed)
             pick_size = 2 * len(ds["train_pos"])                                                        # :130
@@ -299,7 +301,8 @@ class ModelHandler(object):
             if (epoch + 1) % args.valid_epochs == 0:                                                      # :158-169
                 print("Valid at epoch {}".format(epoch))
                 auc_val, recall_val, f1_mac_val, precision_val = U.test(ds["idx_valid"], ds["y_valid"], engine or model,
-                                                                        args.batch_size, self.result, epoch, epoch_best, flag="val")
+                                                                        args.batch_size, self.result, epoch, epoch_best, flag="val",
+                                                                        on_device=on_device)
                 gain_auc = (auc_val - auc_best) / auc_best
                 gain_f1_mac = (f1_mac_val - f1_mac_best) / f1_mac_best
                 if (gain_auc + gain_f1_mac) > 0:
@@ -321,6 +324,7 @@ class ModelHandler(object):
             if engine is not None:
                 engine.params_changed()          # (the engine's own copy of the label classifier follows the restored one)
         auc_test, recall_test, f1_mac_test, precision_test = U.test(ds["idx_test"], ds["y_test"], engine or model, args.batch_size,
-                                                                    self.result, epoch_best=epoch_best, flag="test")
+                                                                    self.result, epoch_best=epoch_best, flag="test",
+                                                                    on_device=on_device)
         self.model, self.engine, self.epoch_best, self.last_epoch = model, engine, epoch_best, epoch
         return auc_test, recall_test, f1_mac_test

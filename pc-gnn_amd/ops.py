@@ -298,3 +298,62 @@ def step_front_b(g: DeviceGraph, s0: torch.Tensor, pos_keys: Optional[torch.Tens
                                     ws.list_capacity, _p(ws.status), _p(center_out), center_id_offset, _stream(g.device)),
                "pcg_step_front_b")
     return pos_keys if sort else None
+
+
+_EVAL_CACHE = {}
+
+
+def eval_thresholds(thresholds=None) -> np.ndarray:
+    """The threshold vector of an evaluation: float64, ascending; default the reference's linspace(0.01, 0.99, 100)."""
+    th = np.linspace(0.01, 0.99, 100) if thresholds is None else np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    if th.size < 1 or th.size > 1024 or np.any(np.isnan(th)) or np.any(np.diff(th) < 0):
+        raise ValueError("eval_counts: 1 .. 1024 ascending thresholds")
+    return th
+
+
+def eval_counts(prob: torch.Tensor, labels: torch.Tensor, thresholds=None, stream=None, status: Optional[torch.Tensor] = None):
+    """The integer counts every reported metric is a function of (pcg_eval_counts): uint64 words in an int64 device tensor
+    [8 + 2 T] = tp, fp, fn, tn, n1, n0, 2U, 0, tp_t[T], npred_t[T].  prob: float32 [n, 2] on the device, labels: int32 [n] on the
+    device, thresholds: None (linspace(0.01, 0.99, 100)), a host sequence or a float64 device tensor.  Nothing synchronises;
+    a bad label / a NaN sets PCG_ST_EVAL_INPUT in ``status`` (a device int32 word; the per-device default one is read by
+    utils.device_metrics).  The workspace and the default thresholds are kept per device and reused by the next call."""
+    lib = _lib.load()
+    dev = prob.device
+    if dev.type != "cuda":
+        raise _lib.PcgnnLibraryError("eval_counts runs on the GPU only: there is no CPU fallback for the product path")
+    if prob.dtype != torch.float32 or prob.dim() != 2 or prob.shape[1] != 2 or labels.dtype != torch.int32 or labels.numel() != prob.shape[0]:
+        raise ValueError("eval_counts: prob float32 [n, 2], labels int32 [n]")
+    prob, labels = prob.contiguous(), labels.contiguous()
+    n = prob.shape[0]
+    cache = _EVAL_CACHE.setdefault((dev.type, dev.index if dev.index is not None else torch.cuda.current_device()), {})
+    if torch.is_tensor(thresholds):
+        th = thresholds.to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        key = None if thresholds is None else tuple(float(t) for t in np.asarray(thresholds, dtype=np.float64).reshape(-1))
+        th = cache.get(("th", key))
+        if th is None:
+            th = cache[("th", key)] = torch.from_numpy(eval_thresholds(thresholds)).to(dev)
+    T = th.numel()
+    nbytes = lib.pcg_eval_workspace_bytes(n, T)
+    if nbytes < 0:
+        raise _lib.PcgnnLibraryError(f"pcg_eval_workspace_bytes rejected n {n} / {T} thresholds")
+    if cache.get("ws") is None or cache["ws"].numel() < nbytes:
+        cache["ws"] = None
+        cache["ws"] = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = cache.get("status")
+        if status is None:
+            status = cache["status"] = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = torch.empty(8 + 2 * T, dtype=torch.int64, device=dev)
+    st = _stream(dev) if stream is None else C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
+    _lib.check(lib.pcg_eval_counts(_p(prob), _p(labels), n, _p(th), T, _p(cache["ws"]), _p(out), _p(status), st), "pcg_eval_counts")
+    return out
+
+
+def eval_status(device) -> torch.Tensor:
+    """The per-device status word eval_counts ORs PCG_ST_EVAL_INPUT into by default."""
+    dev = torch.device(device)
+    cache = _EVAL_CACHE.setdefault((dev.type, dev.index if dev.index is not None else torch.cuda.current_device()), {})
+    if cache.get("status") is None:
+        cache["status"] = torch.zeros(1, dtype=torch.int32, device=dev)
+    return cache["status"]

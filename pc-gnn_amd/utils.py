@@ -57,6 +57,94 @@ def roc_auc(y_true, score) -> float:
     return float((ranks[y].sum() - n1 * (n1 + 1) / 2.0) / (n1 * n0))
 
 
+def _prf_counts(tp, fp, fn):
+    """_prf from the three counts (the same statements)."""
+    tp, fp, fn = float(tp), float(fp), float(fn)
+    prec = tp / (tp + fp) if tp + fp > 0 else 0.0
+    rec = tp / (tp + fn) if tp + fn > 0 else 0.0
+    f1 = 2 * prec * rec / (prec + rec) if prec + rec > 0 else 0.0
+    return prec, rec, f1
+
+
+def metrics_from_counts(counts, thresholds=None) -> dict:
+    """PURE HOST.  Every metric ``binary_metrics`` / ``roc_auc`` / ``get_best_f1`` / ``test_f1`` report, from the integer
+    vector ``pcg_eval_counts`` forms (ops.eval_counts): counts [8 + 2 T] = tp, fp, fn, tn, n1, n0, 2U, 0, tp_t[T], npred_t[T].
+    The float64 arithmetic from the integers on is the statements of those functions, so the values are ``==`` theirs:
+    the keys of binary_metrics (same ValueError when a class is absent), plus ``best_f1`` / ``best_threshold`` (get_best_f1's
+    rule: the first threshold wins, it must beat 0), ``best_index`` (its position, -1 if none) and ``f1_macro_at`` (a list:
+    test_f1's F1-macro of the prediction ``p > thresholds[i]``)."""
+    c = [int(v) & 0xFFFFFFFFFFFFFFFF for v in np.asarray(counts).reshape(-1).tolist()]
+    th = np.linspace(0.01, 0.99, 100) if thresholds is None else np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    T = len(th)
+    if len(c) != 8 + 2 * T:
+        raise ValueError(f"metrics_from_counts: {len(c)} words for {T} thresholds (8 + 2 T expected)")
+    tp, fp, fn, tn, n1, n0, two_u = c[:7]
+    if n1 == 0 or n0 == 0:
+        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+    p1, r1, f1 = _prf_counts(tp, fp, fn)
+    p0, r0, f0 = _prf_counts(tn, fn, fp)
+    m = {"accuracy": float(np.float64(tp + tn) / (n1 + n0)), "f1": f1, "f1_macro": (f1 + f0) / 2, "precision": p1,
+         "precision_macro": (p1 + p0) / 2, "recall": r1, "recall_macro": (r1 + r0) / 2,
+         "auc": float((two_u / 2.0) / (n1 * n0))}
+    tp_t = np.array(c[8:8 + T], dtype=np.float64)
+    n_pred = np.array(c[8 + T:8 + 2 * T], dtype=np.float64)
+    denom = n_pred + float(n1)                                         # 2TP + FP + FN
+    f1_t = np.where(denom > 0, 2.0 * tp_t / np.maximum(denom, 1.0), 0.0)
+    best_f1, best_t, best_i = 0.0, 0.0, -1
+    for i, (f, t) in enumerate(zip(f1_t, th)):
+        if f > best_f1:
+            best_f1, best_t, best_i = float(f), float(t), i
+    macro = []
+    for i in range(T):
+        tpi, npi = c[8 + i], c[8 + T + i]
+        fpi, fni = npi - tpi, n1 - tpi
+        macro.append(0.5 * (_prf_counts(tpi, fpi, fni)[2] + _prf_counts(n0 - fpi, fni, fpi)[2]))
+    m.update(best_f1=best_f1, best_threshold=best_t, best_index=best_i, f1_macro_at=macro)
+    return m
+
+
+def device_metrics(prob_dev, labels, thresholds=None) -> dict:
+    """metrics_from_counts of class probabilities that are on the device: ops.eval_counts (HIP) + ONE copy of 8 + 2 T words
+    (with the status word) + the host arithmetic.  labels: int32 on the device, or anything ops._i32 takes."""
+    from . import _lib, ops
+    lab = labels if torch.is_tensor(labels) and labels.dtype == torch.int32 and labels.device == prob_dev.device \
+        else ops._i32(labels, prob_dev.device)
+    th = ops.eval_thresholds(thresholds)
+    status = ops.eval_status(prob_dev.device)
+    counts = ops.eval_counts(prob_dev, lab.view(-1), None if thresholds is None else th)
+    words = torch.cat([counts, status.to(torch.int64)]).cpu().numpy()
+    if int(words[-1]):
+        status.zero_()
+        if int(words[-1]) & _lib.PCG_ST_EVAL_INPUT:
+            raise _lib.PcgnnLibraryError("evaluation input: a label outside {0, 1} or a NaN probability")
+        raise _lib.PcgnnLibraryError(f"device status {int(words[-1])}")
+    return metrics_from_counts(words[:-1], th)
+
+
+def _device_eval(test_nodes, labels, model, batch_size: int, thresholds=None) -> dict:
+    """The on_device evaluation of ``test`` / ``test_f1``: a model that has ``evaluate`` (FusedPCGNN, DistributedPCGNN) runs it;
+    the others' batch probabilities are concatenated on the device and go through device_metrics."""
+    nodes = np.asarray(test_nodes)
+    if hasattr(model, "evaluate") and (getattr(model, "eval_by_infer", True)):
+        return model.evaluate(nodes, labels, thresholds=thresholds)
+    y = np.asarray(labels)
+    with torch.no_grad():
+        outs = []
+        fused = hasattr(model, "predict")
+        ids_dev = torch.as_tensor(nodes, dtype=torch.int32, device=model.dev) if fused else None
+        for start in range(0, len(nodes), batch_size):
+            if fused:
+                outs.append(torch.sigmoid(model.predict(ids_dev[start:start + batch_size], None, False)[0]))
+            else:
+                outs.append(model.to_prob(nodes[start:start + batch_size].tolist(), y[start:start + batch_size], train_flag=False)[0])
+        if not outs:
+            raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+        prob = torch.cat(outs).float()
+    if hasattr(model, "check"):
+        model.check()
+    return device_metrics(prob, y, thresholds)
+
+
 def predict_proba(test_nodes, model, batch_size: int, labels=None) -> np.ndarray:
     """Test-mode class probabilities [n, 2] of ``test_nodes`` (sigmoid of the gnn logits, utils.py:305), on the host.
     A FusedPCGNN runs its whole-set pass (``infer``: one call, one score pass) - test-mode results do not depend on how the
@@ -88,17 +176,22 @@ def predict_proba(test_nodes, model, batch_size: int, labels=None) -> np.ndarray
 
 def test(test_nodes, labels, model, batch_size: int, result=None, epoch: Optional[int] = None,
          epoch_best: Optional[int] = None, flag: Optional[str] = None,
-         print_line: Optional[bool] = True) -> Tuple[float, float, float, float]:
+         print_line: Optional[bool] = True, on_device: bool = False) -> Tuple[float, float, float, float]:
     """Evaluate ``model`` (PCALayer / GCN / GraphSage mirror, or a FusedPCGNN) on ``test_nodes``:
     batched ``to_prob(..., train_flag=False)`` -> argmax / positive-class confidence -> metrics.
     Returns (auc, recall, f1_macro, precision) like the reference (utils.py:333).  Test-mode results do not depend on the
-    batching: a FusedPCGNN evaluates the whole set in one pass (predict_proba); ``batch_size`` batches the other models."""
+    batching: a FusedPCGNN evaluates the whole set in one pass (predict_proba); ``batch_size`` batches the other models.
+    on_device: the probabilities stay on the device and the metrics come from the integer counts formed there
+    (``model.evaluate`` / device_metrics): the same values, the same line, one small copy instead of [n, 2] floats + numpy."""
     labels = np.asarray(labels)
-    prob = predict_proba(test_nodes, model, batch_size, labels)
-    if hasattr(model, "check"):
-        model.check()          # a batch that overflowed its selection list must not pass for a prediction
-    pred = prob.argmax(axis=1)                                               # :306
-    m = binary_metrics(labels, pred, prob[:, 1])                             # :308, :316-323
+    if on_device:
+        m = _device_eval(test_nodes, labels, model, batch_size)
+    else:
+        prob = predict_proba(test_nodes, model, batch_size, labels)
+        if hasattr(model, "check"):
+            model.check()          # a batch that overflowed its selection list must not pass for a prediction
+        pred = prob.argmax(axis=1)                                               # :306
+        m = binary_metrics(labels, pred, prob[:, 1])                             # :308, :316-323
     line = (f"- F1: {m['f1']:.4f}\t- Recall: {m['recall']:.4f}\t- Precision: {m['precision']:.4f}\t"
             f"- Accuracy: {m['accuracy']:.4f}\t- AUC-ROC: {m['auc']:.4f}\t- F1-macro: {m['f1_macro']:.4f}\t"
             f"- Recall-macro: {m['recall_macro']:.4f}\t- AP: {m['precision_macro']:.4f}\t\n")   # :325
@@ -137,11 +230,25 @@ def get_best_f1(labels, probs, thresholds=None) -> Tuple[float, float]:
     return best_f1, best_t
 
 
-def test_f1(test_nodes, labels, model, batch_size: int, flag: str = "valid", valid_thresh: Optional[float] = None):
+def test_f1(test_nodes, labels, model, batch_size: int, flag: str = "valid", valid_thresh: Optional[float] = None,
+            on_device: bool = False):
     """The "(f1)" evaluation (src/utils(f1).py:280-332): F1-macro at the best validation threshold (flag "valid":
     searched here and returned; otherwise ``valid_thresh`` is applied), the other metrics from the argmax prediction.
-    Returns (auc, recall, f1_macro, precision, threshold) like the reference.  Probabilities as ``test`` (predict_proba)."""
+    Returns (auc, recall, f1_macro, precision, threshold) like the reference.  Probabilities as ``test`` (predict_proba).
+    on_device: as ``test``; flag "valid" takes the best threshold and the F1-macro at it from the 100-threshold sweep's counts,
+    otherwise the sweep is the one threshold ``valid_thresh``."""
     y = np.asarray(labels)
+    if on_device:
+        if flag == "valid":
+            m = _device_eval(test_nodes, y, model, batch_size)
+            threshold = m["best_threshold"]
+            if m["best_index"] >= 0:
+                f1_macro = m["f1_macro_at"][m["best_index"]]
+            else:                                                     # no threshold beat 0: the cut is get_best_f1's 0.0
+                f1_macro = _device_eval(test_nodes, y, model, batch_size, thresholds=[threshold])["f1_macro_at"][0]
+            return m["auc"], m["recall"], f1_macro, m["precision"], threshold
+        m = _device_eval(test_nodes, y, model, batch_size, thresholds=[valid_thresh])
+        return m["auc"], m["recall"], m["f1_macro_at"][0], m["precision"], None
     prob = predict_proba(test_nodes, model, batch_size, y)
     if hasattr(model, "check"):
         model.check()
