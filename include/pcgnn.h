@@ -518,6 +518,38 @@ int pcg_infer_chunk_dist(const pcg_graph_desc *g, const float *theta, int32_t em
                          int64_t table_slots, uint32_t *counts, float *s0, const double *thresholds, void *workspace,
                          int32_t chunk_rows, int64_t list_capacity, float *out_logits, float *out_center, uint32_t *status,
                          void *stream);
+/* Scoring nodes that are NOT in the resident graph (test mode, forward only; FusedPCGNN.infer_new).  g is the BASE graph (N =
+ * g->n_nodes >= 1 nodes): nothing of it is modified and the logits of its nodes are not recomputed.  q describes a QUERY BATCH of nq
+ * new nodes, query node j having the global id N + j:
+ *   q->n_nodes = nq;  q->X = Xq [nq, feat_stride] (16-byte aligned, pad columns zero);  q->indptr[r] int64 [nq + 1];
+ *   q->indices[r] int32: GLOBAL ids in [0, N + nq), ascending inside a row - base nodes, other nodes of the batch, the node itself
+ *   (a caller mirroring the reference keeps the self-loop: N + j in row j);  q->n_pos = 0, q->train_pos = NULL;
+ *   q->max_degree = the query rows' own maximum.  feat_dim, feat_stride and n_rel must equal g's (else PCG_E_ARG); N + nq < 2^31.
+ * ids [n]: query-local rows in [0, nq), any order, duplicates allowed.  out_logits [n][2]; out_center [n][2] or NULL.
+ * s0 [N + nq] floats, owned by the caller across calls: score_base != 0 - the call first scores the base table into s0[0, N) (the
+ * workgroups, rows and fma order of pcg_score_table); score_base == 0 - the caller guarantees that those N entries hold the scores
+ * of theta's current label classifier (a previous call's, with theta unchanged since).  Either way the query rows are scored into
+ * s0[N, N + nq) (the per-row arithmetic of pcg_score_table).
+ * Launches: one front (the scores above || the look-back words of the two plan slots zeroed), then per chunk of chunk_rows ids
+ * (the last one may be shorter): plan (test mode, pcg_plan_epochs over q's rows) -> select (pcg_choose_select_planned: centre b's
+ * score s0[ids[b] + N], lists of global ids) -> a two-table gather (entry id < N reads row id of g->X, id >= N row id - N of q->X;
+ * the chunks and the summation order per row of pcg_choose_gather_planned; rows of several 128-entry chunks left as partial sums)
+ * -> the persistent forward-only dense launch of pcg_infer_set with the self rows from q->X.  Never synchronises, never allocates.
+ * workspace: pcg_infer_new_workspace_bytes(g, q, emb, chunk_rows, list_capacity) bytes (>= pcg_infer_workspace_bytes of q for the
+ * same chunk and capacity; negative = rejected arguments), no initial contents required; list_capacity as pcg_infer_set's, over the
+ * QUERY rows' degrees (else PCG_ST_SEL_OVERFLOW in *status and that chunk selects nothing).
+ * The caller's contract, as for the base CSR: every entry of q->indices is in [0, N + nq) - the select kernel reads s0[id] for
+ * every neighbour before anything checks it.  The gather skips a list entry outside that range like a hole and sets
+ * PCG_ST_LIST_ID_RANGE, which is a report, not a guard.  (pc-gnn_amd/graph.py: QueryBatch validates on the host.)
+ * n == 0 or nq == 0: nothing is enqueued.
+ * Parity: every logit is bit for bit what pcg_infer_set writes for node N + j on a graph built with the query rows appended to
+ * the base table and CSR, with the same theta (a node's test-mode logits depend on its own row, its own lists, the scores and
+ * rows of those neighbours and the parameters - on nothing else in the graph). */
+int64_t pcg_infer_new_workspace_bytes(const pcg_graph_desc *g, const pcg_graph_desc *q, int32_t emb, int32_t chunk_rows,
+                                      int64_t list_capacity);
+int pcg_infer_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float *theta, int32_t emb, const int32_t *ids, int32_t n,
+                  int32_t chunk_rows, float *s0, int32_t score_base, const double *thresholds, void *workspace,
+                  int64_t list_capacity, float *out_logits, float *out_center, uint32_t *status, void *stream);
 int pcg_step_front_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, float *s0,
                          uint64_t *pos_keys, const int32_t *nodes, const int32_t *labels, int32_t B,
                          const double *thresholds, const double *rho, int32_t add_self, void *workspace,

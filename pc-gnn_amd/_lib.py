@@ -17,7 +17,7 @@ PCG_ST_SYNC_TIMEOUT = 4
 PCG_ST_SORT_OVERFLOW = 8
 PCG_ST_EVAL_INPUT = 16
 PCG_NORM_COUNT, PCG_NORM_SQRT_COUNT = 0, 1
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class GraphDesc(C.Structure):
@@ -104,6 +104,8 @@ PROTOTYPES = {
     "pcg_infer_dist_workspace_bytes": (_I64, [_G, _I32, _I32, _I64]),
     "pcg_infer_chunk_dist": (C.c_int, [_G, _P, _I32, _P, _I32, _I32, _P, _I64, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _P,
                                        C.POINTER(_F64), _P, _I32, _I64, _P, _P, _P, _P]),
+    "pcg_infer_new_workspace_bytes": (_I64, [_G, _G, _I32, _I32, _I64]),
+    "pcg_infer_new": (C.c_int, [_G, _G, _P, _I32, _P, _I32, _I32, _P, _I32, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P]),
     "pcg_eval_workspace_bytes": (_I64, [_I64, _I32]),
     "pcg_eval_counts": (C.c_int, [_P, _P, _I64, _P, _I32, _P, _P, _P, _P]),
     "pcg_step_front_train": (C.c_int, [_G, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, C.POINTER(_F64), C.POINTER(_F64), _I32, _P,

@@ -66,6 +66,12 @@ __device__ __forceinline__ void store_row(float *out, const float4 (&acc)[NACC],
 // HALO_X (partitioned inference, pcg_infer_chunk_dist; needs MAP): translated rows >= a.hm.halo_base are read from halo_X (row
 // - halo_base, stride feat_stride) instead of a.X - the inference halo lives in a buffer of its own.  The training
 // instantiations leave it false: their code is what it was before the flag existed.
+// HALO_X without MAP (the query-batch path, pcg_infer_new): the lists hold ids of [base table | query table]; an id >=
+// a.hm.halo_base (= the base table's rows) is row id - halo_base of halo_X (the query table), nothing else of a.hm is read.  The
+// table is chosen by a compare and a select between two addresses formed from the id already in the register - no load sits
+// between the id and the row.  For a query id the base-table address a.X + id * stride is still FORMED (it lies past the end of
+// a.X) and then replaced by the select: it is never loaded from.  Keep it that way - a branch around it would put the row load
+// inside a conditional again and serialise the gathers.
 template <int NACC, bool MAP = false, bool HALO_X = false>
 __device__ __forceinline__ void gather_chunks_body(const AggArgs &a, uint32_t block, uint32_t n_blocks,
                                                    const float *__restrict__ halo_X = nullptr) {
@@ -194,6 +200,12 @@ __global__ void __launch_bounds__(256) gather_chunks_dist(const AggArgs a, const
 template <int NACC>
 __global__ void __launch_bounds__(256) gather_chunks_infer(const AggArgs a, const float *__restrict__ halo_X) {
     gather_chunks_body<NACC, true, true>(a, blockIdx.x, gridDim.x, halo_X);
+}
+
+// The two-table gather of a query batch (pcg_infer_new): ids of the base table and of the query table behind it, no translation
+template <int NACC>
+__global__ void __launch_bounds__(256) gather_chunks_two(const AggArgs a, const float *__restrict__ query_X) {
+    gather_chunks_body<NACC, false, true>(a, blockIdx.x, gridDim.x, query_X);
 }
 
 // The gather launch of a TRAINING step, with what else fits beside it (SideJob, choose.h): workgroups
@@ -369,6 +381,26 @@ int launch_gather_infer(const float *X, int32_t feat_dim, int32_t feat_stride, i
     a.hm = hm;
     if (feat_stride <= 256) hipLaunchKernelGGL(gather_chunks_infer<1>, dim3(GATHER_BLOCKS), dim3(256), 0, st, a, halo_X);
     else hipLaunchKernelGGL(gather_chunks_infer<2>, dim3(GATHER_BLOCKS), dim3(256), 0, st, a, halo_X);
+    PCG_LAUNCH_CHECK();
+    return PCG_OK;
+}
+
+// (declared in infer_new.hip) lists of ids in [0, base_rows + query_rows): id < base_rows -> row id of X, else row id - base_rows
+// of query_X (both [.., feat_stride]); an id beyond both is skipped (PCG_ST_LIST_ID_RANGE); multi-chunk rows left as partial
+// sums for the dense launch.  Chunking and summation order per row: gather_chunks' (the same body).
+int launch_gather_two(const float *X, int64_t base_rows, const float *query_X, int64_t query_rows, int32_t feat_dim,
+                      int32_t feat_stride, int32_t n_rows, const int32_t *cnt, const Workspace &w, float *agg, int32_t agg_stride,
+                      uint32_t *status, hipStream_t st) {
+    if (!X || !query_X || !cnt || !agg || n_rows < 1 || base_rows < 1 || query_rows < 1) return PCG_E_ARG;
+    if (base_rows + query_rows >= (1ll << 31)) return PCG_E_ARG;
+    if (feat_stride % 4 != 0 || feat_stride < feat_dim || agg_stride < feat_dim) return PCG_E_ARG;
+    if (feat_stride > 512) return PCG_E_UNSUPPORTED;
+    if (((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(query_X)) & 15u) != 0) return PCG_E_ARG;
+    AggArgs a;
+    fill_agg_args(a, X, feat_dim, feat_stride, base_rows + query_rows, n_rows, cnt, w, PCG_NORM_COUNT, agg, agg_stride, status);
+    a.hm.halo_base = (int32_t)base_rows;
+    if (feat_stride <= 256) hipLaunchKernelGGL(gather_chunks_two<1>, dim3(GATHER_BLOCKS), dim3(256), 0, st, a, query_X);
+    else hipLaunchKernelGGL(gather_chunks_two<2>, dim3(GATHER_BLOCKS), dim3(256), 0, st, a, query_X);
     PCG_LAUNCH_CHECK();
     return PCG_OK;
 }

@@ -13,16 +13,10 @@
 // and gather chunks are laid out per row (RowRec::lbeg, chunk0), the dense phases sum in the same order whatever tile the row
 // lands in.  So the chunked pass leaves bit for bit what pcg_train_dense (forward only, labels NULL) leaves batch by batch.
 // Reference lines replaced: src/utils.py:298-305 (the batched evaluation loop), src/model.py:34-39 (PCALayer.forward).
-#include "dense.h"
+#include "infer.h"
 #include "halo_map.h"
 
 namespace pcg {
-
-struct ZeroRegions {          // up to four runs of 32-bit words to zero
-    uint32_t *p[4];
-    int64_t n[4];
-};
-constexpr int INFER_ZERO_WORDS = 256 * 16;   // words per zeroing workgroup
 
 __global__ void __launch_bounds__(256) infer_front_kernel(const float *__restrict__ X, int feat_dim, int stride,
                                                           const float *__restrict__ W, const float *__restrict__ bias,
@@ -33,16 +27,7 @@ __global__ void __launch_bounds__(256) infer_front_kernel(const float *__restric
         score_table_body(X, feat_dim, stride, W, bias, 0, n_nodes, s0, b, n_score_blocks);
         return;
     }
-    // the zeroing workgroups: words [w0, w0 + INFER_ZERO_WORDS) of the concatenated regions
-    const int64_t w0 = (int64_t)(b - n_score_blocks) * INFER_ZERO_WORDS;
-    for (int64_t i = w0 + threadIdx.x; i < w0 + INFER_ZERO_WORDS; i += blockDim.x) {
-        int64_t j = i;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (j >= 0 && j < z.n[k]) z.p[k][j] = 0u;
-            j -= z.n[k];
-        }
-    }
+    infer_zero_body(z, b - n_score_blocks);   // the zeroing workgroups
 }
 
 // PERSIST: tile blockIdx.x, then + gridDim.x, ...; else one tile per workgroup (the run-time shapes: a loop around their
@@ -61,7 +46,7 @@ __global__ void __launch_bounds__(DENSE_THREADS) infer_dense_kernel(const DenseA
 }
 
 // WLDS for a forward-only launch: the training kernel's choice, if the K-split partial tiles fit where dcomb / dh_r live
-static bool infer_wlds(int F, int E, int R) {
+bool infer_wlds(int F, int E, int R) {
     if (!dense_wlds(F, E, R)) return false;
     const int ntile_e = E / 16, kparts = ntile_e <= DENSE_WAVES ? DENSE_WAVES / ntile_e : 1;
     return (int64_t)kparts * TB * E <= (int64_t)(1 + R) * TB * (E + 1);
@@ -85,7 +70,7 @@ static int infer_blocks(int B) {
     return n_tiles < cus ? n_tiles : cus;
 }
 
-static int launch_infer_dense(const DenseArgs &a, int B, hipStream_t st) {
+int launch_infer_dense(const DenseArgs &a, int B, hipStream_t st) {
     const int F = a.feat_dim, E = a.emb, R = a.n_rel;
     const bool wlds = infer_wlds(F, E, R);
     const size_t smem = dense_smem_bytes(F, E, R, wlds);
@@ -119,12 +104,8 @@ static int launch_infer_dense(const DenseArgs &a, int B, hipStream_t st) {
     return PCG_OK;
 }
 
-// the call's workspace: [plan slot of full chunks | plan slot of the last, shorter chunk | data part | agg [R][chunk][F] |
-// cnt [R][chunk] | centre logits [chunk][2] (when the caller wants none)]
-struct InferCarve {
-    int64_t plan_bytes, data, agg, cnt, center, total;
-};
-static int infer_carve(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity, InferCarve &c) {
+// the call's workspace (InferCarve, infer.h)
+int infer_carve(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity, InferCarve &c) {
     if (!g || chunk_rows < 1 || list_capacity < 1 || list_capacity >= (1ll << 31)) return PCG_E_ARG;
     if (emb < 16 || emb % 16 != 0 || g->n_rel < 1 || g->n_rel > PCG_MAX_REL || g->feat_dim < 1) return PCG_E_UNSUPPORTED;
     if ((int64_t)g->n_rel * chunk_rows >= (1ll << 31)) return PCG_E_ARG;
@@ -137,6 +118,20 @@ static int infer_carve(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows,
     c.center = c.cnt + align256(4 * R * B);
     c.total = c.center + align256(8 * B);
     return PCG_OK;
+}
+
+void infer_zero_regions(ZeroRegions &z, const pcg_graph_desc *g, int32_t chunk_rows, int32_t tail, int64_t list_capacity,
+                        unsigned char *slot0, unsigned char *slot1, unsigned char *data) {
+    const int32_t slot_B[2] = {chunk_rows, tail};
+    unsigned char *slot[2] = {slot0, slot1};
+    for (int s = 0; s < 2; ++s) {
+        Workspace w;
+        carve1(g, slot_B[s], list_capacity, data, &w, slot[s]);
+        z.p[2 * s] = w.counters;                                  // counters | heads: contiguous (256 + 512 bytes)
+        z.n[2 * s] = (reinterpret_cast<unsigned char *>(w.heads) - reinterpret_cast<unsigned char *>(w.counters) + 4 * 8 * 16) / 4;
+        z.p[2 * s + 1] = reinterpret_cast<uint32_t *>(w.plan_totals);
+        z.n[2 * s + 1] = 64 * ((int64_t)g->n_rel * slot_B[s] / 256 + 2) / 4;
+    }
 }
 
 // ---- partitioned inference (pcg_infer_chunk_dist, pc-gnn_amd/dist.py) ------------------------------------------------------
@@ -164,16 +159,7 @@ __global__ void __launch_bounds__(256) infer_front_dist_kernel(const float *__re
         score_table_body(halo_X, feat_dim, stride, W, bias, 0, n_halo_rows, s0, b, n_halo, halo_ids);
         return;
     }
-    b -= n_halo;
-    const int64_t w0 = (int64_t)b * INFER_ZERO_WORDS;
-    for (int64_t i = w0 + threadIdx.x; i < w0 + INFER_ZERO_WORDS; i += blockDim.x) {
-        int64_t j = i;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (j >= 0 && j < z.n[k]) z.p[k][j] = 0u;
-            j -= z.n[k];
-        }
-    }
+    infer_zero_body(z, b - n_halo);
 }
 
 // the call's workspace: [plan slot (chunk_rows) | data part | agg [R][chunk][F] | cnt [R][chunk] | centre logits [chunk][2]];
@@ -230,15 +216,7 @@ int pcg_infer_set(const pcg_graph_desc *g, const float *theta, int32_t emb, cons
     // call's chunk sizes place them.  A slot's earlier plans may have laid other arrays over those words: zeroed, none of them
     // can pass for a published total (the tags the plan launches count from the zeroed sequence word start at 1)
     pcg::ZeroRegions z = {};
-    const int32_t slot_B[2] = {chunk_rows, tail};
-    for (int s = 0; s < 2; ++s) {
-        pcg::Workspace w;
-        pcg::carve1(g, slot_B[s], list_capacity, data, &w, slot[s]);
-        z.p[2 * s] = w.counters;                                  // counters | heads: contiguous (256 + 512 bytes)
-        z.n[2 * s] = (reinterpret_cast<unsigned char *>(w.heads) - reinterpret_cast<unsigned char *>(w.counters) + 4 * 8 * 16) / 4;
-        z.p[2 * s + 1] = reinterpret_cast<uint32_t *>(w.plan_totals);
-        z.n[2 * s + 1] = 64 * ((int64_t)R * slot_B[s] / 256 + 2) / 4;
-    }
+    pcg::infer_zero_regions(z, g, chunk_rows, tail, list_capacity, slot[0], slot[1], data);
     const int64_t zero_words = z.n[0] + z.n[1] + z.n[2] + z.n[3];
     const int n_zero = (int)((zero_words + pcg::INFER_ZERO_WORDS - 1) / pcg::INFER_ZERO_WORDS);
     const int n_score = (int)pcg::score_table_blocks(g->n_nodes, g->feat_stride);

@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .graph import DeviceGraph
+from .graph import DeviceGraph, QueryBatch
 from .model import PCALayer
 
 _p = ops._p
@@ -171,6 +171,12 @@ class FusedPCGNN:
         # its default chunk keeps the workspace within infer_workspace_bytes
         self.infer_workspace_bytes = int(infer_workspace_bytes)
         self._inf = {}
+        # infer_new(): the base table's scores are kept across calls and reused while theta is what they were computed with.
+        # _param_version counts the host calls that enqueue a write of theta (training steps, epoch runs, a flush with an update
+        # pending, params_changed / a loaded state dict); _theta_dirty: such a call may have left a deferred update for flush()
+        self._param_version = 0
+        self._theta_dirty = False
+        self._new_scored_base = None
         # utils.test / test_f1 evaluate through infer() - unless the caller bounded the selection list (list_capacity): infer()
         # sizes its own list exactly, so such an engine keeps the per-batch predict loop, whose batches report an overflow
         self.eval_by_infer = list_capacity is None
@@ -288,10 +294,16 @@ class FusedPCGNN:
             None if touched is None else C.c_void_p(touched), self._stream()), "pcg_step_scores_train")
         return self.keys if g.n_pos else None
 
+    def _theta_written(self):
+        """a call that enqueues a write of theta (now, or deferred to the next flush): infer_new's cached base scores are stale"""
+        self._param_version += 1
+        self._theta_dirty = True
+
     def params_changed(self):
         """Tell the engine that the parameters were written from outside (a state dict loaded into the flat buffer's views):
         the stepped copy of the label classifier and the score table are taken from theta again."""
         self.flush()
+        self._param_version += 1
         self.clf_next.copy_(self.theta[self.n_rest:])
         self._fresh = False
 
@@ -434,6 +446,9 @@ class FusedPCGNN:
     def flush(self):
         """Apply a deferred Adam update now (no-op on the device if none is pending).  Enqueued, not synchronised."""
         b1, b2 = self.betas
+        if self._theta_dirty:                        # (a training call since the last flush: an update may be pending)
+            self._param_version += 1
+            self._theta_dirty = False
         _lib.check(self.lib.pcg_adam_flush(
             _p(self.theta), _p(self.m), _p(self.v), _p(self.slabs), 0, self.n_params, self.n_rest, _p(self.step_counter),
             _p(self.sync), self.lr, b1, b2, self.eps, self.wd, _p(self.clf_next), _p(self.acts), self.act_ld, self.F, self.E, self.R,
@@ -480,6 +495,7 @@ class FusedPCGNN:
         B = ids.numel()
         if B == 0:
             return
+        self._theta_written()
         if B > self.maxB:
             self.flush()
             self._alloc(B)
@@ -505,6 +521,7 @@ class FusedPCGNN:
         B = ids.numel()
         if B == 0:
             return
+        self._theta_written()
         if B > self.maxB:
             self.flush()
             self._alloc(B)
@@ -699,6 +716,7 @@ class FusedPCGNN:
             return
         lo, B = self._ep_batches[b]
         self._lastB = B
+        self._theta_written()
         defer = defer and b + 1 < len(self._ep_batches)
         key = (self._cur, lo, B, self._ep_shape, "deferred") if defer else (self._cur, lo, B, self._ep_shape)
         gr = self._ep_graphs.get(key)
@@ -722,6 +740,7 @@ class FusedPCGNN:
             return
         lo, B = self._ep_batches[b]
         self._lastB = B
+        self._theta_written()
         key = (self._cur, lo, B, self._ep_shape, "timed")
         grs = self._ep_graphs.get(key)
         ids, lab = self._ep_ids[lo:lo + B], self._ep_lab[lo:lo + B]
@@ -775,6 +794,7 @@ class FusedPCGNN:
         epoch's kernels; the only cross-stream waits are two events per epoch (the other buffer set is free / is ready).
         first_step > 0: the REST of an epoch that is staged and planned already and whose first batches have been run some other
         way (batches first_step .. n_steps - 1): no sampler, no plans."""
+        self._theta_written()
         nb = len(self._ep_batches)
         n_steps = nb if n_steps is None else min(n_steps, nb)
         n = self._ep_n * self._ep_k
@@ -1006,13 +1026,92 @@ class FusedPCGNN:
             inf["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
         if inf.get("s0") is None:
             inf["s0"] = torch.empty(g.n_nodes, dtype=torch.float32, device=self.dev)
+        if inf.get("status") is None:
             inf["status"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
         _lib.check(lib.pcg_infer_set(g.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk, _p(inf["s0"]), self._thr,
                                      _p(inf["ws"]), cap, _p(logits), _p(center), _p(inf["status"]), self._stream()), "pcg_infer_set")
-        st = int(inf["status"].item())
+        self._infer_status()
+        return (logits, center) if want_center else logits
+
+    def _infer_status(self):
+        """the status word of an infer / infer_new call: one read (synchronises); a set bit is cleared and raised"""
+        st = int(self._inf["status"].item())
         if st:
-            inf["status"].zero_()
+            self._inf["status"].zero_()
             self._raise_status(st)
+
+    def infer_new(self, query: QueryBatch, ids=None, chunk: Optional[int] = None, want_center: bool = False,
+                  reuse_scores: bool = True, _list_capacity: Optional[int] = None):
+        """Test-mode logits of nodes that are NOT in the graph (pcg_infer_new): ``query`` holds nq new nodes - a feature row
+        each and, per relation, a neighbour list of global ids in [0, N + nq), query node j being N + j (graph.QueryBatch).
+        Returns the gnn logits [n, 2] (+ the label-aware logits [n, 2] if want_center) of the query rows ``ids`` (query-local,
+        any order, duplicates allowed; None = all nq): bit for bit what ``infer`` would return for node N + j on a graph built
+        with the query rows appended - a node's test-mode logits depend on its own row, its own lists, the scores and rows
+        of those neighbours and the parameters, on nothing else.  The base graph is not modified, nothing of it is
+        recomputed, and the batch is not appended to it.  chunk as ``infer``'s, over the query's degrees.
+        The base table's scores are kept between calls (a buffer of N + capacity floats) and reused while nothing has written
+        the parameters since (training steps, epoch runs, a flush with an update pending, ``params_changed``, a loaded state
+        dict - a parameter-version counter); a warm call scores the nq query rows only.  reuse_scores=False forces the table
+        pass.  The training engine is left alone exactly as by ``infer`` (a deferred update is applied first).  Synchronises
+        once (the status word).  (_list_capacity: not part of the interface - the tests' way to make a selection list
+        overflow; the call sizes its list exactly.)"""
+        g, lib = self.g, self.lib
+        self.flush()
+        if query.n_base != g.n_nodes or query.feat_dim != g.feat_dim or query.R != g.R:
+            raise ValueError(f"infer_new: the query batch was built for a base graph of {query.n_base} nodes / {query.feat_dim} "
+                             f"features / {query.R} relations, this engine's has {g.n_nodes} / {g.feat_dim} / {g.R}")
+        if query.X is None or query.device != self.dev or query.feat_stride != g.feat_stride:
+            query.to(self.dev, g)
+        nq = query.nq
+        if ids is None:
+            n = nq
+            ids_host = None
+            ids_dev = torch.arange(n, dtype=torch.int32, device=self.dev)
+            caps = infer_row_caps(query.deg_host, self.thresholds)
+        else:
+            ids_host = (ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)).reshape(-1).astype(np.int64)
+            n = int(ids_host.size)
+            if n and (ids_host.min() < 0 or ids_host.max() >= nq):
+                raise ValueError(f"infer_new: ids outside 0 .. {nq - 1} (query-local rows)")
+            ids_dev = ops._i32(ids, self.dev).view(-1) if torch.is_tensor(ids) else \
+                torch.from_numpy(ids_host.astype(np.int32)).to(self.dev)
+            caps = infer_row_caps(query.deg_host, self.thresholds, ids_host)
+        logits = torch.empty(n, 2, dtype=torch.float32, device=self.dev)
+        center = torch.empty(n, 2, dtype=torch.float32, device=self.dev) if want_center else None
+        if n == 0:
+            return (logits, center) if want_center else logits
+        ws_bytes = lambda c, cap: int(lib.pcg_infer_new_workspace_bytes(g.desc_ref(), query.desc_ref(), self.E, c, cap))
+        chunk = default_infer_chunk(caps, ws_bytes, self.infer_workspace_bytes) if chunk is None else int(chunk)
+        chunk = max(1, min(chunk, n))
+        _, cap = infer_chunks(caps, chunk)
+        need = cap
+        if _list_capacity is not None:
+            cap = max(int(_list_capacity), 1)
+        # (a bounded list that overflows: the dense launch still walks the chunk offsets the plan worked out for the rows of
+        #  several chunks - the buffer is as large as the exact capacity's, so those reads stay inside it)
+        nbytes = max(ws_bytes(chunk, cap), ws_bytes(chunk, need)) if ws_bytes(chunk, cap) >= 0 else ws_bytes(chunk, cap)
+        if nbytes < 0:
+            raise _lib.PcgnnLibraryError(f"pcg_infer_new_workspace_bytes rejected chunk {chunk} / list capacity {cap} ({nbytes})")
+        inf = self._inf
+        if inf.get("new_ws") is None or inf["new_ws"].numel() < nbytes:
+            inf["new_ws"] = None
+            inf["new_ws"] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        if inf.get("status") is None:
+            inf["status"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        if inf.get("new_s0") is None or inf["new_s0"].numel() < g.n_nodes + nq:
+            # a grown buffer holds no scores: capacity in powers of two, so a stream of batches grows it a few times at most
+            capacity = 1 << max(nq - 1, 255).bit_length()
+            inf["new_s0"] = None
+            inf["new_s0"] = torch.empty(g.n_nodes + capacity, dtype=torch.float32, device=self.dev)
+            inf["new_s0_version"] = None
+        score_base = not (reuse_scores and inf["new_s0_version"] == self._param_version)
+        self._new_scored_base = score_base          # (whether the last infer_new ran the table pass: tests, scripts)
+        _lib.check(lib.pcg_infer_new(g.desc_ref(), query.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk, _p(inf["new_s0"]),
+                                     1 if score_base else 0, self._thr, _p(inf["new_ws"]), cap, _p(logits), _p(center),
+                                     _p(inf["status"]), self._stream()), "pcg_infer_new")
+        # (the table pass is enqueued before anything that could overflow: the scores are valid whatever the status says)
+        inf["new_s0_version"] = self._param_version
+        self._infer_status()
         return (logits, center) if want_center else logits
 
     def evaluate(self, ids, labels, thresholds=None, chunk: Optional[int] = None) -> dict:

@@ -186,3 +186,176 @@ class DeviceGraph:
     def nbytes(self) -> int:
         return (self.X.numel() * 4 + sum(t.numel() * 8 for t in self.indptr) + sum(t.numel() * 4 for t in self.indices)
                 + self.train_pos.numel() * 4)
+
+
+class BaseShape:
+    """What a ``QueryBatch`` is validated against: the base graph's node count, feature width and relation count.  A
+    ``DeviceGraph`` has the same three attributes; this stands in for one where there is no GPU (host-side checks, tests)."""
+
+    def __init__(self, n_nodes: int, feat_dim: int, n_rel: int):
+        self.n_nodes, self.feat_dim, self.R = int(n_nodes), int(feat_dim), int(n_rel)
+
+
+class QueryBatch:
+    """nq NEW nodes to be scored against a resident base graph of N nodes (``FusedPCGNN.infer_new``, pcg_infer_new): a feature
+    row each and, per relation, a neighbour list of GLOBAL ids in [0, N + nq) - query node j has the global id N + j; its
+    neighbours may be base nodes, other nodes of the batch and the node itself (the reference keeps self-loops,
+    src/utils.py:226-239: a caller mirroring it puts N + j into row j).  The base graph is not modified and nothing of it is
+    recomputed; the batch is not appended to it.
+
+    Everything here happens in numpy ON THE HOST: rows are sorted ascending and de-duplicated, the per-relation degrees and
+    ``max_degree`` computed, and the input validated - ``ValueError`` naming the relation and the row: feature width and
+    relation count against the base graph, every neighbour id in [0, N + nq), ``indptr`` monotone, nq / N + nq / list sizes
+    within int32.  ``to(device, base_graph)`` uploads (features padded to the base graph's ``feat_stride``).
+
+    ``base``: the base ``DeviceGraph``, or a ``BaseShape(n_nodes, feat_dim, n_rel)``.  ``csr``: one raw ``(indptr [nq + 1],
+    indices)`` pair per relation (rows in any order, duplicates allowed)."""
+
+    def __init__(self, features, csr: Sequence[Tuple[np.ndarray, np.ndarray]], base):
+        N, F, R = int(base.n_nodes), int(base.feat_dim), int(base.R)
+        X = features.detach().cpu().numpy() if torch.is_tensor(features) else np.asarray(features)
+        if X.ndim != 2:
+            raise ValueError(f"query features must be [nq, {F}], got shape {tuple(X.shape)}")
+        nq = int(X.shape[0])
+        if X.shape[1] != F:
+            raise ValueError(f"query feature width {X.shape[1]} != the base graph's {F}")
+        if len(csr) != R:
+            raise ValueError(f"query batch has {len(csr)} relations, the base graph {R}")
+        if nq >= (1 << 31) or N + nq >= (1 << 31):
+            raise ValueError(f"nq {nq} + {N} base nodes does not fit int32 ids")
+        self.n_base, self.nq, self.feat_dim, self.R = N, nq, F, R
+        self.X_host = np.ascontiguousarray(X, dtype=np.float32)
+        self.csr: List[Tuple[np.ndarray, np.ndarray]] = []
+        self.deg_host: List[np.ndarray] = []
+        self.max_degree = 0
+        span = N + nq
+        for r, (indptr, indices) in enumerate(csr):
+            indptr = np.asarray(indptr).astype(np.int64).reshape(-1)
+            indices = np.asarray(indices).astype(np.int64).reshape(-1)
+            if indptr.shape[0] != nq + 1:
+                raise ValueError(f"relation {r}: indptr has {indptr.shape[0]} entries for {nq} query rows (want nq + 1)")
+            if indptr[0] != 0:
+                raise ValueError(f"relation {r}, row 0: indptr does not start at 0")
+            deg = np.diff(indptr)
+            if deg.size and deg.min() < 0:
+                raise ValueError(f"relation {r}, row {int(np.argmax(deg < 0))}: indptr is not monotone")
+            if indptr[-1] != indices.shape[0]:
+                raise ValueError(f"relation {r}, row {nq - 1}: indptr ends at {int(indptr[-1])}, the list has {indices.shape[0]} entries")
+            if indices.shape[0] >= (1 << 31):
+                raise ValueError(f"relation {r}: {indices.shape[0]} list entries do not fit int32")
+            rows = np.repeat(np.arange(nq, dtype=np.int64), deg)
+            bad = (indices < 0) | (indices >= span)
+            if bad.any():
+                at = int(np.argmax(bad))
+                raise ValueError(f"relation {r}, row {int(rows[at])}: neighbour id {int(indices[at])} outside [0, {span}) "
+                                 f"({N} base nodes + {nq} query nodes)")
+            key = np.unique(rows * span + indices)              # sorted by row, then by id; duplicates dropped
+            krow = key // span if key.size else key
+            ip = np.zeros(nq + 1, dtype=np.int64)
+            np.cumsum(np.bincount(krow, minlength=nq), out=ip[1:])
+            ix = (key - krow * span).astype(np.int32)
+            d = np.diff(ip)
+            self.csr.append((ip, ix))
+            self.deg_host.append(d)
+            self.max_degree = max(self.max_degree, int(d.max()) if d.size else 0)
+        self.device = None
+        self.X = None
+        self.indptr, self.indices = [], []
+        self.feat_stride = 0
+        self._desc = None
+
+    # -- constructors ---------------------------------------------------------
+    @classmethod
+    def from_adj_lists(cls, features, adj_lists: Sequence[AdjList], base, keys: str = "auto"):
+        """From the reference's form: ``features [nq, F]`` and, per relation, ``{node: set(global ids)}``; rows without a key
+        are empty.  keys="index": the dict keys are query indices in [0, nq); keys="global": global ids in [N, N + nq).
+        keys="auto" decides per dict - all keys >= N: global ids, else query indices - and raises where the two readings
+        cannot be told apart (a batch larger than the base graph, N < nq, with a key in [N, nq)): say which one is meant."""
+        if keys not in ("auto", "index", "global"):
+            raise ValueError(f"keys must be 'auto', 'index' or 'global', got {keys!r}")
+        N = int(base.n_nodes)
+        nq = int(features.shape[0])
+        csr = []
+        for r, adj in enumerate(adj_lists):
+            kk = np.fromiter((int(k) for k in adj.keys()), dtype=np.int64, count=len(adj))
+            if keys == "auto":
+                amb = (kk >= N) & (kk < nq)
+                if amb.any():
+                    raise ValueError(f"relation {r}, row {int(kk[int(np.argmax(amb))])}: the key is both a query index in [0, {nq}) "
+                                     f"and a global id in [{N}, {N + nq}) - pass keys='index' or keys='global'")
+                off = N if kk.size and kk.min() >= N else 0
+            else:
+                off = N if keys == "global" else 0
+            bad = (kk - off < 0) | (kk - off >= nq)
+            if bad.any():
+                k = int(kk[int(np.argmax(bad))])
+                raise ValueError(f"relation {r}, row {k}: not a query node - neither a query index in [0, {nq}) nor a "
+                                 f"global id in [{N}, {N + nq}), or the dict mixes the two")
+            deg = np.zeros(nq, dtype=np.int64)
+            for k, s in adj.items():
+                deg[int(k) - off] = len(s)
+            indptr = np.zeros(nq + 1, dtype=np.int64)
+            np.cumsum(deg, out=indptr[1:])
+            indices = np.empty(int(indptr[-1]), dtype=np.int64)
+            for k, s in adj.items():
+                if s:
+                    j = int(k) - off
+                    indices[indptr[j]:indptr[j + 1]] = np.fromiter(s, dtype=np.int64, count=len(s))
+            csr.append((indptr, indices))
+        return cls(features, csr, base)
+
+    @classmethod
+    def from_scipy(cls, features, matrices, base):
+        """From scipy sparse matrices of shape [nq, N + nq] (row j: the neighbours of query node j; every stored entry is an
+        edge).  Nothing is symmetrised and no self-loop is added: the lists are the caller's."""
+        import scipy.sparse as sp
+        N = int(base.n_nodes)
+        nq = int(features.shape[0])
+        csr = []
+        for r, m in enumerate(matrices):
+            if tuple(m.shape) != (nq, N + nq):
+                raise ValueError(f"relation {r}: matrix shape {tuple(m.shape)} != ({nq}, {N + nq}) = (nq, N + nq)")
+            c = sp.csr_matrix(m)
+            csr.append((c.indptr.astype(np.int64), c.indices.astype(np.int64)))
+        return cls(features, csr, base)
+
+    # -- device side ------------------------------------------------------------
+    def to(self, device, base_graph: "DeviceGraph"):
+        """Upload for ``base_graph`` (the features padded to its ``feat_stride``); returns self."""
+        g = base_graph
+        if (g.n_nodes, g.feat_dim, g.R) != (self.n_base, self.feat_dim, self.R):
+            raise ValueError(f"query batch built for a base graph of {self.n_base} nodes / {self.feat_dim} features / {self.R} "
+                             f"relations, not {g.n_nodes} / {g.feat_dim} / {g.R}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.PcgnnLibraryError("QueryBatch.to needs a GPU device: the PC-GNN hot path has no CPU fallback")
+        self.device = device
+        self.feat_stride = g.feat_stride
+        Xp = torch.zeros(max(self.nq, 1), self.feat_stride, dtype=torch.float32, device=device)
+        if self.nq:
+            Xp[:self.nq, :self.feat_dim] = torch.from_numpy(self.X_host).to(device)
+        self.X = Xp
+        self.indptr = [torch.from_numpy(ip).to(device) for ip, _ in self.csr]
+        self.indices = [torch.from_numpy(ix).to(device) if ix.size else torch.zeros(1, dtype=torch.int32, device=device)
+                        for _, ix in self.csr]
+        self._desc = None
+        return self
+
+    @property
+    def desc(self) -> _lib.GraphDesc:
+        if self.X is None:
+            raise _lib.PcgnnLibraryError("QueryBatch.desc: call to(device, base_graph) first")
+        if self._desc is None:
+            d = _lib.GraphDesc()
+            d.n_nodes, d.feat_dim, d.feat_stride = self.nq, self.feat_dim, self.feat_stride
+            d.n_rel, d.n_pos, d.max_degree = self.R, 0, self.max_degree
+            d.X = self.X.data_ptr()
+            d.train_pos = None
+            for r in range(self.R):
+                d.indptr[r] = self.indptr[r].data_ptr()
+                d.indices[r] = self.indices[r].data_ptr()
+            self._desc = d
+        return self._desc
+
+    def desc_ref(self):
+        return C.byref(self.desc)

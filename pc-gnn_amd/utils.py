@@ -145,6 +145,15 @@ def _device_eval(test_nodes, labels, model, batch_size: int, thresholds=None) ->
     return device_metrics(prob, y, thresholds)
 
 
+def predict_proba_new(query, model, ids=None, chunk=None) -> np.ndarray:
+    """Positive-class probabilities (float32, on the host) of the rows ``ids`` (None = all) of a ``graph.QueryBatch`` - new
+    nodes scored against the resident graph by ``FusedPCGNN.infer_new``: column 1 of the same sigmoid statement as
+    ``predict_proba``'s, so ``predict_proba_new(q, fz) == predict_proba(N + ids, full, B)[:, 1]`` for an engine ``full``
+    whose graph has the query rows appended."""
+    with torch.no_grad():
+        return np.ascontiguousarray(torch.sigmoid(model.infer_new(query, ids=ids, chunk=chunk)).float().cpu().numpy()[:, 1])
+
+
 def predict_proba(test_nodes, model, batch_size: int, labels=None) -> np.ndarray:
     """Test-mode class probabilities [n, 2] of ``test_nodes`` (sigmoid of the gnn logits, utils.py:305), on the host.
     A FusedPCGNN runs its whole-set pass (``infer``: one call, one score pass) - test-mode results do not depend on how the
