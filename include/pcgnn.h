@@ -318,6 +318,44 @@ int pcg_dense_select_train(const pcg_graph_desc *g, float *theta, float *m, floa
  * launches (more than PCG_PIPE_MAX_TILES = 128 tiles of 16 rows by default, rows beyond the select kernel's LDS keys, feature
  * rows of more than 256 floats, a dense shape that does not fit). */
 int32_t pcg_dense_select_blocks(const pcg_graph_desc *g, int32_t emb, int32_t B);
+/* The pipelined step with the label classifier TWO batches ahead.  The classifier's trajectory needs nothing the gather, the
+ * tiles or the weight gradients compute, so the chain classifier step -> table scores -> train-pos keys -> sort of batch t + 2
+ * runs one launch earlier than in pcg_dense_select_train's sequence, and every select finds its keys sorted a launch before it
+ * (no in-kernel sort, no row waits, a positive hub row's window search beside its key pass):
+ *     start:  [scores + sorted keys of batch 0 at hand]  pcg_choose_train_part(1, batch 0, keys_sorted = 1, clf_out = slot 0);
+ *             pcg_step_scores + pcg_pos_sort for batch 1 (the other s0 / key buffer);  pcg_clf_step(batch 1, t_ahead = 2, slot 1)
+ *     for t:  pcg_choose_train_part(2, batch t, s0 / pos_keys = the buffers of batch t + 2)    gather || Adam of t - 1 || scores +
+ *                                                                                               raw keys of t + 2
+ *             pcg_dense_select_ahead(batch t, batch t + 1, classifier batch t + 2)
+ *     last:   pcg_choose_train_part(2, last, score_next = 0), pcg_train_dense(adam_clf = 3, last, sort_keys = NULL)
+ * The fused launch: batch t's tiles (clf_in = slot t % 3), batch t + 1's select as pcg_choose_train_part(1) with keys_sorted = 1
+ * (s0 / pos_keys: batch t + 1's buffers), the classifier step of batch clf_ids / clf_labels / clf_B (Adam's t = count + 3; it
+ * counts the step for the tiles; clf_out = slot (t + 2) % 3), and riders that rank-sort sort_keys' raw half - formed by the
+ * gather launch in front - into its sorted half (sort_keys != pos_keys; nothing in the launch reads them).  clf_ids == NULL: no
+ * classifier step (the end of a sequence) - the tiles count the step; sort_keys == NULL: no riders (n_pos <= 16384 with them).
+ * PCG_E_UNSUPPORTED where pcg_dense_select_blocks(g, emb, B) is 0; pcg_dense_select_ahead_ok(g, emb, largest B of the sequence)
+ * is the caller's test for choosing this schedule. */
+int pcg_dense_select_ahead(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
+                           const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt, const void *plan,
+                           float inv_count, const float *clf_in, float *logits, float *center, float *row_loss, float *acts,
+                           int32_t act_ld, const int32_t *next_ids, const int32_t *next_labels, int32_t next_B, int32_t *next_cnt,
+                           const void *next_plan, float next_inv_count, float *clf_out, float *s0, uint64_t *pos_keys,
+                           const double *thresholds, const double *rho, int32_t add_self, void *workspace, int64_t list_capacity,
+                           uint32_t *status, uint32_t *sync_words, float *clf_next, const float *slabs, int32_t *step_counter,
+                           float lambda_1, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           const int32_t *clf_ids, const int32_t *clf_labels, int32_t clf_B, float clf_inv_count, uint64_t *sort_keys,
+                           void *stream);
+/* 1: the fused launch of a batch of B rows has room for the sort riders (a workgroup per 64 train positives, at most four per
+ * tile: they start on the CUs the tiles leave) beside the tiles and pcg_dense_select_blocks' select workgroups; a graph
+ * without train positives needs none.  0: the sequence keeps pcg_dense_select_train's schedule. */
+int32_t pcg_dense_select_ahead_ok(const pcg_graph_desc *g, int32_t emb, int32_t B);
+/* The label classifier's step for one batch as a launch of its own (select_rows' classifier workgroup alone): clf_next <- the
+ * classifier after the step; theta's classifier and clf_out (if not NULL) <- the one before it; Adam's t = step_counter[0] +
+ * t_ahead (>= 1); the count is left as it is.  slabs / sync_words: as pcg_choose_gather_train's (batches of more than 1024 rows). */
+int pcg_clf_step(const pcg_graph_desc *g, const int32_t *ids, const int32_t *labels, int32_t B, float *theta, float *m, float *v,
+                 int32_t emb, float *clf_next, float *clf_out, const float *slabs, const int32_t *step_counter, uint32_t *sync_words,
+                 float lambda_1, float inv_count, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t t_ahead,
+                 void *stream);
 int32_t pcg_sync_words_count(void);                 /* uint32 words of a `sync_words` buffer (zero-initialised ONCE by the caller; the
                                                         kernels leave every word but [1], [2] zero between launches) */
 int pcg_aggregate_lists_planned(const float *X, int32_t feat_dim, int32_t feat_stride, int64_t table_rows, int32_t n_rows,

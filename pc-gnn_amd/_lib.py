@@ -17,7 +17,7 @@ PCG_ST_SYNC_TIMEOUT = 4
 PCG_ST_SORT_OVERFLOW = 8
 PCG_ST_EVAL_INPUT = 16
 PCG_NORM_COUNT, PCG_NORM_SQRT_COUNT = 0, 1
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class GraphDesc(C.Structure):
@@ -73,6 +73,13 @@ PROTOTYPES = {
                                          _P, _P, _I32, _P, _P, C.c_float, _P, _P, _P, C.POINTER(_F64), C.POINTER(_F64), _I32, _P,
                                          _I64, _P, _P, _P, _P, _P, C.c_float, _F64, _F64, _F64, _F64, _F64, _P]),
     "pcg_dense_select_blocks": (_I32, [_G, _I32, _I32]),
+    "pcg_dense_select_ahead": (C.c_int, [_G, _P, _P, _P, _I32, _P, _P, _I32, _P, _I32, _P, _P, C.c_float, _P, _P, _P, _P, _P, _I32,
+                                         _P, _P, _I32, _P, _P, C.c_float, _P, _P, _P, C.POINTER(_F64), C.POINTER(_F64), _I32, _P,
+                                         _I64, _P, _P, _P, _P, _P, C.c_float, _F64, _F64, _F64, _F64, _F64, _P, _P, _I32, C.c_float,
+                                         _P, _P]),
+    "pcg_dense_select_ahead_ok": (_I32, [_G, _I32, _I32]),
+    "pcg_clf_step": (C.c_int, [_G, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, C.c_float, C.c_float, _F64, _F64, _F64, _F64,
+                               _F64, _I32, _P]),
     "pcg_choose_plan_bytes": (_I64, [_G, _I32, _I64]),
     "pcg_choose_data_bytes": (_I64, [_G, _I32, _I64]),
     "pcg_plan_batches": (C.c_int, [_G, _P, _P, _I32, _I32, C.POINTER(_F64), C.POINTER(_F64), _I32, _I32, _P, _I64, _I64, _P, _P,

@@ -160,6 +160,11 @@ struct ClfStep {
                                //   here, because the next step's select overwrites theta_clf while they run
     int32_t *count_step;       // non-null: the dense launch of the step before has not counted itself yet (t = step_counter + 2)
                                //   and the workgroup that applies Adam counts it (+1) once it has read the count
+    // the classifier stepped further ahead than the selection it rides with (pcg_dense_select_ahead: the select of batch t + 1
+    // carries the step of batch t + 2; pcg_clf_step: a step with no selection at all):
+    const int32_t *nodes, *labels;   // non-null: the batch this step is for (null: the launch's own, ChooseArgs::nodes / labels / B)
+    int32_t B;
+    int32_t t_ahead;           // > 0: Adam's t = step_counter + t_ahead (dense launches of earlier steps that have not counted yet + 1)
 };
 
 struct ChooseArgs {
@@ -222,6 +227,8 @@ int launch_select_rows(const ChooseArgs &a, hipStream_t st);
 struct DenseArgs;
 int dense_select_blocks(const pcg_graph_desc &g, int emb, int B);
 int launch_dense_select(const DenseArgs &d, const ChooseArgs &a, int n_sel, hipStream_t st);
+// select.hip: the label classifier's step as a launch of its own (c.nodes / labels / B name the batch)
+int launch_clf_step(const ClfStep &c, const pcg_graph_desc &g, hipStream_t st);
 // sort.hip: the one-launch bucket sort over raw keys (RANK_MAX < n_pos <= 131072)
 int launch_bk_onepass(const uint64_t *raw, int n_pos, uint64_t *keys, int cap, uint32_t *status, hipStream_t st);
 

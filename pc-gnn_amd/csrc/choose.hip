@@ -736,6 +736,8 @@ static int choose_args(pcg::ChooseArgs &a, const pcg_graph_desc *g, const int32_
     a.clf.clf_next = nullptr;
     a.clf.clf_out = nullptr;
     a.clf.count_step = nullptr;
+    a.clf.nodes = a.clf.labels = nullptr;
+    a.clf.B = a.clf.t_ahead = 0;
     a.n_wg_units = 0;
     pcg::carve1(g, B, list_capacity, static_cast<unsigned char *>(workspace), &a.w,
                 static_cast<unsigned char *>(const_cast<void *>(plan)));
@@ -1262,27 +1264,55 @@ int32_t pcg_dense_select_blocks(const pcg_graph_desc *g, int32_t emb, int32_t B)
     return g ? pcg::dense_select_blocks(*g, emb, B) : 0;
 }
 
-int pcg_dense_select_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
-                           const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt, const void *plan,
-                           float inv_count, const float *clf_in, float *logits, float *center, float *row_loss, float *acts,
-                           int32_t act_ld, const int32_t *next_ids, const int32_t *next_labels, int32_t next_B, int32_t *next_cnt,
-                           const void *next_plan, float next_inv_count, float *clf_out, float *s0, uint64_t *pos_keys,
-                           const double *thresholds, const double *rho, int32_t add_self, void *workspace, int64_t list_capacity,
-                           uint32_t *status, uint32_t *sync_words, float *clf_next, const float *slabs, int32_t *step_counter,
-                           float lambda_1, double lr, double beta1, double beta2, double eps, double weight_decay, void *stream) {
-    if (!g || B < 1 || next_B < 1 || !clf_in || !clf_out || !acts || !cnt || !next_cnt || !workspace || !sync_words || !step_counter)
+// what pcg_dense_select_ahead adds to the fused launch (all null / 0: pcg_dense_select_train, the select half stepping its own
+// batch's classifier and sorting its own keys)
+struct AheadExtra {
+    bool on = false;
+    const int32_t *clf_ids = nullptr, *clf_labels = nullptr;   // the batch whose classifier step rides here (null: none - the tiles count the step)
+    int32_t clf_B = 0;
+    float clf_inv_count = 0.f;
+    uint64_t *sort_keys = nullptr;                             // [sorted half | raw half]: the riders sort the raw half into the sorted one
+};
+
+static int dense_select_launch(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
+                               const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt, const void *plan,
+                               float inv_count, const float *clf_in, float *logits, float *center, float *row_loss, float *acts,
+                               int32_t act_ld, const int32_t *next_ids, const int32_t *next_labels, int32_t next_B, int32_t *next_cnt,
+                               const void *next_plan, float next_inv_count, float *clf_out, float *s0, uint64_t *pos_keys,
+                               const double *thresholds, const double *rho, int32_t add_self, void *workspace, int64_t list_capacity,
+                               uint32_t *status, uint32_t *sync_words, float *clf_next, const float *slabs, int32_t *step_counter,
+                               float lambda_1, double lr, double beta1, double beta2, double eps, double weight_decay,
+                               const AheadExtra &x2, void *stream) {
+    if (!g || B < 1 || next_B < 1 || !clf_in || !acts || !cnt || !next_cnt || !workspace || !sync_words || !step_counter)
         return PCG_E_ARG;
+    const bool clf_on = !x2.on || x2.clf_ids != nullptr;
+    if (clf_on && !clf_out) return PCG_E_ARG;
+    if (x2.on && x2.clf_ids && (!x2.clf_labels || x2.clf_B < 1)) return PCG_E_ARG;
     if (list_capacity < 1 || list_capacity >= (1ll << 31)) return PCG_E_ARG;
     const int n_sel = pcg::dense_select_blocks(*g, emb, B);
     if (n_sel <= 0) return PCG_E_UNSUPPORTED;
-    // batch t + 1's select launch as pcg_choose_train_part(1) sets it up, its train-pos keys unsorted (it sorts them itself)
+    // batch t + 1's select launch as pcg_choose_train_part(1) sets it up.  pcg_dense_select_train: its train-pos keys unsorted (it
+    // sorts them itself); pcg_dense_select_ahead: sorted a launch earlier (keys_sorted = 1)
     TrainParts t;
     int rc = train_parts(t, false, g, next_ids, next_labels, next_B, s0, pos_keys, thresholds, rho, add_self, const_cast<float *>(agg),
                          agg_stride, next_cnt, workspace, next_plan, list_capacity, status, sync_words, theta, m, v, emb, clf_next, slabs,
-                         step_counter, lambda_1, next_inv_count, lr, beta1, beta2, eps, weight_decay, 1, nullptr, nullptr, 0, nullptr, 0);
+                         step_counter, lambda_1, next_inv_count, lr, beta1, beta2, eps, weight_decay, 1, nullptr, nullptr, 0, nullptr,
+                         x2.on ? 1 : 0);
     if (rc != PCG_OK) return rc;
     t.a.clf.clf_out = clf_out;
     t.a.clf.count_step = step_counter;
+    if (x2.on && !x2.clf_ids) {
+        t.a.clf.clf_next = nullptr;               // no classifier step in this launch: every select workgroup is a row workgroup
+        t.a.clf.count_step = nullptr;
+    } else if (x2.on) {
+        // the step of batch t + 2: the dense launches of t (beside it) and t + 1 have not counted themselves
+        t.a.clf.nodes = x2.clf_ids;
+        t.a.clf.labels = x2.clf_labels;
+        t.a.clf.B = x2.clf_B;
+        t.a.clf.scale = x2.clf_inv_count * lambda_1;
+        t.a.clf.n_wg = (x2.clf_B + 1023) / 1024 > 8 ? 8 : (x2.clf_B + 1023) / 1024;
+        t.a.clf.t_ahead = 3;
+    }
     // batch t's tiles as pcg_train_dense(adam_clf = 3) sets them up - without the riding key sort, without counting the step,
     // with the classifier the select launch of batch t left in clf_in
     pcg::DenseExtra x;
@@ -1297,13 +1327,102 @@ int pcg_dense_select_train(const pcg_graph_desc *g, float *theta, float *m, floa
     x.act_ld = act_ld;
     pcg::DenseArgs d;
     int n_sort_blocks = 0;
+    // (no classifier step beside the tiles: nothing in the launch reads the count, the tiles count the step themselves)
     rc = pcg::dense_args(d, n_sort_blocks, g, theta, emb, ids, labels, B, agg, agg_stride, lambda_1, inv_count, logits, center, nullptr,
-                         row_loss, const_cast<float *>(slabs), nullptr, x);
+                         row_loss, const_cast<float *>(slabs), t.a.clf.clf_next ? nullptr : step_counter, x);
     if (rc != PCG_OK) return rc;
     d.W_clf = clf_in;
     d.b_clf = clf_in + 2 * g->feat_dim;
     d.stamps = nullptr;
+    if (x2.on && x2.sort_keys && g->n_pos > 0) {
+        const int64_t cap = pcg_pos_sort_capacity(g->n_pos) / 2;
+        d.sort_out = x2.sort_keys;
+        d.sort_raw = x2.sort_keys + cap;
+        d.sort_n = g->n_pos;
+        d.sort_cap = (int32_t)cap;
+    }
     return pcg::launch_dense_select(d, t.a, n_sel, static_cast<hipStream_t>(stream));
+}
+
+int pcg_dense_select_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
+                           const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt, const void *plan,
+                           float inv_count, const float *clf_in, float *logits, float *center, float *row_loss, float *acts,
+                           int32_t act_ld, const int32_t *next_ids, const int32_t *next_labels, int32_t next_B, int32_t *next_cnt,
+                           const void *next_plan, float next_inv_count, float *clf_out, float *s0, uint64_t *pos_keys,
+                           const double *thresholds, const double *rho, int32_t add_self, void *workspace, int64_t list_capacity,
+                           uint32_t *status, uint32_t *sync_words, float *clf_next, const float *slabs, int32_t *step_counter,
+                           float lambda_1, double lr, double beta1, double beta2, double eps, double weight_decay, void *stream) {
+    return dense_select_launch(g, theta, m, v, emb, ids, labels, B, agg, agg_stride, cnt, plan, inv_count, clf_in, logits, center, row_loss,
+                               acts, act_ld, next_ids, next_labels, next_B, next_cnt, next_plan, next_inv_count, clf_out, s0, pos_keys,
+                               thresholds, rho, add_self, workspace, list_capacity, status, sync_words, clf_next, slabs, step_counter,
+                               lambda_1, lr, beta1, beta2, eps, weight_decay, AheadExtra(), stream);
+}
+
+/* 1: the fused launch of a batch of B rows has room for pcg_dense_select_ahead's sort riders beside the tiles and the select
+ * workgroups: the riders (a workgroup per 64 train positives) are the last workgroups of the grid and start on the CUs the tiles
+ * leave, at most four rounds of them (a round is ~3 us, the select half outlasts the tiles by more than that).  Host helper. */
+int32_t pcg_dense_select_ahead_ok(const pcg_graph_desc *g, int32_t emb, int32_t B) {
+    if (!g || pcg::dense_select_blocks(*g, emb, B) <= 0) return 0;
+    if (g->n_pos <= 0) return 1;                                      // (no keys at all)
+    if (g->n_pos > pcg::RANK_MAX || !g->train_pos) return 0;
+    const int tiles = (B + pcg::TB - 1) / pcg::TB, riders = (g->n_pos + PCG_WAVE - 1) / PCG_WAVE;
+    return riders <= 4 * tiles ? 1 : 0;
+}
+
+int pcg_dense_select_ahead(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
+                           const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt, const void *plan,
+                           float inv_count, const float *clf_in, float *logits, float *center, float *row_loss, float *acts,
+                           int32_t act_ld, const int32_t *next_ids, const int32_t *next_labels, int32_t next_B, int32_t *next_cnt,
+                           const void *next_plan, float next_inv_count, float *clf_out, float *s0, uint64_t *pos_keys,
+                           const double *thresholds, const double *rho, int32_t add_self, void *workspace, int64_t list_capacity,
+                           uint32_t *status, uint32_t *sync_words, float *clf_next, const float *slabs, int32_t *step_counter,
+                           float lambda_1, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           const int32_t *clf_ids, const int32_t *clf_labels, int32_t clf_B, float clf_inv_count, uint64_t *sort_keys,
+                           void *stream) {
+    AheadExtra x2;
+    x2.on = true;
+    x2.clf_ids = clf_ids;
+    x2.clf_labels = clf_labels;
+    x2.clf_B = clf_B;
+    x2.clf_inv_count = clf_inv_count;
+    x2.sort_keys = sort_keys;
+    if (sort_keys && sort_keys == pos_keys) return PCG_E_ARG;       // (the select half reads pos_keys while the riders write)
+    return dense_select_launch(g, theta, m, v, emb, ids, labels, B, agg, agg_stride, cnt, plan, inv_count, clf_in, logits, center, row_loss,
+                               acts, act_ld, next_ids, next_labels, next_B, next_cnt, next_plan, next_inv_count, clf_out, s0, pos_keys,
+                               thresholds, rho, add_self, workspace, list_capacity, status, sync_words, clf_next, slabs, step_counter,
+                               lambda_1, lr, beta1, beta2, eps, weight_decay, x2, stream);
+}
+
+/* The label classifier's step for one batch as a launch of its own: clf_next <- the classifier after the step, theta's classifier
+ * and clf_out (if given) <- the one before it; Adam's t = step_counter[0] + t_ahead (the count is not changed). */
+int pcg_clf_step(const pcg_graph_desc *g, const int32_t *ids, const int32_t *labels, int32_t B, float *theta, float *m, float *v,
+                 int32_t emb, float *clf_next, float *clf_out, const float *slabs, const int32_t *step_counter, uint32_t *sync_words,
+                 float lambda_1, float inv_count, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t t_ahead,
+                 void *stream) {
+    if (!g || !g->X || !ids || !labels || B < 1 || !theta || !m || !v || !clf_next || !slabs || !step_counter || !sync_words || t_ahead < 1)
+        return PCG_E_ARG;
+    const int64_t n_params = pcg_dense_n_params(g->feat_dim, emb, g->n_rel);
+    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, emb, g->n_rel, 3, 0);
+    if (n_params < 0 || o_clf < 0) return PCG_E_ARG;
+    pcg::ClfStep c;
+    c.clf_next = clf_next;
+    c.theta_clf = theta + o_clf;
+    c.m = m + o_clf;
+    c.v = v + o_clf;
+    c.step_counter = step_counter;
+    c.scale = inv_count * lambda_1;
+    c.h = {(float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay};
+    c.n_wg = (B + 1023) / 1024 > 8 ? 8 : (B + 1023) / 1024;
+    c.part = const_cast<float *>(slabs) + o_clf;
+    c.part_stride = n_params;
+    c.ticket = sync_words;
+    c.clf_out = clf_out;
+    c.count_step = nullptr;
+    c.nodes = ids;
+    c.labels = labels;
+    c.B = B;
+    c.t_ahead = t_ahead;
+    return pcg::launch_clf_step(c, *g, static_cast<hipStream_t>(stream));
 }
 
 int pcg_choose_aggregate_planned(const pcg_graph_desc *g, const int32_t *nodes, const int32_t *labels, int32_t B,

@@ -1148,7 +1148,8 @@ __device__ __forceinline__ void clf_step_body(const ClfStep c, const float *__re
     const float p_old = c.clf_next[ic], m_old = c.m[ic], v_old = c.v[ic];
     // this step's dense launch counts it; it has not run yet (count_step: nor has the one of the step before - it runs beside
     // this launch, which counts for it below)
-    const float t = (float)(c.step_counter[0] + (c.count_step ? 2 : 1));
+    // (t_ahead: a step further ahead - every dense launch between the count and this step's own is still to count itself)
+    const float t = (float)(c.step_counter[0] + (c.t_ahead > 0 ? c.t_ahead : (c.count_step ? 2 : 1)));
     constexpr int NPRE = 2;                                     // ids / labels per thread of a block: RB <= NPRE * NT
     int nb = B < RB ? B : RB;
     int id_pre[NPRE], y_pre[NPRE];
@@ -1359,12 +1360,15 @@ __device__ __forceinline__ void select_rows_body(const ChooseArgs &a, int blk, i
         if (a.stamps && leader) a.stamps[(size_t)a.g.n_rel * a.B * 8 + 2] = wall_clock64();
         // this workgroup's slice of the batch: whole multiples of 64 rows (every workgroup has some: n_wg <= ceil(B / 1024))
         const int cw = blk;
-        const int per = ((a.B + a.clf.n_wg - 1) / a.clf.n_wg + PCG_WAVE - 1) & ~(PCG_WAVE - 1);
-        const int r0 = cw * per < a.B ? cw * per : a.B, r1 = r0 + per < a.B ? r0 + per : a.B;
+        // (the batch the step is for: the launch's own, or - the classifier stepped ahead - the one ClfStep names)
+        const int32_t *cn = a.clf.nodes ? a.clf.nodes : a.nodes, *cl = a.clf.nodes ? a.clf.labels : a.labels;
+        const int cB = a.clf.nodes ? a.clf.B : a.B;
+        const int per = ((cB + a.clf.n_wg - 1) / a.clf.n_wg + PCG_WAVE - 1) & ~(PCG_WAVE - 1);
+        const int r0 = cw * per < cB ? cw * per : cB, r1 = r0 + per < cB ? r0 + per : cB;
         unsigned long long *cst = (a.stamps && cw == 0) ? a.stamps + (size_t)a.g.n_rel * a.B * 8 + 8 : nullptr;
         if ((int)threadIdx.x >= SEL_NW * PCG_WAVE) return;          // (a wave that has ended is not waited for at a barrier)
-        if constexpr (CLF == 2) clf_step_body<2, 2>(a.clf, a.g.X, a.g.feat_dim, a.g.feat_stride, a.nodes + r0, a.labels + r0, r1 - r0, lds, (int)threadIdx.x, cst, cw);
-        else if constexpr (CLF == 1) clf_step_body<1, 3>(a.clf, a.g.X, a.g.feat_dim, a.g.feat_stride, a.nodes + r0, a.labels + r0, r1 - r0, lds, (int)threadIdx.x, cst, cw);
+        if constexpr (CLF == 2) clf_step_body<2, 2>(a.clf, a.g.X, a.g.feat_dim, a.g.feat_stride, cn + r0, cl + r0, r1 - r0, lds, (int)threadIdx.x, cst, cw);
+        else if constexpr (CLF == 1) clf_step_body<1, 3>(a.clf, a.g.X, a.g.feat_dim, a.g.feat_stride, cn + r0, cl + r0, r1 - r0, lds, (int)threadIdx.x, cst, cw);
         if (a.stamps && leader) a.stamps[(size_t)a.g.n_rel * a.B * 8 + 3] = wall_clock64();
         return;
     }
@@ -1454,6 +1458,32 @@ template <int CLF>
 __global__ void __launch_bounds__(SEL_NW *PCG_WAVE) __attribute__((amdgpu_waves_per_eu(6, 8))) select_rows(const ChooseArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     select_rows_body<CLF>(a, (int)blockIdx.x, (int)gridDim.x, smem);
+}
+
+// The label classifier's step as a launch of its own (pcg_clf_step: the start of a sequence whose classifier runs two batches
+// ahead - the step of batch 1 has no select launch to ride in).  clf_step_body on select_rows' 8 waves, with its LDS area, its
+// row slices and its summation order: the same result bit for bit.  c.nodes / labels / B: the batch; c.n_wg workgroups.
+template <int CLF>
+__global__ void __launch_bounds__(SEL_NW *PCG_WAVE) clf_step_kernel(const ClfStep c, const float *__restrict__ X, int F, int stride) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint32_t *lds = reinterpret_cast<uint32_t *>(smem);
+    const int cw = (int)blockIdx.x;
+    const int per = ((c.B + c.n_wg - 1) / c.n_wg + PCG_WAVE - 1) & ~(PCG_WAVE - 1);
+    const int r0 = cw * per < c.B ? cw * per : c.B, r1 = r0 + per < c.B ? r0 + per : c.B;
+    if constexpr (CLF == 2) clf_step_body<2, 2>(c, X, F, stride, c.nodes + r0, c.labels + r0, r1 - r0, lds, (int)threadIdx.x, nullptr, cw);
+    else clf_step_body<1, 3>(c, X, F, stride, c.nodes + r0, c.labels + r0, r1 - r0, lds, (int)threadIdx.x, nullptr, cw);
+}
+
+int launch_clf_step(const ClfStep &c, const pcg_graph_desc &g, hipStream_t st) {
+    // (every workgroup has rows: n_wg <= ceil(B / 1024); feature rows of <= 512 floats: the body's LDS block of ids)
+    if (!c.clf_next || !c.nodes || !c.labels || c.B < 1 || c.n_wg < 1 || c.n_wg > 8 || c.n_wg > (c.B + 1023) / 1024 || g.feat_stride > 512)
+        return PCG_E_ARG;
+    if (c.n_wg > 1 && (!c.part || !c.ticket)) return PCG_E_ARG;
+    const size_t smem = sizeof(uint32_t) * WG_KEYCAP;
+    if (g.feat_stride > 256) hipLaunchKernelGGL(clf_step_kernel<2>, dim3(c.n_wg), dim3(SEL_NW * PCG_WAVE), smem, st, c, g.X, g.feat_dim, g.feat_stride);
+    else hipLaunchKernelGGL(clf_step_kernel<1>, dim3(c.n_wg), dim3(SEL_NW * PCG_WAVE), smem, st, c, g.X, g.feat_dim, g.feat_stride);
+    PCG_LAUNCH_CHECK();
+    return PCG_OK;
 }
 
 // Rows beyond the LDS key capacity (> WG_KEYCAP neighbours), in a launch of their own: the multi-pass selection over keys kept
@@ -1622,15 +1652,39 @@ int launch_select_rows(const ChooseArgs &a, hipStream_t st) {
 //   workspace    the select half writes the selection list (data part) and its own plan slot; the tiles read the partial sums
 //                (data part) and batch t's plan slot.  The list comes first in the data part (carve): its place does not
 //                depend on the batch size, so it never overlaps the partial sums of another batch size.
+// With the classifier two batches ahead (pcg_dense_select_ahead) the launch holds four parts - the tiles of t, the select of
+// t + 1 (keys sorted a launch earlier: n_sort = 0, nothing waits), the classifier step of t + 2, riders that sort t + 2's keys:
+//   s0 parity    the select half reads batch t + 1's score table; batch t + 2's was written by the gather launch in front, into
+//                the OTHER table, and nothing in this launch touches it (two tables, by batch parity);
+//   key parity   the select half reads batch t + 1's sorted keys; the riders read the raw half and write the sorted half of the
+//                OTHER key buffer (batch t + 2's: the host refuses sort_keys == pos_keys), which no part of this launch reads -
+//                its first reader is the select half of the NEXT launch;
+//   classifier   three slots: the tiles read slot t % 3 (written two fused launches ago, or by the sequence's start), the step
+//                of t + 2 writes slot (t + 2) % 3, slot (t + 1) % 3 - the next launch's tiles' - is left alone.  clf_next, the
+//                classifier's m / v and theta's copy are the classifier workgroup's alone, as before;
+//   step count   the classifier's Adam reads the count + 3 (the tiles beside it and those of t + 1 have not counted) and counts
+//                for the tiles afterwards; a launch without a classifier step (the end of a sequence) has no reader of the
+//                count at all, and its tiles count themselves (DenseArgs::step_counter);
+//   riders' sync none: rank_sort_body's workgroups share nothing (each ranks its 64 keys against all raw keys and stores them
+//   words        at ranks < n_pos <= sort_cap); nobody in the launch waits for them.  sync words [3 ..] are unused here.
 template <bool WLDS, int F_, int E_, int R_>
-__global__ void __launch_bounds__(DENSE_THREADS) dense_select_kernel(const DenseArgs d, const ChooseArgs s) {
+__global__ void __launch_bounds__(DENSE_THREADS) dense_select_kernel(const DenseArgs d, const ChooseArgs s, const int n_sel) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int n_dense = d.n_tile_blocks;
     if ((int)blockIdx.x < n_dense) {
         dense_tile_body<WLDS, F_, E_, R_>(d, (int)blockIdx.x, reinterpret_cast<float *>(smem));
         return;
     }
-    select_rows_body<1, DENSE_WAVES>(s, (int)blockIdx.x - n_dense, (int)gridDim.x - n_dense, smem);
+    if ((int)blockIdx.x >= n_dense + n_sel) {
+        // the sort riders (the classifier stepped ahead: d.sort_raw != null, host-checked): the LAST workgroups of the grid, so
+        // that they start on the CUs the tiles leave - dense_step_kernel's riders, for the batch after the one selected here
+        uint64_t *sh = reinterpret_cast<uint64_t *>(smem);
+        int *part = reinterpret_cast<int *>(sh + DENSE_SORT_TILE);
+        rank_sort_body<DENSE_SORT_TILE, DENSE_WAVES, false>(nullptr, nullptr, d.sort_n, d.sort_cap, d.sort_out,
+                                                            (int)blockIdx.x - n_dense - n_sel, sh, part, d.sort_raw);
+        return;
+    }
+    select_rows_body<1, DENSE_WAVES>(s, (int)blockIdx.x - n_dense, n_sel, smem);
 }
 
 // Select workgroups of the fused launch for a dense batch of B rows, or 0: the step keeps its three launches.  The selection
@@ -1657,16 +1711,22 @@ int dense_select_blocks(const pcg_graph_desc &g, int emb, int B) {
 }
 
 int launch_dense_select(const DenseArgs &d, const ChooseArgs &a, int n_sel, hipStream_t st) {
-    if (!a.clf.clf_next || a.g.feat_stride > 256 || a.g.max_degree > WG_KEYCAP || d.sort_raw || d.n_split != 1 || n_sel < 1)
-        return PCG_E_ARG;
+    if (a.g.feat_stride > 256 || a.g.max_degree > WG_KEYCAP || d.n_split != 1 || n_sel < 1) return PCG_E_ARG;
+    // sort riders (d.sort_raw): sort_n keys in groups of 64, a workgroup each, behind the select workgroups; the ranks they store
+    // at are < sort_n <= sort_cap
+    if (d.sort_raw && (!d.sort_out || d.sort_n < 1 || d.sort_n > RANK_MAX || d.sort_cap < d.sort_n)) return PCG_E_ARG;
+    const int n_riders = d.sort_raw ? (d.sort_n + PCG_WAVE - 1) / PCG_WAVE : 0;
+    const int clf_wg = a.clf.clf_next ? a.clf.n_wg : 0;
+    if (clf_wg && a.clf.nodes && (!a.clf.labels || a.clf.B < 1 || clf_wg > (a.clf.B + 1023) / 1024)) return PCG_E_ARG;
+    if (n_sel - clf_wg < 8) return PCG_E_ARG;
     ChooseArgs as = a;
     as.key_cap = DENSE_WAVES * WAVE_AREA;
-    const int rc = select_sort_shape(as, n_sel - a.clf.n_wg);
+    const int rc = select_sort_shape(as, n_sel - clf_wg);
     if (rc != PCG_OK) return rc;
     const int F = d.feat_dim, E = d.emb, R = d.n_rel;
     const bool wlds = dense_wlds(F, E, R);
     const size_t dsm = dense_smem_bytes(F, E, R, wlds), ssm = select_smem_bytes(DENSE_WAVES * WAVE_AREA, DENSE_WAVES);
-    typedef void (*kern_t)(const DenseArgs, const ChooseArgs);
+    typedef void (*kern_t)(const DenseArgs, const ChooseArgs, const int);
     kern_t kern;
     if (R == 3 && F == 32 && E == 64 && wlds) kern = dense_select_kernel<true, 32, 64, 3>;
     else if (R == 3 && F == 25 && E == 64 && wlds) kern = dense_select_kernel<true, 25, 64, 3>;
@@ -1686,7 +1746,8 @@ int launch_dense_select(const DenseArgs &d, const ChooseArgs &a, int n_sel, hipS
                 break;
             }
     }
-    hipLaunchKernelGGL(kern, dim3(d.n_tile_blocks + n_sel), dim3(DENSE_THREADS), dsm > ssm ? dsm : ssm, st, d, as);
+    static_assert(sizeof(uint64_t) * DENSE_SORT_TILE + sizeof(int) * DENSE_THREADS <= 64 * 1024, "the riders' LDS is within every dense shape's");
+    hipLaunchKernelGGL(kern, dim3(d.n_tile_blocks + n_sel + n_riders), dim3(DENSE_THREADS), dsm > ssm ? dsm : ssm, st, d, as, n_sel);
     PCG_LAUNCH_CHECK();
     return PCG_OK;
 }

@@ -92,7 +92,7 @@ def default_infer_chunk(caps: np.ndarray, workspace_bytes, max_bytes: int, min_c
 class FusedPCGNN:
     def __init__(self, model: PCALayer, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8,
                  max_batch: int = 1024, global_batch_scale: int = 1, list_capacity: Optional[int] = None,
-                 pipeline: Optional[bool] = None, infer_workspace_bytes: int = 1 << 30):
+                 pipeline: Optional[bool] = None, infer_workspace_bytes: int = 1 << 30, clf_ahead: Optional[bool] = None):
         lib = _lib.load()
         self.lib = lib
         self.model = model
@@ -157,6 +157,18 @@ class FusedPCGNN:
         # pipeline=None: on unless PCG_PIPELINE=0 (A/B runs)
         env = os.environ.get("PCG_PIPELINE")
         self.pipeline = bool(pipeline) if pipeline is not None else env != "0"
+        # ... with the label classifier stepped TWO batches ahead (_enqueue_pipelined_ahead): every select of a sequence finds its
+        # train-pos keys sorted a launch earlier.  It costs three launches more at the start of a sequence and saves the select
+        # half its in-kernel sort and the positive rows' wait for it, which grow with the number of keys: clf_ahead=None / no
+        # PCG_CLF_AHEAD: on for graphs of 1024 train positives and more (measured: YelpChi-like, 2.7 K keys, 39.1 -> 37.4 us per
+        # step; Amazon-like, 0.3 K keys and 24-step sequences, 27.1 -> 27.5: off there); True / False, PCG_CLF_AHEAD=1 / 0: forced
+        env = os.environ.get("PCG_CLF_AHEAD")
+        if clf_ahead is not None:
+            self.clf_ahead = bool(clf_ahead)
+        elif env in ("0", "1"):
+            self.clf_ahead = env == "1"
+        else:
+            self.clf_ahead = g.n_pos >= 1024
         self.status = torch.zeros(1, dtype=torch.int32, device=self.dev)   # ONE device status word
         self._graphs = {}
         self._ep_graphs = {}
@@ -209,7 +221,13 @@ class FusedPCGNN:
         # read the other; every other step uses the first
         self.cnt2 = torch.empty(2, g.R, B, dtype=torch.int32, device=dev)
         self.cnt = self.cnt2[0]
-        self.clf_slots = torch.empty(2, 2 * self.F + 2, dtype=torch.float32, device=dev)   # the classifier each step's dense tiles read
+        # the classifier each pipelined step's dense tiles read: a ring of three (the tiles of t read the one batch t was selected
+        # with while the steps of t + 1 and t + 2 have left theirs: _enqueue_pipelined_ahead; _enqueue_pipelined uses two)
+        self.clf_slots = torch.empty(3, 2 * self.F + 2, dtype=torch.float32, device=dev)
+        # the second score table / key buffer of a sequence whose classifier runs two batches ahead: batch t + 2's scores and keys
+        # are written while batch t + 1's are still to be read.  Scratch of a sequence: it begins and ends on s0 / keys
+        self.s0_alt = torch.empty_like(self.s0)
+        self.keys_alt = torch.empty_like(self.keys)
         self._pipe_blocks = int(lib.pcg_dense_select_blocks(g.desc_ref(), self.E, B))
         self.logits = torch.empty(B, 2, dtype=torch.float32, device=dev)
         self.center = torch.empty(B, 2, dtype=torch.float32, device=dev)
@@ -307,19 +325,22 @@ class FusedPCGNN:
         self.clf_next.copy_(self.theta[self.n_rest:])
         self._fresh = False
 
-    def _enqueue_refresh(self, touched: Optional[int] = None):
+    def _enqueue_refresh(self, touched: Optional[int] = None, into=None):
         """scores + unsorted train-pos keys of the classifier the next select launch uses (clf_next), one launch (no update of
         anything): the first training step after anything else has run, and every first step of an epoch of a touched-rows
-        engine (whose previous step could not know this batch's map)."""
+        engine (whose previous step could not know this batch's map).  into: another (s0, keys) pair than the engine's own - a
+        sequence's second buffers; the engine's own are then left as they are."""
         g = self.g
         F = self.F
+        s0, keys = (self.s0, self.keys) if into is None else into
         _lib.check(self.lib.pcg_step_scores(
-            g.desc_ref(), _p(self.clf_next), C.c_void_p(self.clf_next.data_ptr() + 8 * F), 0, g.n_nodes, _p(self.s0), None,
-            _p(self.keys) if g.n_pos else None, -1, _p(self.sync), None if touched is None else C.c_void_p(touched),
+            g.desc_ref(), _p(self.clf_next), C.c_void_p(self.clf_next.data_ptr() + 8 * F), 0, g.n_nodes, _p(s0), None,
+            _p(keys) if g.n_pos else None, -1, _p(self.sync), None if touched is None else C.c_void_p(touched),
             self._stream()), "pcg_step_scores")
         if self.presort:                             # (the steps that follow are told the keys are sorted)
-            ops.pos_sort(g, self.s0, self.keys)
-        self._fresh = True
+            ops.pos_sort(g, s0, keys)
+        if into is None:
+            self._fresh = True
 
     def _enqueue_choose_train(self, ids, labels, B, plan: int, score_next: bool, next_touched: Optional[int] = None):
         """select (+ the label classifier's step for this batch) and gather (+ the deferred update of the other parameters,
@@ -395,16 +416,84 @@ class FusedPCGNN:
         return (self.pipeline and not self.touched_on and len(batches) >= 2 and self._pipe_blocks > 0
                 and max(B for _, B in batches) <= self.maxB)
 
-    def _train_args(self, ids, labels, B, plan: int, cnt, keys_sorted: int):
-        """pcg_choose_gather_train's arguments (without the stream) for a whole-table engine's step that scores the next one"""
+    def _train_args(self, ids, labels, B, plan: int, cnt, keys_sorted: int, bufs=None, score_next: bool = True):
+        """pcg_choose_gather_train's arguments (without the stream) for a whole-table engine's step that scores the next one.
+        bufs: the (s0, keys) pair the launch reads (select) or writes (the gather launch's score pass), default the engine's own"""
         g = self.g
         agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
         b1, b2 = self.betas
-        return (g.desc_ref(), _p(ids), _p(labels), B, _p(self.s0), _p(self.keys) if g.n_pos else None, self._thr, self._rhos, 0,
+        s0, keys = (self.s0, self.keys) if bufs is None else bufs
+        return (g.desc_ref(), _p(ids), _p(labels), B, _p(s0), _p(keys) if g.n_pos else None, self._thr, self._rhos, 0,
                 _p(agg), agg.stride(-2), _p(cnt), _p(self.data), C.c_void_p(plan), self.list_capacity, _p(self.status), _p(self.sync),
                 _p(self.theta), _p(self.m), _p(self.v), self.E, _p(self.clf_next), _p(self.slabs), _p(self.step_counter),
-                self.lambda_1, 1.0 / (B * self.scale), self.lr, b1, b2, self.eps, self.wd, 1, None, _p(self.acts), self.act_ld,
-                _p(self.wg_scratch), keys_sorted)
+                self.lambda_1, 1.0 / (B * self.scale), self.lr, b1, b2, self.eps, self.wd, 1 if score_next else 0, None,
+                _p(self.acts), self.act_ld, _p(self.wg_scratch), keys_sorted)
+
+    def _ahead(self, steps) -> bool:
+        """whether a pipelined sequence [(ids, labels, B, plan)] steps the label classifier two batches ahead
+        (_enqueue_pipelined_ahead): three steps or more (shorter ones have no steady state), the keys a refresh leaves are sorted
+        (presort; or there are none), and the fused launch has room for the sort riders (pcg_dense_select_ahead_ok)"""
+        return (self.clf_ahead and len(steps) >= 3 and (self.presort or self.g.n_pos == 0)
+                and bool(self.lib.pcg_dense_select_ahead_ok(self.g.desc_ref(), self.E, max(s[2] for s in steps))))
+
+    def _enqueue_pipelined_ahead(self, steps):
+        """_enqueue_pipelined with the label classifier two batches ahead.  The classifier's steps need nothing but the batches'
+        own feature rows and labels, so the chain classifier step -> scores -> train-pos keys -> sort of batch t + 2 runs a launch
+        earlier and every select reads keys sorted a launch before it (C_t: the classifier batch t is selected with):
+            [scores + sorted keys of C_0 at hand]
+            select(0) + classifier step 0 | scores + sorted keys of C_1 -> batch 1's buffers | classifier step 1
+            per step t:  gather(t) [|| Adam of t - 1 || scores + raw keys of C_t+2 -> batch t + 2's buffers]
+                         dense(t) || select(t + 1), keys sorted || classifier step t + 2 || riders: sort of batch t + 2's keys
+            the last step: gather, dense(t) alone
+        Batch n (= len(steps)) does not exist: its scores and sorted keys are what the sequence leaves for whatever follows, and
+        there the look-ahead ends - no classifier step beside dense(n - 3 ...)'s successors, no riders in the last two steps.
+        Buffers: batch t >= 1 uses (s0, keys) or (s0_alt, keys_alt) by the parity of n - t, so batch n's are the engine's own;
+        batch 0's are the engine's own too and are read by select(0) before anything is written.  The classifier slot of batch t
+        is t % 3.  Bit for bit what _enqueue_pipelined leaves."""
+        g, lib = self.g, self.lib
+        n = len(steps)
+        if not self._fresh:
+            self._enqueue_refresh()
+        R, F = g.R, g.feat_dim
+        b1, b2 = self.betas
+        st = self._stream()
+        cnt = lambda p, B: self.cnt2[p].view(-1)[:R * B]
+        own, alt = (self.s0, self.keys), (self.s0_alt, self.keys_alt)
+        buf = lambda t: own if (n - t) % 2 == 0 else alt
+        slot = lambda t: self.clf_slots[t % 3]
+        ids, lab, B, plan = steps[0]
+        _lib.check(lib.pcg_choose_train_part(1, *self._train_args(ids, lab, B, plan, cnt(0, B), 1), _p(slot(0)), st),
+                   "pcg_choose_train_part")
+        self._fresh = False
+        self._enqueue_refresh(into=buf(1))
+        ids1, lab1, B1, _ = steps[1]
+        _lib.check(lib.pcg_clf_step(g.desc_ref(), _p(ids1), _p(lab1), B1, _p(self.theta), _p(self.m), _p(self.v), self.E,
+                                    _p(self.clf_next), _p(slot(1)), _p(self.slabs), _p(self.step_counter), _p(self.sync),
+                                    self.lambda_1, 1.0 / (B1 * self.scale), self.lr, b1, b2, self.eps, self.wd, 2, st), "pcg_clf_step")
+        p = 0
+        for t, (ids, lab, B, plan) in enumerate(steps):
+            # (the gather launch's score pass writes batch t + 2's buffers with the classifier the launch before has stepped)
+            _lib.check(lib.pcg_choose_train_part(2, *self._train_args(ids, lab, B, plan, cnt(p, B), 0, bufs=buf(t + 2),
+                                                                      score_next=t + 2 <= n), None, st), "pcg_choose_train_part")
+            agg = self.agg.view(-1)[:R * B * F].view(R, B, F)
+            if t + 1 == n:
+                self._enqueue_tail(ids, lab, B, agg, plan, True, cnt=cnt(p, B))       # (_fresh is off: no key sort rides here)
+                break
+            nids, nlab, nB, nplan = steps[t + 1]
+            s0n, keysn = buf(t + 1)
+            cids, clab, cB = steps[t + 2][:3] if t + 2 < n else (None, None, 0)
+            _lib.check(lib.pcg_dense_select_ahead(
+                g.desc_ref(), _p(self.theta), _p(self.m), _p(self.v), self.E, _p(ids), _p(lab), B, _p(agg), agg.stride(1),
+                _p(cnt(p, B)), C.c_void_p(plan), 1.0 / (B * self.scale), _p(slot(t)), _p(self.logits), _p(self.center),
+                _p(self.row_loss), _p(self.acts), self.act_ld, _p(nids), _p(nlab), nB, _p(cnt(p ^ 1, nB)), C.c_void_p(nplan),
+                1.0 / (nB * self.scale), _p(slot(t + 2)) if cB else None, _p(s0n), _p(keysn) if g.n_pos else None, self._thr,
+                self._rhos, 0, _p(self.data), self.list_capacity, _p(self.status), _p(self.sync), _p(self.clf_next), _p(self.slabs),
+                _p(self.step_counter), self.lambda_1, self.lr, b1, b2, self.eps, self.wd, _p(cids), _p(clab), cB,
+                1.0 / (max(cB, 1) * self.scale), _p(buf(t + 2)[1]) if (g.n_pos and t + 2 <= n) else None, st),
+                "pcg_dense_select_ahead")
+            p ^= 1
+        self.last_counts = self.cnt2[p].view(-1)[:R * B].view(R, B)
+        self._fresh = True
 
     def _enqueue_pipelined(self, steps):
         """Consecutive training steps [(ids, labels, B, plan)] (deferred Adam, as train_step(defer=True) each), pipelined:
@@ -413,6 +502,8 @@ class FusedPCGNN:
                          dense(t) || select(t + 1)      one launch (pcg_dense_select_train); the last step: dense(t) alone
         Bit for bit what the three-launch steps leave.  The selection of t + 1 writes the other count buffer and the other
         classifier slot than the dense tiles of t read; it sorts its train-pos keys itself."""
+        if self._ahead(steps):
+            return self._enqueue_pipelined_ahead(steps)
         g, lib = self.g, self.lib
         if not self._fresh:
             self._enqueue_refresh()
@@ -548,6 +639,8 @@ class FusedPCGNN:
         stream, capture every fn into a hipGraph of its own, and put the optimizer state back.  A deferred Adam update
         of real steps is applied first (the saved state then includes it); the warm-up's own is flushed and undone."""
         self.flush()
+        # (the classifier slots, s0_alt / keys_alt and the second count buffer are scratch of ONE pipelined sequence: nothing of
+        #  them is read after it, so they are not part of the state; s0 / keys are marked stale below)
         state = (self.theta.clone(), self.m.clone(), self.v.clone(), self.step_counter.clone(), self.clf_next.clone())
         prof, self._prof = self._prof, None
         s = torch.cuda.Stream(self.dev)
