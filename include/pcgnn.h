@@ -52,7 +52,9 @@ enum {
     PCG_ST_SYNC_TIMEOUT = 4,  /* a bounded in-kernel wait (the select kernel's wait for its own train-pos sort) ran out */
     PCG_ST_SORT_OVERFLOW = 8, /* the one-launch bucket sort of the train positives met a bucket of more than 4096 keys (eight times
                                  the mean): its surplus keys were dropped - minority picks of that step may be wrong */
-    PCG_ST_EVAL_INPUT = 16    /* pcg_eval_counts met a label outside {0, 1} or a NaN probability: its counts describe no valid input */
+    PCG_ST_EVAL_INPUT = 16,   /* pcg_eval_counts met a label outside {0, 1} or a NaN probability: its counts describe no valid input */
+    PCG_ST_RANK_MISMATCH = 32 /* pcg_rank_lists / pcg_chosen_set: a row's kept count on the device is not the extent the caller's
+                                 out_begin gives it (or its list region / extent leaves its array); nothing was written for that row */
 };
 
 enum { PCG_NORM_COUNT = 0, PCG_NORM_SQRT_COUNT = 1 };
@@ -73,7 +75,7 @@ typedef struct pcg_graph_desc {
 
 /* library / build identification: "pcgnn_hip gfx950 <abi>" (host pointer, static) */
 const char *pcg_version(void);
-int pcg_abi_version(void);
+int pcg_abi_version(void);   /* 9 (added: pcg_rank_lists, pcg_chosen_set, pcg_chosen_workspace_bytes, PCG_ST_RANK_MISMATCH) */
 
 /* ---- label-aware scores -------------------------------------------------------
  * Replaces  batch_scores = self.label_clf(self.features(unique_nodes))
@@ -588,6 +590,35 @@ int64_t pcg_infer_new_workspace_bytes(const pcg_graph_desc *g, const pcg_graph_d
 int pcg_infer_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float *theta, int32_t emb, const int32_t *ids, int32_t n,
                   int32_t chunk_rows, float *s0, int32_t score_base, const double *thresholds, void *workspace,
                   int64_t list_capacity, float *out_logits, float *out_center, uint32_t *status, void *stream);
+/* The chosen neighbours of test-mode rows in the reference's order, with their distances (choose_step_test's samp_neighs /
+ * samp_scores, src/layers.py:713-736; FusedPCGNN.chosen, ops.choose_ranked).
+ * pcg_rank_lists: over the lists (and the plan) a pcg_choose_select* call in TEST mode (train_flag = 0, add_self = 0) left in
+ * `workspace` (the single-buffer layout of pcg_choose_workspace_bytes(g, B, list_capacity)) for the batch nodes [B].  Row (r, b)
+ * is written at out_begin[r * B + b] of out_ids / out_dist:
+ *   deg <= k + 1 (keep-all): the list's order (ascending position in the ascending-id row), out_dist[j] = |c - s0[id_j]|;
+ *   deg >  k + 1 (ranked)  : ascending distance, ties by list position (torch.sort(stable = True) of the reference's score_diff).
+ * c = center_s0 ? center_s0[b] : s0[nodes[b]] - as pcg_choose_select; the distance is one f32 subtract and abs: the bits of
+ * torch.abs(c - s), and of the key the select kernel ranked by.
+ * out_begin int64 [n_rel * B + 1], ascending from 0: the caller forms it on the host - a test-mode row keeps exactly
+ * pcg_sel_capacity_row(deg, threshold, 0, 0, n_pos, 0) entries - and sizes out_ids / out_dist [out_begin[n_rel * B]] with it.
+ * A row whose device count differs from out_begin[i + 1] - out_begin[i] (or whose extent leaves [0, out_begin[n_rel * B]]) sets
+ * PCG_ST_RANK_MISMATCH in *status and is not written; nothing is ever written outside a row's extent.  A list entry outside
+ * [0, n_nodes) is clamped for the score read and sets PCG_ST_LIST_ID_RANGE.  Two launches (rows of <= 64 kept entries: one wave
+ * each, the shortest four per wave; longer rows: a workgroup per 2048 entries, every one counting its slice against all of the
+ * row's keys); no workgroup waits for another.  Never synchronises, never allocates; B == 0: nothing is enqueued.
+ * pcg_chosen_set: ONE call for any id set ids [n] (any order, duplicates allowed): pcg_infer_set's score pass into s0 [n_nodes],
+ * then per chunk of chunk_rows ids plan (test mode) -> select (rows beyond the select kernel's LDS key capacity in its long-row
+ * launch, as in pcg_infer_set) -> rank; no gather, no dense launch.  Row (r, i) is written at out_begin[r * n + i]
+ * (out_begin int64 [n_rel * n + 1]).  theta, emb: the flat parameter buffer of pcg_dense_step - only its label classifier is
+ * read.  workspace: pcg_chosen_workspace_bytes(g, chunk_rows, list_capacity) bytes, no initial contents required; list_capacity
+ * as pcg_infer_set's (else PCG_ST_SEL_OVERFLOW and that chunk writes nothing).  n == 0: nothing is enqueued. */
+int pcg_rank_lists(const pcg_graph_desc *g, const int32_t *nodes, int32_t B, const float *s0, const float *center_s0,
+                   const void *workspace, int64_t list_capacity, const int64_t *out_begin, int32_t *out_ids, float *out_dist,
+                   uint32_t *status, void *stream);
+int64_t pcg_chosen_workspace_bytes(const pcg_graph_desc *g, int32_t chunk_rows, int64_t list_capacity);
+int pcg_chosen_set(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *ids, int32_t n, int32_t chunk_rows,
+                   float *s0, const double *thresholds, void *workspace, int64_t list_capacity, const int64_t *out_begin,
+                   int32_t *out_ids, float *out_dist, uint32_t *status, void *stream);
 int pcg_step_front_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, float *s0,
                          uint64_t *pos_keys, const int32_t *nodes, const int32_t *labels, int32_t B,
                          const double *thresholds, const double *rho, int32_t add_self, void *workspace,

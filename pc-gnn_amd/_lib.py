@@ -16,8 +16,9 @@ PCG_ST_LIST_ID_RANGE = 2
 PCG_ST_SYNC_TIMEOUT = 4
 PCG_ST_SORT_OVERFLOW = 8
 PCG_ST_EVAL_INPUT = 16
+PCG_ST_RANK_MISMATCH = 32
 PCG_NORM_COUNT, PCG_NORM_SQRT_COUNT = 0, 1
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class GraphDesc(C.Structure):
@@ -113,6 +114,9 @@ PROTOTYPES = {
                                        C.POINTER(_F64), _P, _I32, _I64, _P, _P, _P, _P]),
     "pcg_infer_new_workspace_bytes": (_I64, [_G, _G, _I32, _I32, _I64]),
     "pcg_infer_new": (C.c_int, [_G, _G, _P, _I32, _P, _I32, _I32, _P, _I32, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P]),
+    "pcg_rank_lists": (C.c_int, [_G, _P, _I32, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "pcg_chosen_workspace_bytes": (_I64, [_G, _I32, _I64]),
+    "pcg_chosen_set": (C.c_int, [_G, _P, _I32, _P, _I32, _I32, _P, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P, _P]),
     "pcg_eval_workspace_bytes": (_I64, [_I64, _I32]),
     "pcg_eval_counts": (C.c_int, [_P, _P, _I64, _P, _I32, _P, _P, _P, _P]),
     "pcg_step_front_train": (C.c_int, [_G, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, C.POINTER(_F64), C.POINTER(_F64), _I32, _P,

@@ -33,6 +33,8 @@ struct InferCarve {
 int infer_carve(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity, InferCarve &c);
 bool infer_wlds(int F, int E, int R);
 int launch_infer_dense(const DenseArgs &a, int B, hipStream_t st);
+// the front launch of a whole-set call: the table's scores with (W, bias) || the words of z zeroed
+int launch_infer_front(const pcg_graph_desc *g, const float *W, const float *bias, float *s0, const ZeroRegions &z, hipStream_t st);
 // the look-back words of a call's two plan slots (full chunks | the shorter last chunk) as the layouts of its chunk sizes place them
 void infer_zero_regions(ZeroRegions &z, const pcg_graph_desc *g, int32_t chunk_rows, int32_t tail, int64_t list_capacity,
                         unsigned char *slot0, unsigned char *slot1, unsigned char *data);

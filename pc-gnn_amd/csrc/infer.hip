@@ -30,6 +30,17 @@ __global__ void __launch_bounds__(256) infer_front_kernel(const float *__restric
     infer_zero_body(z, b - n_score_blocks);   // the zeroing workgroups
 }
 
+// the front launch of a whole-set call (pcg_infer_set, pcg_chosen_set): the table's scores with (W, bias) || the words of z zeroed
+int launch_infer_front(const pcg_graph_desc *g, const float *W, const float *bias, float *s0, const ZeroRegions &z, hipStream_t st) {
+    const int64_t zero_words = z.n[0] + z.n[1] + z.n[2] + z.n[3];
+    const int n_zero = (int)((zero_words + INFER_ZERO_WORDS - 1) / INFER_ZERO_WORDS);
+    const int n_score = (int)score_table_blocks(g->n_nodes, g->feat_stride);
+    hipLaunchKernelGGL(infer_front_kernel, dim3(n_score + n_zero), dim3(256), 0, st, g->X, g->feat_dim, g->feat_stride, W, bias,
+                       g->n_nodes, s0, n_score, z);
+    PCG_LAUNCH_CHECK();
+    return PCG_OK;
+}
+
 // PERSIST: tile blockIdx.x, then + gridDim.x, ...; else one tile per workgroup (the run-time shapes: a loop around their
 // run-time index arithmetic needs more than the 128 VGPRs a 1024-thread workgroup has - it spilled)
 template <bool WLDS, int F_, int E_, int R_, bool PERSIST>
@@ -217,12 +228,8 @@ int pcg_infer_set(const pcg_graph_desc *g, const float *theta, int32_t emb, cons
     // can pass for a published total (the tags the plan launches count from the zeroed sequence word start at 1)
     pcg::ZeroRegions z = {};
     pcg::infer_zero_regions(z, g, chunk_rows, tail, list_capacity, slot[0], slot[1], data);
-    const int64_t zero_words = z.n[0] + z.n[1] + z.n[2] + z.n[3];
-    const int n_zero = (int)((zero_words + pcg::INFER_ZERO_WORDS - 1) / pcg::INFER_ZERO_WORDS);
-    const int n_score = (int)pcg::score_table_blocks(g->n_nodes, g->feat_stride);
-    hipLaunchKernelGGL(pcg::infer_front_kernel, dim3(n_score + n_zero), dim3(256), 0, st, g->X, g->feat_dim, g->feat_stride,
-                       theta + pcg::off_clf(F, E, R), theta + pcg::off_bias(F, E, R), g->n_nodes, s0, n_score, z);
-    PCG_LAUNCH_CHECK();
+    rc = pcg::launch_infer_front(g, theta + pcg::off_clf(F, E, R), theta + pcg::off_bias(F, E, R), s0, z, st);
+    if (rc != PCG_OK) return rc;
 
     for (int ch = 0; ch < n_chunks; ++ch) {
         const int64_t off = (int64_t)ch * chunk_rows;

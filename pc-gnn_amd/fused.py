@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .graph import DeviceGraph, QueryBatch
+from .graph import ChosenLists, DeviceGraph, QueryBatch
 from .model import PCALayer
 
 _p = ops._p
@@ -1027,6 +1027,9 @@ class FusedPCGNN:
                         "workgroup's wait for its predecessors' totals")
         if st & _lib.PCG_ST_SORT_OVERFLOW:
             what.append("the one-launch sort of the train positives met a bucket of more than 4096 keys: minority picks may be wrong")
+        if st & _lib.PCG_ST_RANK_MISMATCH:
+            what.append("rank_lists: a row's kept count on the device is not the extent its output offsets give it - the row "
+                        "was not written")
         raise _lib.PcgnnLibraryError("; ".join(what) or f"device status {st}")
 
     def last_loss(self) -> torch.Tensor:
@@ -1125,6 +1128,61 @@ class FusedPCGNN:
                                      _p(inf["ws"]), cap, _p(logits), _p(center), _p(inf["status"]), self._stream()), "pcg_infer_set")
         self._infer_status()
         return (logits, center) if want_center else logits
+
+    def chosen(self, ids=None, chunk: Optional[int] = None) -> ChosenLists:
+        """WHY a node scores as it does: for every requested node and relation, the neighbours the test-mode selection kept - the
+        selection ``infer`` and a deployed model use - in the reference's order with their distances (choose_step_test's
+        samp_neighs / samp_scores, src/layers.py:713-736), on the device (pcg_chosen_set): ONE score pass, then per chunk of ids
+        plan -> select -> rank; no gather, no dense launch.  ids, chunk: as ``infer`` (None = every node; any order, duplicates
+        allowed; a device tensor, numpy array or list; range-checked on the host).  The output offsets are host arithmetic on
+        the degrees (a test-mode row keeps exactly deg > k + 1 ? k : deg entries), so the result is sized exactly.  Returns a
+        ``ChosenLists``.  The training engine is left alone exactly as by ``infer`` (a deferred update is applied first).
+        Synchronises once (the status word)."""
+        g, lib = self.g, self.lib
+        self.flush()
+        inf = self._inf
+        if ids is None:
+            n = g.n_nodes
+            ids_dev = inf.get("all_ids")
+            if ids_dev is None or ids_dev.numel() != n:
+                ids_dev = inf["all_ids"] = torch.arange(n, dtype=torch.int32, device=self.dev)
+            ids_host = np.arange(n, dtype=np.int64)
+        else:
+            ids_host = (ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)).reshape(-1).astype(np.int64)
+            n = int(ids_host.size)
+            if n and (ids_host.min() < 0 or ids_host.max() >= g.n_nodes):
+                raise ValueError(f"chosen: ids outside 0 .. {g.n_nodes - 1}")
+            ids_dev = ops._i32(ids, self.dev).view(-1) if torch.is_tensor(ids) else \
+                torch.from_numpy(ids_host.astype(np.int32)).to(self.dev)
+        caps2 = ops.sel_capacity(g, ids_host, None, self.thresholds, 0.0, False)      # [R, n]: exact in test mode
+        off = ops.rank_offsets(caps2)
+        total = int(off[-1])
+        out_begin = torch.from_numpy(off).to(self.dev)
+        out_ids = torch.empty(total, dtype=torch.int32, device=self.dev)
+        out_dist = torch.empty(total, dtype=torch.float32, device=self.dev)
+        res = ChosenLists(out_begin, out_ids, out_dist, g.R, n, host_offsets=off)
+        if n == 0:
+            return res
+        caps = caps2.sum(0)                                                          # == infer_row_caps
+        ws_bytes = lambda c, cap: int(lib.pcg_chosen_workspace_bytes(g.desc_ref(), c, cap))
+        chunk = default_infer_chunk(caps, ws_bytes, self.infer_workspace_bytes) if chunk is None else int(chunk)
+        chunk = max(1, min(chunk, n))
+        _, cap = infer_chunks(caps, chunk)
+        nbytes = ws_bytes(chunk, cap)
+        if nbytes < 0:
+            raise _lib.PcgnnLibraryError(f"pcg_chosen_workspace_bytes rejected chunk {chunk} / list capacity {cap} ({nbytes})")
+        if inf.get("chosen_ws") is None or inf["chosen_ws"].numel() < nbytes:
+            inf["chosen_ws"] = None
+            inf["chosen_ws"] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        if inf.get("s0") is None:
+            inf["s0"] = torch.empty(g.n_nodes, dtype=torch.float32, device=self.dev)
+        if inf.get("status") is None:
+            inf["status"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        _lib.check(lib.pcg_chosen_set(g.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk, _p(inf["s0"]), self._thr,
+                                      _p(inf["chosen_ws"]), cap, _p(out_begin), _p(out_ids), _p(out_dist), _p(inf["status"]),
+                                      self._stream()), "pcg_chosen_set")
+        self._infer_status()
+        return res
 
     def _infer_status(self):
         """the status word of an infer / infer_new call: one read (synchronises); a set bit is cleared and raised"""

@@ -188,6 +188,59 @@ class DeviceGraph:
                 + self.train_pos.numel() * 4)
 
 
+class ChosenLists:
+    """The neighbours a test-mode selection kept, in the reference's order, with their distances - device tensors
+    (``FusedPCGNN.chosen``, ``ops.choose_ranked``; the kernel: pcg_rank_lists).  Row (r, i) - relation r, the i-th requested
+    node - is ``ids[offsets[r, i]:offsets[r, i + 1]]`` / ``dist[...]``: ascending distance, ties by position in the ascending-id
+    neighbour row, where the reference ranks (deg > k + 1); the ascending-id row itself where it keeps every neighbour
+    (choose_step_test, src/layers.py:713-736).  ``dist`` is ``torch.abs(centre score - neighbour score)`` bit for bit.
+
+    offsets int64 [R, n + 1] (a view of the flat [R * n + 1] array: offsets[r, n] == offsets[r + 1, 0]) | ids int32 [total] |
+    dist float32 [total]."""
+
+    def __init__(self, flat_offsets: torch.Tensor, ids: torch.Tensor, dist: torch.Tensor, R: int, n: int,
+                 host_offsets: Optional[np.ndarray] = None):
+        self.R, self.n = int(R), int(n)
+        self.flat_offsets = flat_offsets
+        self.offsets = flat_offsets.as_strided((self.R, self.n + 1), (self.n, 1))
+        self.ids, self.dist = ids, dist
+        self._host = host_offsets
+
+    def __iter__(self):
+        return iter((self.offsets, self.ids, self.dist))
+
+    def host_offsets(self) -> np.ndarray:
+        """The flat offsets [R * n + 1] on the host (formed there: no copy unless the object was built from device data)."""
+        if self._host is None:
+            self._host = self.flat_offsets.cpu().numpy()
+        return self._host
+
+    def row(self, r: int, i: int):
+        """(ids, dist) of relation r, requested node i: views."""
+        h = self.host_offsets()
+        lo, hi = int(h[r * self.n + i]), int(h[r * self.n + i + 1])
+        return self.ids[lo:hi], self.dist[lo:hi]
+
+    def mean_dist(self) -> torch.Tensor:
+        """The average neighbour distance of every row, [R, n] (the paper's per-relation diagnostic); NaN for an empty row."""
+        rows = self.R * self.n
+        cnt = (self.flat_offsets[1:] - self.flat_offsets[:-1])
+        seg = torch.repeat_interleave(torch.arange(rows, device=self.dist.device), cnt)
+        tot = torch.zeros(rows, dtype=torch.float64, device=self.dist.device).index_add_(0, seg, self.dist.double())
+        return (tot / cnt.double()).float().view(self.R, self.n)
+
+    def to_reference(self, r: int):
+        """Relation r in the reference's return shape: (samp_neighs list[set[int]], samp_scores list[list[float]])."""
+        h = self.host_offsets()
+        lo, hi = int(h[r * self.n]), int(h[(r + 1) * self.n])
+        ids = self.ids[lo:hi].cpu().numpy()
+        dist = self.dist[lo:hi].cpu().numpy()
+        cut = (h[r * self.n:(r + 1) * self.n + 1] - lo).tolist()
+        sets = [set(ids[a:b].tolist()) for a, b in zip(cut[:-1], cut[1:])]
+        scores = [dist[a:b].tolist() for a, b in zip(cut[:-1], cut[1:])]
+        return sets, scores
+
+
 class BaseShape:
     """What a ``QueryBatch`` is validated against: the base graph's node count, feature width and relation count.  A
     ``DeviceGraph`` has the same three attributes; this stands in for one where there is no GPU (host-side checks, tests)."""

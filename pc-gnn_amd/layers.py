@@ -69,33 +69,90 @@ class IntraAgg(nn.Module):
         kernel.  ``sample_list[b]`` must equal ``ceil(len(to_neighs_list[b]) * threshold)``
         for one threshold, as in the reference (layers.py:260-262)."""
         dev = self.weight.device
-        B = len(nodes)
-        lens = np.array([len(l) for l in to_neighs_list], dtype=np.int64)
-        thr = _infer_threshold(lens, np.asarray(sample_list, dtype=np.int64))
         n_nodes = int(self.features.weight.shape[0])
-        indptr = np.zeros(n_nodes + 1, dtype=np.int64)
-        indptr[1:B + 1] = np.cumsum(lens)
-        indptr[B + 1:] = indptr[B]
-        flat, s_flat = [], []
-        for l, sc in zip(to_neighs_list, neigh_scores):
-            ids = np.asarray(list(l), dtype=np.int64)
-            order = np.argsort(ids, kind="stable")
-            flat.append(ids[order])
-            s_flat.append(sc.detach().reshape(-1, 2)[:, 0].cpu().numpy()[order])
-        flat = np.concatenate(flat).astype(np.int32) if flat else np.zeros(0, np.int32)
-        s_flat = np.concatenate(s_flat).astype(np.float32) if s_flat else np.zeros(0, np.float32)
-        g = DeviceGraph(self.features.weight.detach(), [(indptr, flat)], self.train_pos, dev)
-        s0 = torch.zeros(n_nodes, dtype=torch.float32, device=dev)
-        s0[torch.from_numpy(flat.astype(np.int64)).to(dev)] = torch.from_numpy(s_flat).to(dev)
+        g, s0, thr, orders = _pack_explicit_lists(self.features.weight.detach(), n_nodes, to_neighs_list, neigh_scores, sample_list,
+                                                  self.train_pos, dev)
+        B = len(nodes)
         if len(self.train_pos):
             s0[torch.as_tensor(list(self.train_pos), device=dev)] = pos_scores.detach()[:, 0].to(dev)
         rows = torch.arange(B, dtype=torch.int32, device=dev)
         labels = ops._i32(batch_labels, dev) if train_flag else None
         keys = ops.pos_sort(g, s0) if (train_flag and g.n_pos) else None
         center = batch_scores.detach()[:, 0].contiguous().to(dev)
-        agg, _ = ops.choose_aggregate(g, rows, labels, s0, keys, [thr], [self.rho], train_flag, center_s0=center)
+        ws = ops.ChooseWorkspace(g, B)
+        agg, _ = ops.choose_aggregate(g, rows, labels, s0, keys, [thr], [self.rho], train_flag, center_s0=center, ws=ws)
+        # samp_scores (layers.py:591, 630): test mode only - the lists the call above left in ws, ranked (train mode: None, DESIGN)
+        samp_scores = None if train_flag else _ranked_scores(g, rows, s0, [thr], center, orders, ws=ws)[1]
         self_feats = self.features.weight.detach().to(dev)[torch.as_tensor(np.asarray(nodes), device=dev).long()]
-        return self.transform(self_feats, agg[0]), None
+        return self.transform(self_feats, agg[0]), samp_scores
+
+
+def _pack_explicit_lists(features, n_nodes, neighs_list, neigh_scores, sample_list, train_pos, dev):
+    """The reference's explicit per-centre arguments (neighbour id lists, their score rows, sample counts) as what the kernels
+    read: a one-relation CSR over the batch rows (row b = centre b's list, ascending id) and a score table holding every
+    listed id's class-0 score.  Returns (graph, s0, threshold, orders) - orders[b]: the permutation that sorted list b."""
+    B = len(neighs_list)
+    lens = np.array([len(l) for l in neighs_list], dtype=np.int64)
+    thr = _infer_threshold(lens, np.asarray(sample_list, dtype=np.int64))
+    indptr = np.zeros(n_nodes + 1, dtype=np.int64)
+    indptr[1:B + 1] = np.cumsum(lens)
+    indptr[B + 1:] = indptr[B]
+    flat, s_flat, orders = [], [], []
+    for l, sc in zip(neighs_list, neigh_scores):
+        ids = np.asarray(list(l), dtype=np.int64)
+        order = np.argsort(ids, kind="stable")
+        orders.append(order)
+        flat.append(ids[order])
+        s_flat.append(sc.detach().reshape(-1, 2)[:, 0].cpu().numpy()[order])
+    flat = np.concatenate(flat).astype(np.int32) if flat else np.zeros(0, np.int32)
+    s_flat = np.concatenate(s_flat).astype(np.float32) if s_flat else np.zeros(0, np.float32)
+    g = DeviceGraph(features, [(indptr, flat)], train_pos, dev)
+    s0 = torch.zeros(n_nodes, dtype=torch.float32, device=dev)
+    s0[torch.from_numpy(flat.astype(np.int64)).to(dev)] = torch.from_numpy(s_flat).to(dev)
+    return g, s0, thr, orders
+
+
+def _ranked_scores(g, rows, s0, thresholds, center, orders, ws=None):
+    """(samp_neighs, samp_scores) of relation 0 in the reference's return shape.  ws: a workspace that already holds the rows'
+    test-mode lists (else they are selected here).  A keep-all row comes back in the CALLER's list order, as the reference
+    returns it (the kernels see the list sorted by id: orders[b] undoes it); a ranked row by ascending distance."""
+    if ws is None:
+        ch = ops.choose_ranked(g, rows, s0, thresholds, center_s0=center)
+    else:
+        B = rows.numel()
+        caps = ops.sel_capacity(g, np.arange(B, dtype=np.int64), None, thresholds, 0.0, False)
+        off = ops.rank_offsets(caps)
+        ids = torch.empty(int(off[-1]), dtype=torch.int32, device=g.device)
+        dist = torch.empty(int(off[-1]), dtype=torch.float32, device=g.device)
+        out_begin = torch.from_numpy(off).to(g.device)
+        ops.rank_lists(g, rows, s0, ws, out_begin, ids, dist, center_s0=center)
+        ops.check_status(ws.status)
+        ch = ops.ChosenLists(out_begin, ids, dist, g.R, B, host_offsets=off)
+    sets, scores = ch.to_reference(0)
+    for b, order in enumerate(orders):
+        if len(scores[b]) == len(order):            # keep-all: entry t of the sorted list is entry order[t] of the caller's
+            back = [0.0] * len(order)
+            for t, o in enumerate(order.tolist()):
+                back[o] = scores[b][t]
+            scores[b] = back
+    return sets, scores
+
+
+def choose_step_test(center_scores, neigh_scores, neighs_list, sample_list):
+    """The reference's test-mode choose step under its own name, signature and return shape (src/layers.py:700-738) on the HIP
+    path: ``(samp_neighs list[set], samp_scores list[list[float]])`` - per centre the kept neighbours and their score distances,
+    ascending where the reference ranks (more than num_sample + 1 neighbours), in the list's own order where it keeps them all.
+    ``sample_list[b]`` must be ``ceil(len(neighs_list[b]) * threshold)`` for one threshold, as the reference forms it
+    (layers.py:260-262); a neighbour id that appears in several lists carries the same score in each (the reference slices
+    every list's scores out of one table, :246-253)."""
+    dev = center_scores.device if center_scores.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    B = len(neighs_list)
+    top = max([int(max(l)) for l in neighs_list if len(l)], default=0)
+    n_nodes = max(top + 1, B, 1)
+    g, s0, thr, orders = _pack_explicit_lists(torch.zeros(n_nodes, 4), n_nodes, neighs_list, neigh_scores, sample_list, [], dev)
+    rows = torch.arange(B, dtype=torch.int32, device=dev)
+    center = center_scores.detach().reshape(-1, 2)[:, 0].contiguous().to(dev)
+    return _ranked_scores(g, rows, s0, [thr], center, orders)
 
 
 def _infer_threshold(lens: np.ndarray, samples: np.ndarray) -> float:

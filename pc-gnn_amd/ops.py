@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .graph import DeviceGraph
+from .graph import ChosenLists, DeviceGraph
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -232,6 +232,55 @@ def chosen_sets(g: DeviceGraph, nodes, labels, s0, pos_keys, thresholds, rho, tr
                                 center_s0, ws)
     sets = read_sets(g, B, ws)
     return sets, agg, cnt
+
+
+def check_status(status: torch.Tensor):
+    """Read a device status word (synchronises); a set bit is cleared and raised, every bit by name."""
+    st = int(status.item())
+    if st:
+        status.zero_()
+        from .fused import FusedPCGNN
+        FusedPCGNN._raise_status(st)
+
+
+def rank_offsets(caps: np.ndarray) -> np.ndarray:
+    """The flat output offsets [R * n + 1] of the per-row kept counts caps [R, n] (sel_capacity in test mode: exact)."""
+    off = np.zeros(caps.size + 1, dtype=np.int64)
+    np.cumsum(np.asarray(caps, dtype=np.int64).reshape(-1), out=off[1:])
+    return off
+
+
+def rank_lists(g: DeviceGraph, nodes: torch.Tensor, s0: torch.Tensor, ws: ChooseWorkspace, out_begin: torch.Tensor,
+               out_ids: torch.Tensor, out_dist: torch.Tensor, center_s0: Optional[torch.Tensor] = None):
+    """The lists a TEST-mode choose_select / choose_aggregate call left in ``ws``, in the reference's order with their
+    distances (pcg_rank_lists): row (r, b) at out_begin[r * B + b] of out_ids / out_dist.  out_begin: int64 device tensor
+    [R * B + 1] (rank_offsets of the rows' exact kept counts).  A row whose device count differs from its extent sets
+    PCG_ST_RANK_MISMATCH in ws.status and is not written.  Nothing synchronises."""
+    lib = _lib.load()
+    _lib.check(lib.pcg_rank_lists(g.desc_ref(), _p(nodes), nodes.numel(), _p(s0), _p(center_s0), _p(ws.buf), ws.list_capacity,
+                                  _p(out_begin), _p(out_ids), _p(out_dist), _p(ws.status), _stream(g.device)), "pcg_rank_lists")
+
+
+def choose_ranked(g: DeviceGraph, nodes, s0: torch.Tensor, thresholds: Sequence[float],
+                  center_s0: Optional[torch.Tensor] = None) -> ChosenLists:
+    """choose_step_test for all relations of a batch, on the device: select (test mode) followed by rank.  Returns a
+    ``ChosenLists`` (offsets [R, B + 1], ids, dist - unpacks as ``offsets, ids, dist = choose_ranked(...)``).  The offsets are
+    host arithmetic on the degrees; one read of the status word at the end (synchronises)."""
+    nodes = _i32(nodes, g.device).view(-1)
+    B = nodes.numel()
+    caps = sel_capacity(g, nodes.cpu().numpy().astype(np.int64), None, thresholds, 0.0, False)
+    off = rank_offsets(caps)
+    total = int(off[-1])
+    out_begin = torch.from_numpy(off).to(g.device)
+    ids = torch.empty(total, dtype=torch.int32, device=g.device)
+    dist = torch.empty(total, dtype=torch.float32, device=g.device)
+    if B:
+        ws = ChooseWorkspace(g, B, list_capacity=max(total, 1))
+        cnt = torch.empty(g.R * B, dtype=torch.int32, device=g.device)
+        choose_select(g, nodes, None, s0, None, thresholds, 0.0, False, ws, cnt, center_s0=center_s0)
+        rank_lists(g, nodes, s0, ws, out_begin, ids, dist, center_s0=center_s0)
+        check_status(ws.status)
+    return ChosenLists(out_begin, ids, dist, g.R, B, host_offsets=off)
 
 
 def segment_mean(g: DeviceGraph, begin: torch.Tensor, count: torch.Tensor, idx: torch.Tensor,

@@ -154,6 +154,13 @@ def predict_proba_new(query, model, ids=None, chunk=None) -> np.ndarray:
         return np.ascontiguousarray(torch.sigmoid(model.infer_new(query, ids=ids, chunk=chunk)).float().cpu().numpy()[:, 1])
 
 
+def explain_nodes(engine, ids):
+    """A flagged node's score and its reason in one call: (``engine.chosen(ids)`` - the neighbours the model listened to, ranked,
+    with their distances - , the test-mode class probabilities [n, 2] ``predict_proba`` reports for the same ids), on the device."""
+    with torch.no_grad():
+        return engine.chosen(ids), torch.sigmoid(engine.infer(ids)).float()
+
+
 def predict_proba(test_nodes, model, batch_size: int, labels=None) -> np.ndarray:
     """Test-mode class probabilities [n, 2] of ``test_nodes`` (sigmoid of the gnn logits, utils.py:305), on the host.
     A FusedPCGNN runs its whole-set pass (``infer``: one call, one score pass) - test-mode results do not depend on how the
