@@ -1,5 +1,5 @@
-// Shared between the whole-set inference entry points (infer.hip) and the query-batch path (infer_new.hip): the zeroing
-// workgroups of a front kernel, the call's workspace layout and the forward-only dense launch.
+// Shared between the whole-set entry points (infer.hip, infer_new.hip, rank.hip): the zeroing workgroups of a front kernel, the
+// call's workspace layout, the per-chunk plan -> select -> stage loop and the forward-only dense launch.
 #pragma once
 #include "dense.h"
 
@@ -24,19 +24,86 @@ __device__ __forceinline__ void infer_zero_body(const ZeroRegions &z, int b) {
     }
 }
 
-// the call's workspace: [plan slot of full chunks | plan slot of the last, shorter chunk | data part | agg [R][chunk][F] |
-// cnt [R][chunk] | centre logits [chunk][2] (when the caller wants none)]
+// a call's workspace: [plan slot of full chunks | plan slot of the last, shorter chunk (n_slots == 2: the single-GPU calls; the
+// partitioned chunk has one slot) | data part | dense parts: agg [R][chunk][F] | cnt [R][chunk] | dense parts: centre logits
+// [chunk][2] (for a caller who wants none)].  A chunk of fewer rows carves its own layout inside the same bytes (every part grows
+// with the rows).  Without the dense parts (pcg_chosen_set) agg and center are -1 and emb is not looked at.
 struct InferCarve {
     int64_t plan_bytes, data, agg, cnt, center, total;
 };
 // infer.hip
-int infer_carve(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity, InferCarve &c);
+int infer_carve(const pcg_graph_desc *g, int n_slots, bool dense, int32_t emb, int32_t chunk_rows, int64_t list_capacity, InferCarve &c);
 bool infer_wlds(int F, int E, int R);
 int launch_infer_dense(const DenseArgs &a, int B, hipStream_t st);
+// the forward-only dense launch of a chunk whose lists were gathered into agg ([R][B][F]; rows of several chunks: partial sums in
+// w): centres `nodes` are rows of g's table -> out_logits, out_center [B][2]
+int infer_dense(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *nodes, int32_t B, const Workspace &w,
+                float *agg, const int32_t *cnt, float *out_logits, float *out_center, hipStream_t st);
+// the zeroing workgroups a front kernel needs for z
+inline int infer_zero_blocks(const ZeroRegions &z) {
+    return (int)((z.n[0] + z.n[1] + z.n[2] + z.n[3] + INFER_ZERO_WORDS - 1) / INFER_ZERO_WORDS);
+}
 // the front launch of a whole-set call: the table's scores with (W, bias) || the words of z zeroed
 int launch_infer_front(const pcg_graph_desc *g, const float *W, const float *bias, float *s0, const ZeroRegions &z, hipStream_t st);
-// the look-back words of a call's two plan slots (full chunks | the shorter last chunk) as the layouts of its chunk sizes place them
-void infer_zero_regions(ZeroRegions &z, const pcg_graph_desc *g, int32_t chunk_rows, int32_t tail, int64_t list_capacity,
-                        unsigned char *slot0, unsigned char *slot1, unsigned char *data);
+// the feature tables every whole-set call reads: rows of 16-byte groups that one score workgroup's lanes cover
+inline bool infer_table_ok(const pcg_graph_desc *g) {
+    return g->feat_dim >= 1 && g->feat_stride >= g->feat_dim && g->feat_stride % 4 == 0 && g->feat_stride <= 512;
+}
+
+// The chunks of a whole-set call: ids [ch * chunk_rows, + chunk_rows) of n, the last one `tail` rows.  Full chunks plan into slot
+// 0, a shorter last chunk into slot 1 (a tail equal to the chunk is a full chunk); the data part, cnt and the status word are
+// shared.  The front launch of the call zeroes what infer_zero_regions names: the look-back words (counters, queue heads,
+// per-workgroup totals) of every slot as the layouts of the call's chunk sizes place them.  A slot's earlier plans may have laid
+// other arrays over those words: zeroed, none of them can pass for a published total (the tags the plan launches count from the
+// zeroed sequence word start at 1).
+struct ChunkDriver {
+    const pcg_graph_desc *g;      // the graph whose rows are planned and selected
+    const int32_t *ids;
+    int32_t n, chunk_rows;
+    int64_t list_capacity;
+    const double *thresholds;
+    const float *s0;
+    int64_t center_off;           // centre b's score is s0[ids[b] + center_off]
+    int n_slots;
+    unsigned char *slot[2];
+    int64_t plan_bytes;
+    unsigned char *data;
+    int32_t *cnt;
+    uint32_t *status;
+    hipStream_t st;
+
+    int n_chunks() const { return (int)(((int64_t)n + chunk_rows - 1) / chunk_rows); }
+    int32_t tail() const { return n - (n_chunks() - 1) * chunk_rows; }
+    // per chunk: plan (test mode) -> select -> stage(off, B, cid, w): the chunk is ids [off, off + B) = cid[0, B), its lists and
+    // plan are in w
+    template <class Stage>
+    int run(Stage &&stage) const {
+        const int nc = n_chunks();
+        const int32_t last = tail();
+        for (int ch = 0; ch < nc; ++ch) {
+            const int64_t off = (int64_t)ch * chunk_rows;
+            const int32_t B = ch + 1 < nc ? chunk_rows : last;
+            unsigned char *plan = slot[B == chunk_rows ? 0 : 1];
+            const int32_t *cid = ids + off;
+            int rc = pcg_plan_epochs(g, cid, nullptr, B, 1, B, thresholds, nullptr, 0, 0, plan, plan_bytes, list_capacity, status,
+                                     nullptr, st);
+            if (rc != PCG_OK) return rc;
+            rc = pcg_choose_select_planned(g, cid, nullptr, B, s0, nullptr, nullptr, thresholds, nullptr, 0, 0, cnt, data, plan,
+                                           list_capacity, status, nullptr, center_off, st);
+            if (rc != PCG_OK) return rc;
+            Workspace w;
+            carve1(g, B, list_capacity, data, &w, plan);
+            rc = stage(off, B, cid, w);
+            if (rc != PCG_OK) return rc;
+        }
+        return PCG_OK;
+    }
+};
+// the look-back words of d's n_slots plan slots (see ChunkDriver)
+void infer_zero_regions(ZeroRegions &z, const ChunkDriver &d);
+// the driver of a call whose workspace was carved as c (n_slots as given to infer_carve)
+ChunkDriver infer_driver(const pcg_graph_desc *g, const int32_t *ids, int32_t n, int32_t chunk_rows, int64_t list_capacity,
+                         const double *thresholds, const float *s0, int64_t center_off, int n_slots, void *workspace,
+                         const InferCarve &c, uint32_t *status, void *stream);
 
 }  // namespace pcg

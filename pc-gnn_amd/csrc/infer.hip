@@ -3,7 +3,7 @@
 //
 //   infer_front_kernel : the score pass of the label classifier over the whole table (score_table_body: the same workgroups,
 //                        rows and fma order as pcg_score_table) || the look-back words of the call's two plan slots zeroed
-//   per chunk          : plan (test mode) -> select -> gather (pcg_plan_epochs, pcg_choose_gather_planned) -> infer_dense_kernel
+//   per chunk          : plan (test mode) -> select (ChunkDriver::run, infer.h) -> gather (pcg_gather_lists_planned) -> infer_dense_kernel
 //   infer_dense_kernel : a persistent grid of dense workgroups (16 waves, 16-row tiles): each stages W_inter | W_intra[r] into
 //                        LDS once (when they fit: the emb-128 shapes stream them from L2 as the training kernel does) and then
 //                        runs the forward phases of dense_tile_body on tiles blockIdx.x, + gridDim.x, ... - static striding,
@@ -32,8 +32,7 @@ __global__ void __launch_bounds__(256) infer_front_kernel(const float *__restric
 
 // the front launch of a whole-set call (pcg_infer_set, pcg_chosen_set): the table's scores with (W, bias) || the words of z zeroed
 int launch_infer_front(const pcg_graph_desc *g, const float *W, const float *bias, float *s0, const ZeroRegions &z, hipStream_t st) {
-    const int64_t zero_words = z.n[0] + z.n[1] + z.n[2] + z.n[3];
-    const int n_zero = (int)((zero_words + INFER_ZERO_WORDS - 1) / INFER_ZERO_WORDS);
+    const int n_zero = infer_zero_blocks(z);
     const int n_score = (int)score_table_blocks(g->n_nodes, g->feat_stride);
     hipLaunchKernelGGL(infer_front_kernel, dim3(n_score + n_zero), dim3(256), 0, st, g->X, g->feat_dim, g->feat_stride, W, bias,
                        g->n_nodes, s0, n_score, z);
@@ -116,33 +115,77 @@ int launch_infer_dense(const DenseArgs &a, int B, hipStream_t st) {
 }
 
 // the call's workspace (InferCarve, infer.h)
-int infer_carve(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity, InferCarve &c) {
+int infer_carve(const pcg_graph_desc *g, int n_slots, bool dense, int32_t emb, int32_t chunk_rows, int64_t list_capacity, InferCarve &c) {
     if (!g || chunk_rows < 1 || list_capacity < 1 || list_capacity >= (1ll << 31)) return PCG_E_ARG;
-    if (emb < 16 || emb % 16 != 0 || g->n_rel < 1 || g->n_rel > PCG_MAX_REL || g->feat_dim < 1) return PCG_E_UNSUPPORTED;
+    if ((dense && (emb < 16 || emb % 16 != 0)) || g->n_rel < 1 || g->n_rel > PCG_MAX_REL || g->feat_dim < 1) return PCG_E_UNSUPPORTED;
     if ((int64_t)g->n_rel * chunk_rows >= (1ll << 31)) return PCG_E_ARG;
     const CarveSizes sz = carve(g, chunk_rows, list_capacity, nullptr, nullptr, nullptr);
     const int64_t R = g->n_rel, B = chunk_rows, F = g->feat_dim;
     c.plan_bytes = sz.plan_bytes;
-    c.data = 2 * sz.plan_bytes;
-    c.agg = c.data + align256(sz.data_bytes);
-    c.cnt = c.agg + align256(4 * R * B * F);
-    c.center = c.cnt + align256(4 * R * B);
-    c.total = c.center + align256(8 * B);
+    c.data = n_slots * sz.plan_bytes;
+    int64_t off = c.data + align256(sz.data_bytes);
+    auto take = [&](bool present, int64_t bytes) {
+        const int64_t o = off;
+        if (present) off += align256(bytes);
+        return present ? o : -1;
+    };
+    c.agg = take(dense, 4 * R * B * F);
+    c.cnt = take(true, 4 * R * B);
+    c.center = take(dense, 8 * B);
+    c.total = off;
     return PCG_OK;
 }
 
-void infer_zero_regions(ZeroRegions &z, const pcg_graph_desc *g, int32_t chunk_rows, int32_t tail, int64_t list_capacity,
-                        unsigned char *slot0, unsigned char *slot1, unsigned char *data) {
-    const int32_t slot_B[2] = {chunk_rows, tail};
-    unsigned char *slot[2] = {slot0, slot1};
-    for (int s = 0; s < 2; ++s) {
+void infer_zero_regions(ZeroRegions &z, const ChunkDriver &d) {
+    const int32_t slot_B[2] = {d.chunk_rows, d.tail()};
+    for (int s = 0; s < d.n_slots; ++s) {
         Workspace w;
-        carve1(g, slot_B[s], list_capacity, data, &w, slot[s]);
+        carve1(d.g, slot_B[s], d.list_capacity, d.data, &w, d.slot[s]);
         z.p[2 * s] = w.counters;                                  // counters | heads: contiguous (256 + 512 bytes)
         z.n[2 * s] = (reinterpret_cast<unsigned char *>(w.heads) - reinterpret_cast<unsigned char *>(w.counters) + 4 * 8 * 16) / 4;
         z.p[2 * s + 1] = reinterpret_cast<uint32_t *>(w.plan_totals);
-        z.n[2 * s + 1] = 64 * ((int64_t)g->n_rel * slot_B[s] / 256 + 2) / 4;
+        z.n[2 * s + 1] = 64 * ((int64_t)d.g->n_rel * slot_B[s] / 256 + 2) / 4;
     }
+}
+
+ChunkDriver infer_driver(const pcg_graph_desc *g, const int32_t *ids, int32_t n, int32_t chunk_rows, int64_t list_capacity,
+                         const double *thresholds, const float *s0, int64_t center_off, int n_slots, void *workspace,
+                         const InferCarve &c, uint32_t *status, void *stream) {
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    ChunkDriver d;
+    d.g = g;
+    d.ids = ids;
+    d.n = n;
+    d.chunk_rows = chunk_rows;
+    d.list_capacity = list_capacity;
+    d.thresholds = thresholds;
+    d.s0 = s0;
+    d.center_off = center_off;
+    d.n_slots = n_slots;
+    d.slot[0] = ws;
+    d.slot[1] = n_slots > 1 ? ws + c.plan_bytes : nullptr;
+    d.plan_bytes = c.plan_bytes;
+    d.data = ws + c.data;
+    d.cnt = reinterpret_cast<int32_t *>(ws + c.cnt);
+    d.status = status;
+    d.st = static_cast<hipStream_t>(stream);
+    return d;
+}
+
+int infer_dense(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *nodes, int32_t B, const Workspace &w,
+                float *agg, const int32_t *cnt, float *out_logits, float *out_center, hipStream_t st) {
+    DenseExtra x;
+    x.chunk_begin = w.chunk_begin;
+    x.partial = w.partial;
+    x.cnt = cnt;
+    x.partial_stride = g->feat_stride;
+    DenseArgs a;
+    int n_sort_blocks = 0;
+    const int rc = dense_args(a, n_sort_blocks, g, theta, emb, nodes, nullptr, B, agg, g->feat_dim, 0.f, 1.f, out_logits, out_center,
+                              nullptr, nullptr, nullptr, nullptr, x);
+    if (rc != PCG_OK) return rc;
+    a.stamps = nullptr;
+    return launch_infer_dense(a, B, st);
 }
 
 // ---- partitioned inference (pcg_infer_chunk_dist, pc-gnn_amd/dist.py) ------------------------------------------------------
@@ -173,30 +216,13 @@ __global__ void __launch_bounds__(256) infer_front_dist_kernel(const float *__re
     infer_zero_body(z, b - n_halo);
 }
 
-// the call's workspace: [plan slot (chunk_rows) | data part | agg [R][chunk][F] | cnt [R][chunk] | centre logits [chunk][2]];
-// a chunk of fewer rows carves its own layout inside the same bytes (every part grows with the rows)
-static int infer_dist_carve(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity, InferCarve &c) {
-    if (!g || chunk_rows < 1 || list_capacity < 1 || list_capacity >= (1ll << 31)) return PCG_E_ARG;
-    if (emb < 16 || emb % 16 != 0 || g->n_rel < 1 || g->n_rel > PCG_MAX_REL || g->feat_dim < 1) return PCG_E_UNSUPPORTED;
-    if ((int64_t)g->n_rel * chunk_rows >= (1ll << 31)) return PCG_E_ARG;
-    const CarveSizes sz = carve(g, chunk_rows, list_capacity, nullptr, nullptr, nullptr);
-    const int64_t R = g->n_rel, B = chunk_rows, F = g->feat_dim;
-    c.plan_bytes = sz.plan_bytes;
-    c.data = sz.plan_bytes;
-    c.agg = c.data + align256(sz.data_bytes);
-    c.cnt = c.agg + align256(4 * R * B * F);
-    c.center = c.cnt + align256(4 * R * B);
-    c.total = c.center + align256(8 * B);
-    return PCG_OK;
-}
-
 }  // namespace pcg
 
 extern "C" {
 
 int64_t pcg_infer_workspace_bytes(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity) {
     pcg::InferCarve c;
-    const int rc = pcg::infer_carve(g, emb, chunk_rows, list_capacity, c);
+    const int rc = pcg::infer_carve(g, 2, true, emb, chunk_rows, list_capacity, c);
     return rc != PCG_OK ? rc : c.total;
 }
 
@@ -206,64 +232,36 @@ int pcg_infer_set(const pcg_graph_desc *g, const float *theta, int32_t emb, cons
                   float *s0, const double *thresholds, void *workspace, int64_t list_capacity, float *out_logits, float *out_center,
                   uint32_t *status, void *stream) {
     if (!g || !g->X || !theta || !ids || n < 0 || !s0 || !thresholds || !workspace || !out_logits || !status) return PCG_E_ARG;
-    if (g->feat_dim < 1 || g->feat_stride < g->feat_dim || g->feat_stride % 4 != 0 || g->feat_stride > 512) return PCG_E_UNSUPPORTED;
+    if (!pcg::infer_table_ok(g)) return PCG_E_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(g->X) & 15u) != 0) return PCG_E_ARG;
     pcg::InferCarve c;
-    int rc = pcg::infer_carve(g, emb, chunk_rows, list_capacity, c);
+    int rc = pcg::infer_carve(g, 2, true, emb, chunk_rows, list_capacity, c);
     if (rc != PCG_OK) return rc;
     const int F = g->feat_dim, E = emb, R = g->n_rel;
     if (pcg::dense_smem_bytes(F, E, R, pcg::infer_wlds(F, E, R)) > 160 * 1024) return PCG_E_UNSUPPORTED;
     if (n == 0) return PCG_OK;
     unsigned char *ws = static_cast<unsigned char *>(workspace);
-    unsigned char *slot[2] = {ws, ws + c.plan_bytes}, *data = ws + c.data;
-    float *agg = reinterpret_cast<float *>(ws + c.agg);
-    int32_t *cnt = reinterpret_cast<int32_t *>(ws + c.cnt);
-    float *center_scratch = reinterpret_cast<float *>(ws + c.center);
-    const int n_chunks = (int)(((int64_t)n + chunk_rows - 1) / chunk_rows);
-    const int32_t tail = n - (n_chunks - 1) * chunk_rows;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *agg = reinterpret_cast<float *>(ws + c.agg), *center_scratch = reinterpret_cast<float *>(ws + c.center);
+    const pcg::ChunkDriver d = pcg::infer_driver(g, ids, n, chunk_rows, list_capacity, thresholds, s0, 0, 2, workspace, c, status, stream);
 
-    // the front: scores || the look-back words (counters, queue heads, per-workgroup totals) of both slots as the layouts of this
-    // call's chunk sizes place them.  A slot's earlier plans may have laid other arrays over those words: zeroed, none of them
-    // can pass for a published total (the tags the plan launches count from the zeroed sequence word start at 1)
+    // the front: scores || the look-back words of both plan slots
     pcg::ZeroRegions z = {};
-    pcg::infer_zero_regions(z, g, chunk_rows, tail, list_capacity, slot[0], slot[1], data);
-    rc = pcg::launch_infer_front(g, theta + pcg::off_clf(F, E, R), theta + pcg::off_bias(F, E, R), s0, z, st);
+    pcg::infer_zero_regions(z, d);
+    rc = pcg::launch_infer_front(g, theta + pcg::off_clf(F, E, R), theta + pcg::off_bias(F, E, R), s0, z, d.st);
     if (rc != PCG_OK) return rc;
-
-    for (int ch = 0; ch < n_chunks; ++ch) {
-        const int64_t off = (int64_t)ch * chunk_rows;
-        const int32_t B = ch + 1 < n_chunks ? chunk_rows : tail;
-        unsigned char *plan = slot[B == chunk_rows ? 0 : 1];
-        const int32_t *cid = ids + off;
-        rc = pcg_plan_epochs(g, cid, nullptr, B, 1, B, thresholds, nullptr, 0, 0, plan, c.plan_bytes, list_capacity, status, nullptr,
-                             stream);
+    return d.run([&](int64_t off, int32_t B, const int32_t *cid, const pcg::Workspace &w) {
+        // (w.counters: the first part of the chunk's plan slot)
+        const int rc = pcg_gather_lists_planned(g->X, F, g->feat_stride, g->n_nodes, R * B, d.cnt, g, B, d.data, w.counters,
+                                                list_capacity, agg, F, status, stream);
         if (rc != PCG_OK) return rc;
-        rc = pcg_choose_gather_planned(g, cid, nullptr, B, s0, nullptr, nullptr, thresholds, nullptr, 0, 0, agg, F, cnt, data, plan,
-                                       list_capacity, status, nullptr, stream);
-        if (rc != PCG_OK) return rc;
-        pcg::Workspace w;
-        pcg::carve1(g, B, list_capacity, data, &w, plan);
-        pcg::DenseExtra x;
-        x.chunk_begin = w.chunk_begin;
-        x.partial = w.partial;
-        x.cnt = cnt;
-        x.partial_stride = g->feat_stride;
-        pcg::DenseArgs a;
-        int n_sort_blocks = 0;
-        rc = pcg::dense_args(a, n_sort_blocks, g, theta, emb, cid, nullptr, B, agg, F, 0.f, 1.f, out_logits + 2 * off,
-                             out_center ? out_center + 2 * off : center_scratch, nullptr, nullptr, nullptr, nullptr, x);
-        if (rc != PCG_OK) return rc;
-        a.stamps = nullptr;
-        rc = pcg::launch_infer_dense(a, B, st);
-        if (rc != PCG_OK) return rc;
-    }
-    return PCG_OK;
+        return pcg::infer_dense(g, theta, emb, cid, B, w, agg, d.cnt, out_logits + 2 * off,
+                                out_center ? out_center + 2 * off : center_scratch, d.st);
+    });
 }
 
 int64_t pcg_infer_dist_workspace_bytes(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity) {
     pcg::InferCarve c;
-    const int rc = pcg::infer_dist_carve(g, emb, chunk_rows, list_capacity, c);
+    const int rc = pcg::infer_carve(g, 1, true, emb, chunk_rows, list_capacity, c);
     return rc != PCG_OK ? rc : c.total;
 }
 
@@ -276,47 +274,33 @@ int pcg_infer_chunk_dist(const pcg_graph_desc *g, const float *theta, int32_t em
     if (!g || !g->X || !theta || !ids || B < 0 || B > chunk_rows || !row_gid || !halo_X || !halo_ids || halo_cap < 1 || !table ||
         !counts || !s0 || !thresholds || !workspace || !out_logits || !status)
         return PCG_E_ARG;
-    if (g->feat_dim < 1 || g->feat_stride < g->feat_dim || g->feat_stride % 4 != 0 || g->feat_stride > 512) return PCG_E_UNSUPPORTED;
+    if (!pcg::infer_table_ok(g)) return PCG_E_UNSUPPORTED;
     if (((reinterpret_cast<uintptr_t>(g->X) | reinterpret_cast<uintptr_t>(halo_X)) & 15u) != 0) return PCG_E_ARG;
     const int64_t n_local = (int64_t)hi - lo, halo_base = n_local + g->n_pos;
     if (lo < 0 || n_local < 0 || n_table_rows < 0 || n_table_rows > g->n_nodes || halo_base > g->n_nodes) return PCG_E_ARG;
     if (table_slots < 1024 || (table_slots & (table_slots - 1)) != 0 || (g->n_pos > 0 && (!pos_ids || !pos_idx))) return PCG_E_ARG;
     pcg::InferCarve c;
-    int rc = pcg::infer_dist_carve(g, emb, chunk_rows, list_capacity, c);
+    int rc = pcg::infer_carve(g, 1, true, emb, chunk_rows, list_capacity, c);
     if (rc != PCG_OK) return rc;
     const int F = g->feat_dim, E = emb, R = g->n_rel;
     if (pcg::dense_smem_bytes(F, E, R, pcg::infer_wlds(F, E, R)) > 160 * 1024) return PCG_E_UNSUPPORTED;
     if (B == 0) return PCG_OK;
     unsigned char *ws = static_cast<unsigned char *>(workspace);
-    unsigned char *plan = ws, *data = ws + c.data;
-    float *agg = reinterpret_cast<float *>(ws + c.agg);
-    int32_t *cnt = reinterpret_cast<int32_t *>(ws + c.cnt);
-    float *center_scratch = reinterpret_cast<float *>(ws + c.center);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    pcg::Workspace w;
-    pcg::carve1(g, B, list_capacity, data, &w, plan);
+    float *agg = reinterpret_cast<float *>(ws + c.agg), *center_scratch = reinterpret_cast<float *>(ws + c.center);
+    // one chunk of B rows in the one slot (the layout is B's own); centre scores by global id: s0[ids[b] + lo]; lists of global ids
+    const pcg::ChunkDriver d = pcg::infer_driver(g, ids, B, B, list_capacity, thresholds, s0, lo, 1, workspace, c, status, stream);
 
     // front: halo scores (+ the table's on the first chunk) || the look-back words of this chunk's plan layout
     pcg::ZeroRegions z = {};
-    z.p[0] = w.counters;                                          // counters | heads: contiguous (256 + 512 bytes)
-    z.n[0] = (reinterpret_cast<unsigned char *>(w.heads) - reinterpret_cast<unsigned char *>(w.counters) + 4 * 8 * 16) / 4;
-    z.p[1] = reinterpret_cast<uint32_t *>(w.plan_totals);
-    z.n[1] = 64 * ((int64_t)R * B / 256 + 2) / 4;
-    const int n_zero = (int)((z.n[0] + z.n[1] + pcg::INFER_ZERO_WORDS - 1) / pcg::INFER_ZERO_WORDS);
+    pcg::infer_zero_regions(z, d);
+    const int n_zero = pcg::infer_zero_blocks(z);
     const int64_t tab_rows = first ? n_table_rows : 0;
     const int n_tab = tab_rows > 0 ? (int)pcg::score_table_blocks(tab_rows, g->feat_stride) : 0;
     const int n_halo = (int)pcg::score_table_blocks(halo_cap, g->feat_stride);
-    hipLaunchKernelGGL(pcg::infer_front_dist_kernel, dim3(n_tab + n_halo + n_zero), dim3(256), 0, st, g->X, halo_X, g->feat_dim,
+    hipLaunchKernelGGL(pcg::infer_front_dist_kernel, dim3(n_tab + n_halo + n_zero), dim3(256), 0, d.st, g->X, halo_X, g->feat_dim,
                        g->feat_stride, theta + pcg::off_clf(F, E, R), theta + pcg::off_bias(F, E, R), row_gid, tab_rows, halo_ids,
                        (int64_t)halo_cap, s0, n_tab, n_halo, z);
     PCG_LAUNCH_CHECK();
-    // plan (test mode) -> select (centre scores by global id: s0[ids[b] + lo]; lists of global ids)
-    rc = pcg_plan_epochs(g, ids, nullptr, B, 1, B, thresholds, nullptr, 0, 0, plan, c.plan_bytes, list_capacity, status, nullptr,
-                         stream);
-    if (rc != PCG_OK) return rc;
-    rc = pcg_choose_select_planned(g, ids, nullptr, B, s0, nullptr, nullptr, thresholds, nullptr, 0, 0, cnt, data, plan,
-                                   list_capacity, status, nullptr, lo, stream);
-    if (rc != PCG_OK) return rc;
     // gather: ids -> owned / train-pos rows of g->X, fetched rows of the inference halo (its own hash table)
     pcg::HaloMap hm;
     hm.keys = table;
@@ -326,21 +310,12 @@ int pcg_infer_chunk_dist(const pcg_graph_desc *g, const float *theta, int32_t em
     hm.pos_ids = pos_ids; hm.pos_idx = pos_idx; hm.n_pos = g->n_pos;
     hm.halo_cap = halo_cap; hm.halo_base = (int32_t)halo_base;
     hm.overflow = counts + 128;
-    rc = pcg::launch_gather_infer(g->X, F, g->feat_stride, R * B, cnt, w, agg, F, status, hm, halo_X, st);
-    if (rc != PCG_OK) return rc;
-    // dense: the centres are local table rows
-    pcg::DenseExtra x;
-    x.chunk_begin = w.chunk_begin;
-    x.partial = w.partial;
-    x.cnt = cnt;
-    x.partial_stride = g->feat_stride;
-    pcg::DenseArgs a;
-    int n_sort_blocks = 0;
-    rc = pcg::dense_args(a, n_sort_blocks, g, theta, emb, ids, nullptr, B, agg, F, 0.f, 1.f, out_logits,
-                         out_center ? out_center : center_scratch, nullptr, nullptr, nullptr, nullptr, x);
-    if (rc != PCG_OK) return rc;
-    a.stamps = nullptr;
-    return pcg::launch_infer_dense(a, B, st);
+    return d.run([&](int64_t, int32_t, const int32_t *, const pcg::Workspace &w) {
+        const int rc = pcg::launch_gather_infer(g->X, F, g->feat_stride, R * B, d.cnt, w, agg, F, status, hm, halo_X, d.st);
+        if (rc != PCG_OK) return rc;
+        // dense: the centres are local table rows
+        return pcg::infer_dense(g, theta, emb, ids, B, w, agg, d.cnt, out_logits, out_center ? out_center : center_scratch, d.st);
+    });
 }
 
 }  // extern "C"

@@ -5,8 +5,8 @@
 //   infer_new_front_kernel : [the base table's score pass (score_table_body over g->X: pcg_score_table's workgroups, rows and fma
 //                            order) - only when the caller's s0[0, N) is not current] || the query rows' scores -> s0[N, N + nq)
 //                            || the look-back words of the call's two plan slots zeroed
-//   per chunk of ids       : plan (test mode, over the QUERY's CSR) -> select (centre score s0[ids[b] + N]; lists of global ids)
-//                            -> two-table gather (gather.hip: id < N reads g->X, id >= N reads q->X) -> infer_dense_kernel with
+//   per chunk of ids       : plan (test mode, over the QUERY's CSR) -> select (centre score s0[ids[b] + N]; lists of global ids:
+//                            ChunkDriver::run, infer.h) -> two-table gather (gather.hip: id < N reads g->X, id >= N reads q->X) -> infer_dense_kernel with
 //                            the self rows from q->X
 //
 // PC-GNN here is one layer and test mode makes no minority picks: a node's logits are a function of its own feature row, its own
@@ -61,7 +61,7 @@ int64_t pcg_infer_new_workspace_bytes(const pcg_graph_desc *g, const pcg_graph_d
     if (rc != PCG_OK) return rc;
     // plan, select, gather and dense all work on the QUERY's rows: the layout is pcg_infer_set's for that descriptor
     pcg::InferCarve c;
-    rc = pcg::infer_carve(q, emb, chunk_rows, list_capacity, c);
+    rc = pcg::infer_carve(q, 2, true, emb, chunk_rows, list_capacity, c);
     return rc != PCG_OK ? rc : c.total;
 }
 
@@ -71,9 +71,9 @@ int pcg_infer_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float 
     int rc = pcg::infer_new_descs(g, q);
     if (rc != PCG_OK) return rc;
     if (n < 0) return PCG_E_ARG;
-    if (g->feat_dim < 1 || g->feat_stride < g->feat_dim || g->feat_stride % 4 != 0 || g->feat_stride > 512) return PCG_E_UNSUPPORTED;
+    if (!pcg::infer_table_ok(g)) return PCG_E_UNSUPPORTED;
     pcg::InferCarve c;
-    rc = pcg::infer_carve(q, emb, chunk_rows, list_capacity, c);
+    rc = pcg::infer_carve(q, 2, true, emb, chunk_rows, list_capacity, c);
     if (rc != PCG_OK) return rc;
     const int F = g->feat_dim, E = emb, R = g->n_rel;
     if (pcg::dense_smem_bytes(F, E, R, pcg::infer_wlds(F, E, R)) > 160 * 1024) return PCG_E_UNSUPPORTED;
@@ -82,57 +82,27 @@ int pcg_infer_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float 
     if (((reinterpret_cast<uintptr_t>(g->X) | reinterpret_cast<uintptr_t>(q->X)) & 15u) != 0) return PCG_E_ARG;
     const int64_t N = g->n_nodes, nq = q->n_nodes;
     unsigned char *ws = static_cast<unsigned char *>(workspace);
-    unsigned char *slot[2] = {ws, ws + c.plan_bytes}, *data = ws + c.data;
-    float *agg = reinterpret_cast<float *>(ws + c.agg);
-    int32_t *cnt = reinterpret_cast<int32_t *>(ws + c.cnt);
-    float *center_scratch = reinterpret_cast<float *>(ws + c.center);
-    const int n_chunks = (int)(((int64_t)n + chunk_rows - 1) / chunk_rows);
-    const int32_t tail = n - (n_chunks - 1) * chunk_rows;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *agg = reinterpret_cast<float *>(ws + c.agg), *center_scratch = reinterpret_cast<float *>(ws + c.center);
+    // the rows are the query's, the scores are indexed by global id (centre b: s0[ids[b] + N])
+    const pcg::ChunkDriver d = pcg::infer_driver(q, ids, n, chunk_rows, list_capacity, thresholds, s0, N, 2, workspace, c, status, stream);
 
     // the front: [base scores] || query scores || the look-back words of both plan slots (as pcg_infer_set zeroes them)
     pcg::ZeroRegions z = {};
-    pcg::infer_zero_regions(z, q, chunk_rows, tail, list_capacity, slot[0], slot[1], data);
-    const int64_t zero_words = z.n[0] + z.n[1] + z.n[2] + z.n[3];
-    const int n_zero = (int)((zero_words + pcg::INFER_ZERO_WORDS - 1) / pcg::INFER_ZERO_WORDS);
+    pcg::infer_zero_regions(z, d);
+    const int n_zero = pcg::infer_zero_blocks(z);
     const int n_base = score_base ? (int)pcg::score_table_blocks(N, g->feat_stride) : 0;
     const int n_query = (int)pcg::score_table_blocks(nq, g->feat_stride);
-    hipLaunchKernelGGL(pcg::infer_new_front_kernel, dim3(n_base + n_query + n_zero), dim3(256), 0, st, g->X, N, q->X, nq, F,
+    hipLaunchKernelGGL(pcg::infer_new_front_kernel, dim3(n_base + n_query + n_zero), dim3(256), 0, d.st, g->X, N, q->X, nq, F,
                        g->feat_stride, theta + pcg::off_clf(F, E, R), theta + pcg::off_bias(F, E, R), s0, n_base, n_query, z);
     PCG_LAUNCH_CHECK();
 
-    for (int ch = 0; ch < n_chunks; ++ch) {
-        const int64_t off = (int64_t)ch * chunk_rows;
-        const int32_t B = ch + 1 < n_chunks ? chunk_rows : tail;
-        unsigned char *plan = slot[B == chunk_rows ? 0 : 1];
-        const int32_t *cid = ids + off;
-        rc = pcg_plan_epochs(q, cid, nullptr, B, 1, B, thresholds, nullptr, 0, 0, plan, c.plan_bytes, list_capacity, status, nullptr,
-                             stream);
-        if (rc != PCG_OK) return rc;
-        // select: the rows are the query's, the scores are indexed by global id (centre b: s0[ids[b] + N])
-        rc = pcg_choose_select_planned(q, cid, nullptr, B, s0, nullptr, nullptr, thresholds, nullptr, 0, 0, cnt, data, plan,
-                                       list_capacity, status, nullptr, N, stream);
-        if (rc != PCG_OK) return rc;
-        pcg::Workspace w;
-        pcg::carve1(q, B, list_capacity, data, &w, plan);
-        rc = pcg::launch_gather_two(g->X, N, q->X, nq, F, g->feat_stride, R * B, cnt, w, agg, F, status, st);
+    return d.run([&](int64_t off, int32_t B, const int32_t *cid, const pcg::Workspace &w) {
+        const int rc = pcg::launch_gather_two(g->X, N, q->X, nq, F, g->feat_stride, R * B, d.cnt, w, agg, F, status, d.st);
         if (rc != PCG_OK) return rc;
         // dense: the centres are rows of the query table
-        pcg::DenseExtra x;
-        x.chunk_begin = w.chunk_begin;
-        x.partial = w.partial;
-        x.cnt = cnt;
-        x.partial_stride = q->feat_stride;
-        pcg::DenseArgs a;
-        int n_sort_blocks = 0;
-        rc = pcg::dense_args(a, n_sort_blocks, q, theta, emb, cid, nullptr, B, agg, F, 0.f, 1.f, out_logits + 2 * off,
-                             out_center ? out_center + 2 * off : center_scratch, nullptr, nullptr, nullptr, nullptr, x);
-        if (rc != PCG_OK) return rc;
-        a.stamps = nullptr;
-        rc = pcg::launch_infer_dense(a, B, st);
-        if (rc != PCG_OK) return rc;
-    }
-    return PCG_OK;
+        return pcg::infer_dense(q, theta, emb, cid, B, w, agg, d.cnt, out_logits + 2 * off,
+                                out_center ? out_center + 2 * off : center_scratch, d.st);
+    });
 }
 
 }  // extern "C"

@@ -321,22 +321,6 @@ static int launch_rank_lists(const pcg_graph_desc *g, const int32_t *nodes, int3
     return PCG_OK;
 }
 
-// the call's workspace: [plan slot of full chunks | plan slot of the last, shorter chunk | data part | cnt [R][chunk]]
-struct ChosenCarve {
-    int64_t plan_bytes, data, cnt, total;
-};
-static int chosen_carve(const pcg_graph_desc *g, int32_t chunk_rows, int64_t list_capacity, ChosenCarve &c) {
-    if (!g || chunk_rows < 1 || list_capacity < 1 || list_capacity >= (1ll << 31)) return PCG_E_ARG;
-    if (g->n_rel < 1 || g->n_rel > PCG_MAX_REL || g->feat_dim < 1) return PCG_E_UNSUPPORTED;
-    if ((int64_t)g->n_rel * chunk_rows >= (1ll << 31)) return PCG_E_ARG;
-    const CarveSizes sz = carve(g, chunk_rows, list_capacity, nullptr, nullptr, nullptr);
-    c.plan_bytes = sz.plan_bytes;
-    c.data = 2 * sz.plan_bytes;
-    c.cnt = c.data + align256(sz.data_bytes);
-    c.total = c.cnt + align256(4 * (int64_t)g->n_rel * chunk_rows);
-    return PCG_OK;
-}
-
 }  // namespace pcg
 
 extern "C" {
@@ -355,8 +339,9 @@ int pcg_rank_lists(const pcg_graph_desc *g, const int32_t *nodes, int32_t B, con
 }
 
 int64_t pcg_chosen_workspace_bytes(const pcg_graph_desc *g, int32_t chunk_rows, int64_t list_capacity) {
-    pcg::ChosenCarve c;
-    const int rc = pcg::chosen_carve(g, chunk_rows, list_capacity, c);
+    // (pcg_infer_set's two plan slots and data part, then cnt [R][chunk]: no dense parts)
+    pcg::InferCarve c;
+    const int rc = pcg::infer_carve(g, 2, false, 0, chunk_rows, list_capacity, c);
     return rc != PCG_OK ? rc : c.total;
 }
 
@@ -365,45 +350,24 @@ int pcg_chosen_set(const pcg_graph_desc *g, const float *theta, int32_t emb, con
                    int32_t *out_ids, float *out_dist, uint32_t *status, void *stream) {
     if (!g || !g->X || !theta || !ids || n < 0 || !s0 || !thresholds || !workspace || !out_begin || !out_ids || !out_dist || !status)
         return PCG_E_ARG;
-    if (g->feat_dim < 1 || g->feat_stride < g->feat_dim || g->feat_stride % 4 != 0 || g->feat_stride > 512) return PCG_E_UNSUPPORTED;
+    if (!pcg::infer_table_ok(g)) return PCG_E_UNSUPPORTED;
     if (emb < 16 || emb % 16 != 0) return PCG_E_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(g->X) & 15u) != 0 || g->n_nodes < 1) return PCG_E_ARG;
-    pcg::ChosenCarve c;
-    int rc = pcg::chosen_carve(g, chunk_rows, list_capacity, c);
+    pcg::InferCarve c;
+    int rc = pcg::infer_carve(g, 2, false, 0, chunk_rows, list_capacity, c);
     if (rc != PCG_OK) return rc;
     if (n == 0) return PCG_OK;
     const int F = g->feat_dim, E = emb, R = g->n_rel;
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    unsigned char *slot[2] = {ws, ws + c.plan_bytes}, *data = ws + c.data;
-    int32_t *cnt = reinterpret_cast<int32_t *>(ws + c.cnt);
-    const int n_chunks = (int)(((int64_t)n + chunk_rows - 1) / chunk_rows);
-    const int32_t tail = n - (n_chunks - 1) * chunk_rows;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    const pcg::ChunkDriver d = pcg::infer_driver(g, ids, n, chunk_rows, list_capacity, thresholds, s0, 0, 2, workspace, c, status, stream);
 
     // pcg_infer_set's front: the score pass || the look-back words of both plan slots zeroed
     pcg::ZeroRegions z = {};
-    pcg::infer_zero_regions(z, g, chunk_rows, tail, list_capacity, slot[0], slot[1], data);
-    rc = pcg::launch_infer_front(g, theta + pcg::off_clf(F, E, R), theta + pcg::off_bias(F, E, R), s0, z, st);
+    pcg::infer_zero_regions(z, d);
+    rc = pcg::launch_infer_front(g, theta + pcg::off_clf(F, E, R), theta + pcg::off_bias(F, E, R), s0, z, d.st);
     if (rc != PCG_OK) return rc;
-
-    for (int ch = 0; ch < n_chunks; ++ch) {
-        const int64_t off = (int64_t)ch * chunk_rows;
-        const int32_t B = ch + 1 < n_chunks ? chunk_rows : tail;
-        unsigned char *plan = slot[B == chunk_rows ? 0 : 1];
-        const int32_t *cid = ids + off;
-        rc = pcg_plan_epochs(g, cid, nullptr, B, 1, B, thresholds, nullptr, 0, 0, plan, c.plan_bytes, list_capacity, status, nullptr,
-                             stream);
-        if (rc != PCG_OK) return rc;
-        // (rows beyond the select kernel's LDS key capacity: its long-row launch, as in pcg_infer_set)
-        rc = pcg_choose_select_planned(g, cid, nullptr, B, s0, nullptr, nullptr, thresholds, nullptr, 0, 0, cnt, data, plan,
-                                       list_capacity, status, nullptr, 0, stream);
-        if (rc != PCG_OK) return rc;
-        pcg::Workspace w;
-        pcg::carve1(g, B, list_capacity, data, &w, plan);
-        rc = pcg::launch_rank_lists(g, cid, B, n, off, s0, nullptr, w, out_begin, out_ids, out_dist, status, st);
-        if (rc != PCG_OK) return rc;
-    }
-    return PCG_OK;
+    return d.run([&](int64_t off, int32_t B, const int32_t *cid, const pcg::Workspace &w) {
+        return pcg::launch_rank_lists(g, cid, B, n, off, s0, nullptr, w, out_begin, out_ids, out_dist, status, d.st);
+    });
 }
 
 }  // extern "C"

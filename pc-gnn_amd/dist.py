@@ -925,20 +925,14 @@ class DistributedPCGNN:
         lists or halo went over capacity, every rank raises."""
         g, part, lib, _p = self.g, self.part, self.lib, self.ops._p
         self.flush()
+        from .fused import default_infer_chunk, infer_row_caps, whole_set_buffers, whole_set_ids, whole_set_workspace
         inf = self._inf
+        ids_host, ids_dev, n = whole_set_ids(ids_local, part.n_local, self.dev, "infer: ids_local", all_ids=inf.get("all_dev"))
         if ids_local is None:
+            inf["all_dev"] = ids_dev
             ids_host = inf.get("all_host")
             if ids_host is None:
-                ids_host = inf["all_host"] = np.arange(part.n_local, dtype=np.int64)
-                inf["all_dev"] = torch.arange(part.n_local, dtype=torch.int32, device=self.dev)
-            ids_dev = inf["all_dev"]
-        else:
-            ids_host = (ids_local.detach().cpu().numpy() if torch.is_tensor(ids_local) else np.asarray(ids_local)).reshape(-1)
-            ids_host = ids_host.astype(np.int64)
-            if ids_host.size and (ids_host.min() < 0 or ids_host.max() >= part.n_local):
-                raise ValueError(f"infer: ids_local outside 0 .. {part.n_local - 1}")
-            ids_dev = torch.from_numpy(ids_host.astype(np.int32)).to(self.dev)
-        n = int(ids_host.size)
+                ids_host = inf["all_host"] = np.arange(n, dtype=np.int64)
         # the halo pitch: the same on every rank (equal-split all-to-alls)
         if ids_local is None:
             pairs = inf.get("all_pairs")
@@ -954,7 +948,6 @@ class DistributedPCGNN:
         exchange = pitch > 0
         pitch = max(pitch, 1)
         # the chunks (cached for the owned set: its rows never change) and how many every rank runs
-        from .fused import default_infer_chunk, infer_row_caps
         ws_bytes = lambda c, cap: int(lib.pcg_infer_dist_workspace_bytes(g.desc_ref(), self.E, c, cap))
         if chunk is None:
             caps = infer_row_caps([np.diff(ip) for ip, _ in self.csr_host], self.thresholds, ids_host)
@@ -972,15 +965,9 @@ class DistributedPCGNN:
         center = torch.empty(n, 2, dtype=torch.float32, device=self.dev) if want_center else None
         h = self._infer_halo(pitch)
         rows = max([b - a for a, b in chunks], default=1)
-        nbytes = ws_bytes(rows, cap)
-        if nbytes < 0:
-            raise self._libmod.PcgnnLibraryError(f"pcg_infer_dist_workspace_bytes rejected chunk {rows} / list capacity {cap} ({nbytes})")
-        if inf.get("ws") is None or inf["ws"].numel() < nbytes:
-            inf["ws"] = None
-            inf["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        if inf.get("s0") is None:
-            inf["s0"] = torch.zeros(self.s0_full.numel(), dtype=torch.float32, device=self.dev)
-            inf["status"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        ws = whole_set_workspace(inf, "ws", self.dev, ws_bytes, "pcg_infer_dist_workspace_bytes", rows, cap)
+        whole_set_buffers(inf, self.dev, "s0", self.s0_full.numel())
+        if inf.get("none") is None:
             inf["none"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
         st = self.ops._stream(self.dev)
         if not exchange:
@@ -1001,7 +988,7 @@ class DistributedPCGNN:
             self._libmod.check(lib.pcg_infer_chunk_dist(
                 g.desc_ref(), _p(self.theta), self.E, _p(cid), b - a, 1 if k == 0 else 0, _p(self.row_gid), part.n_local + g.n_pos,
                 _p(h.halo_rows), _p(h.req_out), h.halo_cap, part.lo, part.hi, _p(h.pos_ids32), _p(h.pos_idx32), _p(h.table), h.slots,
-                _p(h.counts), _p(inf["s0"]), self._thr, _p(inf["ws"]), rows, cap, _p(logits[a:b]),
+                _p(h.counts), _p(inf["s0"]), self._thr, _p(ws), rows, cap, _p(logits[a:b]),
                 _p(center[a:b]) if center is not None else None, _p(inf["status"]), st), "pcg_infer_chunk_dist")
         halo, lists = self._agree_flags(h.overflow_word, inf["status"])
         if halo or lists:

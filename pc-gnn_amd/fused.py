@@ -89,6 +89,62 @@ def default_infer_chunk(caps: np.ndarray, workspace_bytes, max_bytes: int, min_c
     return c
 
 
+def whole_set_ids(ids, rows: int, dev, what: str, note: str = "", all_ids: Optional[torch.Tensor] = None):
+    """The ids of a whole-set call (a tensor, numpy array or list of row numbers in [0, rows); None = every row) as
+    (ids_host int64 - None when ids is None -, ids_dev int32 on dev, n).  all_ids: the caller's cached arange(rows) for None.
+    `what` names the method and its argument in the range error (f"{what} outside 0 .. {rows - 1}{note}")."""
+    if ids is None:
+        if all_ids is None or all_ids.numel() != rows:
+            all_ids = torch.arange(rows, dtype=torch.int32, device=dev)
+        return None, all_ids, rows
+    ids_host = (ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)).reshape(-1).astype(np.int64)
+    n = int(ids_host.size)
+    if n and (ids_host.min() < 0 or ids_host.max() >= rows):
+        raise ValueError(f"{what} outside 0 .. {rows - 1}{note}")
+    ids_dev = ops._i32(ids, dev).view(-1) if torch.is_tensor(ids) else torch.from_numpy(ids_host.astype(np.int32)).to(dev)
+    return ids_host, ids_dev, n
+
+
+def whole_set_workspace(inf: dict, key: str, dev, ws_bytes, what: str, chunk: int, cap: int, need: Optional[int] = None):
+    """inf[key]: the grow-only device workspace of a whole-set call, of at least ws_bytes(chunk, cap) bytes (and of
+    ws_bytes(chunk, need), when a list capacity other than the exact one, `need`, was forced)."""
+    nbytes = ws_bytes(chunk, cap)
+    if nbytes >= 0 and need is not None:
+        nbytes = max(nbytes, ws_bytes(chunk, need))
+    if nbytes < 0:
+        raise _lib.PcgnnLibraryError(f"{what} rejected chunk {chunk} / list capacity {cap} ({nbytes})")
+    if inf.get(key) is None or inf[key].numel() < nbytes:
+        inf[key] = None
+        inf[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return inf[key]
+
+
+def whole_set_chunk(inf: dict, key: str, dev, ws_bytes, what: str, caps: np.ndarray, chunk: Optional[int], max_bytes: int,
+                    list_capacity: Optional[int] = None):
+    """(chunk, list capacity, workspace) of a whole-set call over len(caps) > 0 ids: the caller's chunk (None: default_infer_chunk)
+    clamped to the set, the capacity that covers its largest chunk exactly, and inf[key] grown to hold them.  list_capacity
+    forces another capacity (the tests' way to an overflow): a bounded list that overflows leaves the dense launch walking the
+    chunk offsets the plan worked out for the rows of several chunks - the buffer is as large as the exact capacity's, so those
+    reads stay inside it."""
+    chunk = default_infer_chunk(caps, ws_bytes, max_bytes) if chunk is None else int(chunk)
+    chunk = max(1, min(chunk, len(caps)))
+    _, need = infer_chunks(caps, chunk)
+    cap = need if list_capacity is None else max(int(list_capacity), 1)
+    return chunk, cap, whole_set_workspace(inf, key, dev, ws_bytes, what, chunk, cap, need)
+
+
+def whole_set_buffers(inf: dict, dev, s0_key: str, need: int, alloc: Optional[int] = None) -> bool:
+    """inf["status"] (the call's status word) and inf[s0_key] (its score buffer, at least `need` floats; a new one has `alloc`),
+    created when missing.  True: the score buffer is new and holds no scores."""
+    if inf.get("status") is None:
+        inf["status"] = torch.zeros(1, dtype=torch.int32, device=dev)
+    if inf.get(s0_key) is not None and inf[s0_key].numel() >= need:
+        return False
+    inf[s0_key] = None
+    inf[s0_key] = torch.zeros(alloc or need, dtype=torch.float32, device=dev)
+    return True
+
+
 class FusedPCGNN:
     def __init__(self, model: PCALayer, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8,
                  max_batch: int = 1024, global_batch_scale: int = 1, list_capacity: Optional[int] = None,
@@ -1089,43 +1145,21 @@ class FusedPCGNN:
         B and any chunk.  chunk: ids per chunk (default: all of them, or fewer - never under 16384 - if the workspace would
         exceed infer_workspace_bytes).  The training engine is left alone: its score table, keys, plans, captured graphs and
         buffer sizes are untouched (a deferred update is applied first, as predict does).  Synchronises once (the status word)."""
-        g, lib = self.g, self.lib
+        g, lib, inf = self.g, self.lib, self._inf
         self.flush()
+        ids_host, ids_dev, n = whole_set_ids(ids, g.n_nodes, self.dev, "infer: ids", all_ids=inf.get("all_ids"))
         if ids is None:
-            n = g.n_nodes
-            ids_dev = self._inf.get("all_ids")
-            if ids_dev is None or ids_dev.numel() != n:
-                ids_dev = self._inf["all_ids"] = torch.arange(n, dtype=torch.int32, device=self.dev)
-            caps = infer_row_caps(g.deg_host, self.thresholds)
-        else:
-            ids_host = (ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)).reshape(-1).astype(np.int64)
-            n = int(ids_host.size)
-            if n and (ids_host.min() < 0 or ids_host.max() >= g.n_nodes):
-                raise ValueError(f"infer: ids outside 0 .. {g.n_nodes - 1}")
-            ids_dev = ops._i32(ids, self.dev).view(-1) if torch.is_tensor(ids) else \
-                torch.from_numpy(ids_host.astype(np.int32)).to(self.dev)
-            caps = infer_row_caps(g.deg_host, self.thresholds, ids_host)
+            inf["all_ids"] = ids_dev
         logits = torch.empty(n, 2, dtype=torch.float32, device=self.dev)
         center = torch.empty(n, 2, dtype=torch.float32, device=self.dev) if want_center else None
         if n == 0:
             return (logits, center) if want_center else logits
         ws_bytes = lambda c, cap: int(lib.pcg_infer_workspace_bytes(g.desc_ref(), self.E, c, cap))
-        chunk = default_infer_chunk(caps, ws_bytes, self.infer_workspace_bytes) if chunk is None else int(chunk)
-        chunk = max(1, min(chunk, n))
-        _, cap = infer_chunks(caps, chunk)
-        nbytes = ws_bytes(chunk, cap)
-        if nbytes < 0:
-            raise _lib.PcgnnLibraryError(f"pcg_infer_workspace_bytes rejected chunk {chunk} / list capacity {cap} ({nbytes})")
-        inf = self._inf
-        if inf.get("ws") is None or inf["ws"].numel() < nbytes:
-            inf["ws"] = None
-            inf["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        if inf.get("s0") is None:
-            inf["s0"] = torch.empty(g.n_nodes, dtype=torch.float32, device=self.dev)
-        if inf.get("status") is None:
-            inf["status"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        chunk, cap, ws = whole_set_chunk(inf, "ws", self.dev, ws_bytes, "pcg_infer_workspace_bytes",
+                                         infer_row_caps(g.deg_host, self.thresholds, ids_host), chunk, self.infer_workspace_bytes)
+        whole_set_buffers(inf, self.dev, "s0", g.n_nodes)
         _lib.check(lib.pcg_infer_set(g.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk, _p(inf["s0"]), self._thr,
-                                     _p(inf["ws"]), cap, _p(logits), _p(center), _p(inf["status"]), self._stream()), "pcg_infer_set")
+                                     _p(ws), cap, _p(logits), _p(center), _p(inf["status"]), self._stream()), "pcg_infer_set")
         self._infer_status()
         return (logits, center) if want_center else logits
 
@@ -1138,22 +1172,12 @@ class FusedPCGNN:
         the degrees (a test-mode row keeps exactly deg > k + 1 ? k : deg entries), so the result is sized exactly.  Returns a
         ``ChosenLists``.  The training engine is left alone exactly as by ``infer`` (a deferred update is applied first).
         Synchronises once (the status word)."""
-        g, lib = self.g, self.lib
+        g, lib, inf = self.g, self.lib, self._inf
         self.flush()
-        inf = self._inf
+        ids_host, ids_dev, n = whole_set_ids(ids, g.n_nodes, self.dev, "chosen: ids", all_ids=inf.get("all_ids"))
         if ids is None:
-            n = g.n_nodes
-            ids_dev = inf.get("all_ids")
-            if ids_dev is None or ids_dev.numel() != n:
-                ids_dev = inf["all_ids"] = torch.arange(n, dtype=torch.int32, device=self.dev)
+            inf["all_ids"] = ids_dev
             ids_host = np.arange(n, dtype=np.int64)
-        else:
-            ids_host = (ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)).reshape(-1).astype(np.int64)
-            n = int(ids_host.size)
-            if n and (ids_host.min() < 0 or ids_host.max() >= g.n_nodes):
-                raise ValueError(f"chosen: ids outside 0 .. {g.n_nodes - 1}")
-            ids_dev = ops._i32(ids, self.dev).view(-1) if torch.is_tensor(ids) else \
-                torch.from_numpy(ids_host.astype(np.int32)).to(self.dev)
         caps2 = ops.sel_capacity(g, ids_host, None, self.thresholds, 0.0, False)      # [R, n]: exact in test mode
         off = ops.rank_offsets(caps2)
         total = int(off[-1])
@@ -1163,23 +1187,12 @@ class FusedPCGNN:
         res = ChosenLists(out_begin, out_ids, out_dist, g.R, n, host_offsets=off)
         if n == 0:
             return res
-        caps = caps2.sum(0)                                                          # == infer_row_caps
         ws_bytes = lambda c, cap: int(lib.pcg_chosen_workspace_bytes(g.desc_ref(), c, cap))
-        chunk = default_infer_chunk(caps, ws_bytes, self.infer_workspace_bytes) if chunk is None else int(chunk)
-        chunk = max(1, min(chunk, n))
-        _, cap = infer_chunks(caps, chunk)
-        nbytes = ws_bytes(chunk, cap)
-        if nbytes < 0:
-            raise _lib.PcgnnLibraryError(f"pcg_chosen_workspace_bytes rejected chunk {chunk} / list capacity {cap} ({nbytes})")
-        if inf.get("chosen_ws") is None or inf["chosen_ws"].numel() < nbytes:
-            inf["chosen_ws"] = None
-            inf["chosen_ws"] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        if inf.get("s0") is None:
-            inf["s0"] = torch.empty(g.n_nodes, dtype=torch.float32, device=self.dev)
-        if inf.get("status") is None:
-            inf["status"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        chunk, cap, ws = whole_set_chunk(inf, "chosen_ws", self.dev, ws_bytes, "pcg_chosen_workspace_bytes",
+                                         caps2.sum(0), chunk, self.infer_workspace_bytes)     # (the sum == infer_row_caps)
+        whole_set_buffers(inf, self.dev, "s0", g.n_nodes)
         _lib.check(lib.pcg_chosen_set(g.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk, _p(inf["s0"]), self._thr,
-                                      _p(inf["chosen_ws"]), cap, _p(out_begin), _p(out_ids), _p(out_dist), _p(inf["status"]),
+                                      _p(ws), cap, _p(out_begin), _p(out_ids), _p(out_dist), _p(inf["status"]),
                                       self._stream()), "pcg_chosen_set")
         self._infer_status()
         return res
@@ -1213,52 +1226,23 @@ class FusedPCGNN:
                              f"features / {query.R} relations, this engine's has {g.n_nodes} / {g.feat_dim} / {g.R}")
         if query.X is None or query.device != self.dev or query.feat_stride != g.feat_stride:
             query.to(self.dev, g)
-        nq = query.nq
-        if ids is None:
-            n = nq
-            ids_host = None
-            ids_dev = torch.arange(n, dtype=torch.int32, device=self.dev)
-            caps = infer_row_caps(query.deg_host, self.thresholds)
-        else:
-            ids_host = (ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)).reshape(-1).astype(np.int64)
-            n = int(ids_host.size)
-            if n and (ids_host.min() < 0 or ids_host.max() >= nq):
-                raise ValueError(f"infer_new: ids outside 0 .. {nq - 1} (query-local rows)")
-            ids_dev = ops._i32(ids, self.dev).view(-1) if torch.is_tensor(ids) else \
-                torch.from_numpy(ids_host.astype(np.int32)).to(self.dev)
-            caps = infer_row_caps(query.deg_host, self.thresholds, ids_host)
+        nq, inf = query.nq, self._inf
+        ids_host, ids_dev, n = whole_set_ids(ids, nq, self.dev, "infer_new: ids", " (query-local rows)")
         logits = torch.empty(n, 2, dtype=torch.float32, device=self.dev)
         center = torch.empty(n, 2, dtype=torch.float32, device=self.dev) if want_center else None
         if n == 0:
             return (logits, center) if want_center else logits
         ws_bytes = lambda c, cap: int(lib.pcg_infer_new_workspace_bytes(g.desc_ref(), query.desc_ref(), self.E, c, cap))
-        chunk = default_infer_chunk(caps, ws_bytes, self.infer_workspace_bytes) if chunk is None else int(chunk)
-        chunk = max(1, min(chunk, n))
-        _, cap = infer_chunks(caps, chunk)
-        need = cap
-        if _list_capacity is not None:
-            cap = max(int(_list_capacity), 1)
-        # (a bounded list that overflows: the dense launch still walks the chunk offsets the plan worked out for the rows of
-        #  several chunks - the buffer is as large as the exact capacity's, so those reads stay inside it)
-        nbytes = max(ws_bytes(chunk, cap), ws_bytes(chunk, need)) if ws_bytes(chunk, cap) >= 0 else ws_bytes(chunk, cap)
-        if nbytes < 0:
-            raise _lib.PcgnnLibraryError(f"pcg_infer_new_workspace_bytes rejected chunk {chunk} / list capacity {cap} ({nbytes})")
-        inf = self._inf
-        if inf.get("new_ws") is None or inf["new_ws"].numel() < nbytes:
-            inf["new_ws"] = None
-            inf["new_ws"] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        if inf.get("status") is None:
-            inf["status"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        if inf.get("new_s0") is None or inf["new_s0"].numel() < g.n_nodes + nq:
-            # a grown buffer holds no scores: capacity in powers of two, so a stream of batches grows it a few times at most
-            capacity = 1 << max(nq - 1, 255).bit_length()
-            inf["new_s0"] = None
-            inf["new_s0"] = torch.empty(g.n_nodes + capacity, dtype=torch.float32, device=self.dev)
+        chunk, cap, ws = whole_set_chunk(inf, "new_ws", self.dev, ws_bytes, "pcg_infer_new_workspace_bytes",
+                                         infer_row_caps(query.deg_host, self.thresholds, ids_host), chunk,
+                                         self.infer_workspace_bytes, _list_capacity)
+        # a grown buffer holds no scores: capacity in powers of two, so a stream of batches grows it a few times at most
+        if whole_set_buffers(inf, self.dev, "new_s0", g.n_nodes + nq, g.n_nodes + (1 << max(nq - 1, 255).bit_length())):
             inf["new_s0_version"] = None
         score_base = not (reuse_scores and inf["new_s0_version"] == self._param_version)
         self._new_scored_base = score_base          # (whether the last infer_new ran the table pass: tests, scripts)
         _lib.check(lib.pcg_infer_new(g.desc_ref(), query.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk, _p(inf["new_s0"]),
-                                     1 if score_base else 0, self._thr, _p(inf["new_ws"]), cap, _p(logits), _p(center),
+                                     1 if score_base else 0, self._thr, _p(ws), cap, _p(logits), _p(center),
                                      _p(inf["status"]), self._stream()), "pcg_infer_new")
         # (the table pass is enqueued before anything that could overflow: the scores are valid whatever the status says)
         inf["new_s0_version"] = self._param_version

@@ -1,5 +1,5 @@
 """CPU checks of FusedPCGNN.infer's host-side planner: per-id list capacities (the exact pcg_sel_capacity_row sums of a test-mode
-selection) and chunk bounds."""
+selection), chunk bounds and the ids every whole-set call accepts."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -48,3 +48,34 @@ def test_default_chunk_keeps_the_workspace_within_its_bound():
     assert 16384 <= c < 100_000 and ws(c, 10 * c) <= 3_000_000
     assert default_infer_chunk(caps, ws, 10) == 16384                   # never under 16384 rows
     assert default_infer_chunk(caps[:1000], ws, 10) == 1000             # (a set smaller than that: one chunk)
+
+
+def test_ids_helper_accepts_tensor_array_list_and_none():
+    import pytest
+    import torch
+    from pcgnn_amd.fused import whole_set_ids
+    dev, rows = torch.device("cpu"), 40
+    want = [7, 7, 0, 39, 3, 1]
+    got = [whole_set_ids(ids, rows, dev, "infer: ids")
+           for ids in (torch.tensor(want), torch.tensor(want, dtype=torch.int32), np.array(want), np.array([want], np.int16), want)]
+    for host, on_dev, n in got:
+        assert n == len(want) and host.dtype == np.int64 and host.tolist() == want
+        assert on_dev.dtype == torch.int32 and on_dev.device == dev and on_dev.tolist() == want
+    # None: every row, no host copy; a cached arange of the right length is handed back as it is
+    host, on_dev, n = whole_set_ids(None, rows, dev, "infer: ids")
+    assert host is None and n == rows and on_dev.dtype == torch.int32 and on_dev.tolist() == list(range(rows))
+    assert whole_set_ids(None, rows, dev, "infer: ids", all_ids=on_dev)[1] is on_dev
+    assert whole_set_ids(None, rows + 1, dev, "infer: ids", all_ids=on_dev)[1].tolist() == list(range(rows + 1))
+    for empty in ([], np.zeros(0, np.int64), torch.zeros(0, dtype=torch.int64)):
+        host, on_dev, n = whole_set_ids(empty, rows, dev, "infer: ids")
+        assert n == 0 and host.size == 0 and on_dev.numel() == 0
+    # the range check: the messages of infer, chosen, infer_new and the partitioned infer
+    for bad in (-1, rows):
+        with pytest.raises(ValueError, match=r"^infer: ids outside 0 \.\. 39$"):
+            whole_set_ids([1, bad], rows, dev, "infer: ids")
+        with pytest.raises(ValueError, match=r"^chosen: ids outside 0 \.\. 39$"):
+            whole_set_ids(np.array([bad]), rows, dev, "chosen: ids")
+        with pytest.raises(ValueError, match=r"^infer_new: ids outside 0 \.\. 39 \(query-local rows\)$"):
+            whole_set_ids(torch.tensor([bad]), rows, dev, "infer_new: ids", " (query-local rows)")
+        with pytest.raises(ValueError, match=r"^infer: ids_local outside 0 \.\. 39$"):
+            whole_set_ids([bad], rows, dev, "infer: ids_local")
