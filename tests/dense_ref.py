@@ -1,0 +1,215 @@
+"""A plain-torch CPU reference of the dense tail of a PC-GNN training step, and the seeded synthetic cases the gradient tests
+run it on (tests/test_dense_ref_host.py, tests/test_gpu_grad_f64.py).
+
+The function is ``OraclePCGNN.forward`` / ``.loss`` (oracle/pcgnn_oracle.py) with the selection taken as an input: mean of the
+chosen rows, ``relu(cat(self, agg_r) @ W_r)`` per relation, ``relu(cat(self, h_1 .. h_R) @ W_inter)``, gnn logits, label-aware
+logits from ``X[ids]``, ``CE(gnn) + lambda_1 * CE(label)`` (mean reduction), autograd for every parameter.  ``dtype`` picks the
+precision of every operation: float64 is the reference, float32 - the same code - the yardstick the kernels' error is
+measured by.
+
+ReLU kinks: a pre-activation within rounding of zero may take another mask in f32 than in f64, and the gradient jumps with it.
+``ambiguous`` marks such entries (|pre_f64| < 16 * max|pre_f32 - pre_f64|), ``resolve_masks`` takes the device's own mask for
+them and the f64 sign for every other entry, and a reference run with ``masks`` computes ``pre * mask`` with the mask held
+constant instead of ``relu(pre)``.
+"""
+import numpy as np
+import torch
+import torch.nn.functional as Fn
+
+from tests.util import PARAM_KEYS, synth_graph
+
+AMBIGUOUS_CAP = 1e-4        # at most this share of a case's activations may be ambiguous (a condition, not a measurement)
+MARGIN, FLOOR = 8.0, 2.0 ** -20
+
+
+def sets_to_index(sets):
+    """sets[r][b] (Python sets of node ids) -> a list of per-relation tuples (rows int64, cols int64, counts float64 [B])"""
+    if len(sets) and isinstance(sets[0], tuple):         # (an index already)
+        return sets
+    out = []
+    for rel in sets:
+        cnt = np.array([len(s) for s in rel], dtype=np.int64)
+        rows = np.repeat(np.arange(len(rel), dtype=np.int64), cnt)
+        cols = np.fromiter((j for s in rel for j in sorted(s)), dtype=np.int64, count=int(cnt.sum()))
+        out.append((torch.from_numpy(rows), torch.from_numpy(cols), torch.from_numpy(cnt.astype(np.float64))))
+    return out
+
+
+def dense_ref(X, ids, labels, sets, params, lambda_1, dtype=torch.float64, masks=None, row_weight=None):
+    """X [n, F]; ids / labels [B]; sets: sets[r][b] or sets_to_index(sets); params: the reference's state-dict names -> tensors;
+    masks: None (F.relu) or R + 1 tensors [B, E] (h_1 .. h_R, combined) of 0 / 1 - the masked ReLU ``pre * mask``.
+    row_weight [B]: every row's loss term times its weight before the sum / B (None: ones - the mean; the host tests drop or
+    double a row with it).  Returns dict(loss, logits [B, 2], center [B, 2], pre: R + 1 tensors [B, E], grads: name -> tensor),
+    everything in ``dtype``, detached."""
+    X = torch.as_tensor(X).to(dtype)
+    ids = torch.as_tensor(np.asarray(ids)).long()
+    y = torch.as_tensor(np.asarray(labels)).long()
+    B, R = ids.numel(), len(sets)
+    index = sets_to_index(sets)
+    p = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in params.items()}
+    self_feats = X[ids]
+    act = (lambda r, pre: Fn.relu(pre)) if masks is None else (lambda r, pre: pre * masks[r].to(dtype))
+    feats, pre = [self_feats], []
+    for r, (rows, cols, cnt) in enumerate(index):
+        agg = torch.zeros(B, X.shape[1], dtype=dtype).index_add_(0, rows, X[cols]) / cnt.to(dtype)[:, None]
+        pre.append(torch.cat((self_feats, agg), dim=1).mm(p[f"inter1.intra_agg{r + 1}.weight"]))
+        feats.append(act(r, pre[-1]))
+    pre.append(torch.cat(feats, dim=1).mm(p["inter1.weight"]))
+    comb = act(R, pre[-1])
+    logits = comb.mm(p["weight"].t())
+    center = Fn.linear(self_feats, p["inter1.label_clf.weight"], p["inter1.label_clf.bias"])
+    rows_loss = Fn.cross_entropy(logits, y, reduction="none") + lambda_1 * Fn.cross_entropy(center, y, reduction="none")
+    if row_weight is not None:
+        rows_loss = rows_loss * torch.as_tensor(row_weight).to(dtype)
+    loss = rows_loss.sum() / B
+    names = list(p)
+    grads = torch.autograd.grad(loss, [p[k] for k in names])
+    return dict(loss=loss.detach(), logits=logits.detach(), center=center.detach(), pre=[t.detach() for t in pre],
+                grads={k: g.detach() for k, g in zip(names, grads)})
+
+
+def ambiguous(pre64, pre32):
+    """(tau, per-activation bool tensors, share of the case's activations): |pre_f64| < tau = 16 * max|pre_f32 - pre_f64|"""
+    tau = 16.0 * max(float((a.double() - b).abs().max()) for a, b in zip(pre32, pre64))
+    amb = [b.abs() < tau for b in pre64]
+    return tau, amb, sum(int(a.sum()) for a in amb) / sum(a.numel() for a in amb)
+
+
+def resolve_masks(pre64, amb, dev_masks=None):
+    """The masks a reference run uses: the f64 sign, and the device's own mask where the entry is ambiguous (dev_masks None -
+    no device at hand -: the f64 sign there too).  Returns (masks, number of NON-ambiguous entries where the device's mask is
+    not the f64 sign - which the caller asserts to be zero)."""
+    masks, wrong = [], 0
+    for r, p64 in enumerate(pre64):
+        sign = p64 > 0
+        if dev_masks is None:
+            masks.append(sign.double())
+            continue
+        d = dev_masks[r].bool()
+        wrong += int(((d != sign) & ~amb[r]).sum())
+        masks.append(torch.where(amb[r], d, sign).double())
+    return masks, wrong
+
+
+def device_masks(acts, F, E, R, B):
+    """``h > 0`` for h_1 .. h_R and the combined embeddings, from an engine's ``acts`` buffer after an acts-mode dense launch
+    (layout: the top of csrc/wgrad.h - a batch row per column): R + 1 bool tensors [B, E] on the CPU."""
+    a = acts.detach().cpu()
+    r_comb = (F + R * E) + R * F + E + R * E
+    out = [(a[F + r * E:F + (r + 1) * E, :B] > 0).t().contiguous() for r in range(R)]
+    out.append((a[r_comb:r_comb + E, :B] > 0).t().contiguous())
+    return out
+
+
+def rel_err(x, ref):
+    """max|x - ref| / max|ref| (float64 arithmetic)"""
+    x, ref = torch.as_tensor(x).detach().cpu().double(), torch.as_tensor(ref).double()
+    return float((x - ref).abs().max()) / float(ref.abs().max())
+
+
+def tolerance(e_f32):
+    """what a kernel's error may be where the same code in float32 on the CPU has error e_f32 (both by rel_err against float64):
+    the kernels and torch add the same terms in different orders, so a small multiple; the floor - a few ulps of the largest
+    element - covers cases where the float32 run happens to be exact (B = 1)"""
+    return MARGIN * e_f32 + FLOOR
+
+
+def recover_grad(m_new, theta_old, beta1, wd, m_old=None):
+    """The gradient one Adam step took, from its first moment: m_new = beta1 * m_old + (1 - beta1) * (g + wd * theta_old)
+    (torch.optim.Adam, coupled weight decay; m_old None: zero).  float64 arithmetic on the given (float32) values."""
+    m_new, theta_old = m_new.detach().cpu().double(), theta_old.detach().cpu().double()
+    if m_old is not None:
+        m_new = m_new - beta1 * m_old.detach().cpu().double()
+    return m_new / (1.0 - beta1) - wd * theta_old
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the cases: one seeded graph and parameter set per (F, E, R); batches drawn with replacement (duplicate centres occur)
+# ---------------------------------------------------------------------------------------------------------------------------
+BATCHES = [2049, 2048, 1025, 1024, 1023, 65, 64, 63, 17, 16, 15, 1, 17]       # descending; then 17 once more, after B = 1
+BATCHES_SHORT = [2049, 1025, 65, 17, 1, 17]
+# (F, E, R) -> (kernel, batch sizes, seed of the case: one at which every batch keeps AMBIGUOUS_CAP)
+SHAPES = {
+    (32, 64, 3): ("dense_step_kernel<true, 32, 64, 3>", BATCHES, 11),
+    (25, 64, 3): ("dense_step_kernel<true, 25, 64, 3>", BATCHES, 11),
+    (32, 128, 3): ("dense_step_kernel<false, 32, 128, 3>", BATCHES, 11),
+    (25, 128, 3): ("dense_step_kernel<false, 25, 128, 3>", BATCHES, 11),
+    (10, 16, 1): ("dense_step_kernel<false, 0, 0, 0>", BATCHES_SHORT, 11),
+    (16, 48, 5): ("dense_step_kernel<false, 0, 0, 0>", BATCHES_SHORT, 11),
+    (24, 16, 5): ("dense_step_kernel<true, 0, 0, 0>", BATCHES_SHORT, 12),
+}
+REL_DEG = {1: (12,), 3: (4, 12, 3), 5: (4, 12, 3, 6, 2)}
+MAX_BATCH = 2049
+
+
+def dense_wlds(F, E, R):
+    """The dense kernel's rule for staging the weight matrices in LDS (dense_wlds / dense_smem_bytes in csrc/dense.h),
+    restated: which of the two run-time-shape kernels a shape gets."""
+    kpad, tb, waves = 16, 16, 16
+    k1p, k2p = (2 * F + kpad - 1) // kpad * kpad, (F + R * E + kpad - 1) // kpad * kpad
+    ntile_e = E // 16
+    kparts = waves // ntile_e if ntile_e <= waves else 1
+    floats = R * tb * (k1p + 1) + tb * (k2p + 1) + (2 + R) * tb * (E + 1) + 4 * tb + 2 * E + 2 * F + 4 + 4
+    floats += (k2p + R * k1p) * (E + 4)
+    return 4 * floats <= 160 * 1024 and (waves * 64) % (E // 4) == 0 and kparts * tb * E <= R * k1p * (E + 4)
+
+
+class GradCase:
+    """The fields ``tests.util.build_model`` reads (n, f, emb, R, alpha, train_pos, X, params()) over a ``synth_graph`` of 2000
+    nodes, ~15 % positives, the train positives those among the first half of the nodes; seeded Xavier-scale parameters."""
+    lr, wd, rho, alpha = 0.01, 0.001, 0.5, 2.0
+    betas = (0.9, 0.999)
+
+    def __init__(self, F, E, R, seed=11):
+        self.n, self.f, self.emb, self.R, self.seed = 2000, F, E, R, seed
+        self.X, self.labels, self.csr = synth_graph(seed, self.n, F, REL_DEG[R], 0.15)
+        self.train_pos = [int(v) for v in range(self.n // 2) if self.labels[v] == 1]
+        gen = torch.Generator().manual_seed(seed + 1000 * F + 10 * E + R)
+        shapes = {"weight": (2, E), "inter1.weight": (F + R * E, E), "inter1.label_clf.weight": (2, F), "inter1.label_clf.bias": (2,)}
+        shapes.update({f"inter1.intra_agg{r + 1}.weight": (2 * F, E) for r in range(R)})
+        self._params = {}
+        for k in PARAM_KEYS(R):
+            shp = shapes[k]
+            # xavier_uniform_'s bound for the matrices, nn.Linear's 1 / sqrt(fan_in) for the label classifier
+            bound = (6.0 / (shp[0] + shp[1])) ** 0.5 if "label_clf" not in k else 1.0 / F ** 0.5
+            self._params[k] = ((torch.rand(shp, generator=gen) * 2 - 1) * bound).float()
+
+    @classmethod
+    def of(cls, shape):
+        return cls(*shape, seed=SHAPES[shape][2])
+
+    def params(self):
+        return {k: v.clone() for k, v in self._params.items()}
+
+    def batch(self, B, salt=0):
+        """(ids, labels) int64 numpy, drawn with replacement"""
+        rs = np.random.RandomState(self.seed * 100003 + 31 * B + salt)
+        ids = rs.randint(0, self.n, size=B)
+        return ids, self.labels[ids]
+
+    def host_sets(self, ids, labels, params=None):
+        """the oracle's training-mode selection for a batch (CPU tests: no device to take the sets from)"""
+        from oracle import pcgnn_oracle as O
+        p = self._params if params is None else params
+        X = torch.from_numpy(self.X)
+        s0 = Fn.linear(X, p["inter1.label_clf.weight"].float(), p["inter1.label_clf.bias"].float())[:, 0]
+        pos = torch.as_tensor(self.train_pos).long()
+        sets = []
+        for indptr, idx in self.csr:
+            lists = [idx[indptr[v]:indptr[v + 1]].tolist() for v in ids]
+            nsc = [s0[torch.as_tensor(l).long()] for l in lists]
+            sets.append(O.choose_sets(s0[torch.as_tensor(ids).long()], labels.tolist(), lists, nsc, self.train_pos, s0[pos],
+                                      0.5, self.rho, True))
+        return sets
+
+
+def reference_pair(case, ids, labels, sets, params=None, dev_masks=None):
+    """The float64 reference and its float32 yardstick for one batch, with the ReLU-kink rule applied.  Returns
+    (ref64, ref32, share of ambiguous activations, non-ambiguous entries where the device's mask is not the f64 sign)."""
+    params = case.params() if params is None else params
+    index = sets_to_index(sets)
+    args = (case.X, ids, labels, index, params, case.alpha)
+    plain64, plain32 = dense_ref(*args, dtype=torch.float64), dense_ref(*args, dtype=torch.float32)
+    _, amb, share = ambiguous(plain64["pre"], plain32["pre"])
+    masks, wrong = resolve_masks(plain64["pre"], amb, dev_masks)
+    return dense_ref(*args, dtype=torch.float64, masks=masks), dense_ref(*args, dtype=torch.float32, masks=masks), share, wrong

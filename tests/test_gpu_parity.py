@@ -12,7 +12,8 @@ import pytest
 import torch
 
 from oracle import pcgnn_oracle as O
-from tests.util import GOLDEN, PARAM_KEYS, GoldenCase, csr_to_adj, synth_graph
+from tests import dense_ref as D
+from tests.util import GOLDEN, PARAM_KEYS, GoldenCase, build_model, csr_to_adj, synth_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -39,18 +40,6 @@ def dev():
 
 def graph_of(P, c):
     return P.DeviceGraph(c.X, c.csr, c.train_pos, dev())
-
-
-def build_model(P, c, rho, graph=None):
-    feats = torch.nn.Embedding(c.n, c.f)
-    feats.weight = torch.nn.Parameter(torch.from_numpy(c.X.copy()), requires_grad=False)
-    intras = [P.IntraAgg(feats, c.f, c.emb, c.train_pos, rho, cuda=True) for _ in range(c.R)]
-    inter = P.InterAgg(feats, c.f, c.emb, c.train_pos, graph if graph is not None else c.adj_lists(), intras, cuda=True)
-    model = P.PCALayer(2, inter, c.alpha)
-    sd = model.state_dict()
-    for k, v in c.params().items():
-        sd[k].copy_(v)
-    return model.cuda()
 
 
 # ---------------------------------------------------------------------------
@@ -568,11 +557,18 @@ def test_fused_forward_grads_adam_golden(P, case):
     # gradients of every parameter
     # (both ways the engine forms them: the training step's - transposed activations, weight gradients as GEMMs over the batch -
     #  and the data-parallel paths' per-tile slabs summed in tile order)
+    by_via = {}
     for via in ("slabs", "acts"):
-        grads = fz.gradients(ids, lab, via=via)
+        grads = by_via[via] = fz.gradients(ids, lab, via=via)
         assert abs(float(fz.last_loss()) - float(c.z[tag + "_loss"])) < LOGIT_TOL
         for k in PARAM_KEYS(c.R):
             np.testing.assert_allclose(grads[k].cpu().numpy(), c.z[f"{tag}_grad_{k}"], rtol=0, atol=2e-5, err_msg=f"{k} via {via}")
+    # ... and against float64 (tests/dense_ref.py: the golden sets; the engine's own ReLU masks where f32 and f64 may differ)
+    r64, r32, _, wrong = D.reference_pair(c, c.nodes, c.batch_labels, [c.sel(f"{tag}_train", r) for r in range(c.R)],
+                                          dev_masks=D.device_masks(fz.acts, c.f, c.emb, c.R, len(c.nodes)))
+    assert wrong == 0
+    for via, k in [(via, k) for via in by_via for k in PARAM_KEYS(c.R)]:
+        assert D.rel_err(by_via[via][k], r64["grads"][k]) <= D.tolerance(D.rel_err(r32["grads"][k], r64["grads"][k])), f"{k} via {via}"
     # one Adam step: where the reference's own gradient is well away from zero the first update is -lr * g'/(|g'| + eps)
     # with g' = g + wd * p (coupled decay) - elementwise tight there; loose where |g'| ~ the gradient tolerance
     p0 = {k: v.clone() for k, v in c.params().items()}

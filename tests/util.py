@@ -74,3 +74,18 @@ def synth_graph(seed, n, feat_dim, rel_avg_deg, pos_rate, skew=1.5, hub=True):
 def csr_to_adj(csr, n):
     indptr, idx = csr
     return {v: set(idx[indptr[v]:indptr[v + 1]].tolist()) for v in range(n)}
+
+
+def build_model(P, c, rho, graph=None):
+    """PCALayer(InterAgg(IntraAgg x R)) of the package P on the GPU with the case's parameters (c: n, f, emb, R, alpha, X,
+    train_pos, params(); adj_lists() unless a DeviceGraph is given)"""
+    import torch
+    feats = torch.nn.Embedding(c.n, c.f)
+    feats.weight = torch.nn.Parameter(torch.from_numpy(c.X.copy()), requires_grad=False)
+    intras = [P.IntraAgg(feats, c.f, c.emb, c.train_pos, rho, cuda=True) for _ in range(c.R)]
+    inter = P.InterAgg(feats, c.f, c.emb, c.train_pos, graph if graph is not None else c.adj_lists(), intras, cuda=True)
+    model = P.PCALayer(2, inter, c.alpha)
+    sd = model.state_dict()
+    for k, v in c.params().items():
+        sd[k].copy_(v)
+    return model.cuda()
