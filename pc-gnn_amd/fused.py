@@ -254,6 +254,7 @@ class FusedPCGNN:
         g, dev, lib = self.g, self.dev, self.lib
         if torch.cuda.is_current_stream_capturing():
             raise _lib.PcgnnLibraryError("batch larger than max_batch inside a graph capture: allocate before capturing")
+        self._drop_prepared()                        # (an epoch prepared ahead goes with its buffers)
         # every captured graph holds raw pointers into the buffers replaced below
         self._graphs.clear()
         self._ep_graphs.clear()
@@ -777,7 +778,13 @@ class FusedPCGNN:
         sampler; ``plan_staged()`` must follow before any of the staged steps runs).  Several epochs staged together are sampled
         and planned by ONE launch each - the sampler's and the plan's latency chains are paid once per n_epochs epochs - and are
         walked as one sequence of batches 0 .. n_epochs * ceil(n / batch_size) - 1 (every epoch's last batch may be the shorter
-        one).  Returns the CURRENT set's (ids, labels), n_epochs * n long."""
+        one).  Returns the CURRENT set's (ids, labels), n_epochs * n long.
+        Another (n, batch_size, n_epochs) than the last call's DROPS a set that ``epoch_run(prefetch=...)`` has prepared: its ids
+        and plans are laid out for the old shape.  The call waits for whatever is still preparing it, the set counts as not
+        ready, and the next epoch is sampled and planned anew, at the new shape.  The epoch numbers the dropped set had consumed
+        are SKIPPED, not drawn again: the sampler's device counter only ever moves forward (it was moved on when the set was
+        planned), so the next epoch sampled is the one after the dropped set's last.  Every epoch number still names
+        independent draws of the same distribution, and no number is trained twice."""
         if batch_size > self.maxB:
             self.flush()
             self._alloc(batch_size)
@@ -788,6 +795,7 @@ class FusedPCGNN:
         if sets is None or sets[0]["ids"].numel() < total or self._ep_stride != stride or sets[0]["plans"].numel() < nb * stride:
             if torch.cuda.is_current_stream_capturing():
                 raise _lib.PcgnnLibraryError("stage_epoch with a new shape inside a graph capture")
+            self._drop_prepared()                    # (before the old buffers go: nothing may still be writing them)
             self._ep_sets = [dict(ids=torch.zeros(total, dtype=torch.int32, device=self.dev),
                                   lab=torch.zeros(total, dtype=torch.int32, device=self.dev),
                                   plans=torch.zeros(nb * stride, dtype=torch.uint8, device=self.dev),
@@ -803,6 +811,9 @@ class FusedPCGNN:
             # there - zero the slots so that no stale word can pass for a published total
             if torch.cuda.is_current_stream_capturing():
                 raise _lib.PcgnnLibraryError("stage_epoch with a new epoch size inside a graph capture")
+            # a set prepared ahead holds the old shape's ids and is about to lose its plans: it is dropped (its epoch numbers are
+            # skipped), after whatever is still writing it has finished
+            self._drop_prepared()
             for st in self._ep_sets:
                 st["plans"].zero_()
             self._ep_graphs.clear()
@@ -811,6 +822,18 @@ class FusedPCGNN:
         # batch j of the staged sequence: (first pick, size)
         self._ep_batches = [(e * n + b * batch_size, min(batch_size, n - b * batch_size)) for e in range(n_epochs) for b in range(nb_e)]
         return self._ep_ids[:total], self._ep_lab[:total]
+
+    def _drop_prepared(self):
+        """Forget a set that ``epoch_run(prefetch=...)`` has sampled and planned ahead - its buffers are about to be rewritten or
+        replaced.  The current stream first waits for the side stream's sampler and plan launches (prefetch="stream"): nothing
+        may still be writing the set.  The epoch numbers it had consumed are skipped (``stage_epoch``)."""
+        if not torch.cuda.is_current_stream_capturing():      # (a capturing stream cannot wait for work outside its capture)
+            main = torch.cuda.current_stream(self.dev)
+            if getattr(self, "_ev_ready", None) is not None:
+                main.wait_event(self._ev_ready)
+            if getattr(self, "_side", None) is not None:
+                main.wait_stream(self._side)
+        self._cur_ready, self._ev_ready = False, None
 
     def take_prefetched(self) -> bool:
         """True if the current set already holds a sampled and planned epoch that no step has used yet (left by
@@ -852,9 +875,9 @@ class FusedPCGNN:
         one graph launch - no copies, no indexing kernels (model_handler.py:142-148 slices a Python list here)."""
         n = ids.numel()
         ep_ids, ep_lab = self.stage_epoch(n, batch_size)
+        self._drop_prepared()                        # (the ids go into the current set: an epoch prepared ahead there is lost)
         ep_ids.copy_(ids)
         ep_lab.copy_(labels)
-        self._cur_ready = False
         self.plan_staged()
 
     def epoch_step(self, b: int, defer: bool = False):
@@ -938,6 +961,11 @@ class FusedPCGNN:
         prefetch=True (needs ``sample``): the sampler and the plans of the NEXT epoch run on a parallel branch of this epoch's
         graph, into the other buffer set; afterwards that set is the current one and ready (``take_prefetched``).  The first
         such call - or one after the ready set was used up by other calls - samples its own epoch first.
+        A prepared set is DROPPED by whatever rewrites or replaces its buffers before a step has used it: ``stage_epoch`` with
+        another (n, batch_size, n_epochs), ``begin_epoch`` (its ids go into that set), a batch above max_batch anywhere (every
+        buffer is re-allocated).  The epoch numbers the dropped set had consumed are skipped - ``bump_counter`` is never moved
+        back - and the next epoch is sampled and planned anew.  Calls that leave the epoch buffers alone (``train_step`` within
+        max_batch, ``predict``, ``infer``, ``chosen``, ``flush``) leave the prepared set ready.
         prefetch="stream": the same division of labour without a fork inside the graph: the sampler and plan launches of the next
         epoch are enqueued - by the host, behind this epoch's graph launch - on a second stream, where they run beside this
         epoch's kernels; the only cross-stream waits are two events per epoch (the other buffer set is free / is ready).
@@ -956,6 +984,12 @@ class FusedPCGNN:
         primed = (prefetch or on_stream) and self._cur_ready
         key = ("epoch", cur, self._ep_shape, n_steps, sample is not None, None if bump_counter is None else bump_counter.data_ptr(),
                flush, prefetch, primed, on_stream, first_step)
+        main = torch.cuda.current_stream(self.dev)
+        if primed and getattr(self, "_ev_ready", None) is not None:
+            # the side stream has sampled and planned this set: wait here, in front of a capture too - its warm-up plans the
+            # set again and runs the steps over it
+            main.wait_event(self._ev_ready)
+            self._ev_ready = None
         gr = self._ep_graphs.get(key)
         if gr is None:
             st = self._ep_sets[cur]
@@ -1006,10 +1040,6 @@ class FusedPCGNN:
                 self._enqueue_refresh(self._ep_touch(first_step, cur))
         elif not self.touched_on and not self._fresh:
             self._enqueue_refresh()
-        main = torch.cuda.current_stream(self.dev)
-        if primed and getattr(self, "_ev_ready", None) is not None:
-            main.wait_event(self._ev_ready)          # the side stream has sampled and planned this set
-            self._ev_ready = None
         gr.replay()
         self._fresh = (not self.touched_on) or self._ep_next_touch(n_steps - 1, cur) is not None
         if on_stream:
