@@ -686,7 +686,10 @@ int pcg_wgrad(const float *acts, int32_t act_ld, int32_t B, int32_t feat_dim, in
  *   table    uint32 [2 * table_slots], table_slots = pcg_halo_table_slots(halo_cap)
  *   counts   uint32 [131], zeroed ONCE by the caller; after a collect [0, world) = unique remote ids per owner, [128] =
  *            overflow bits (1: table full, 2: more unique remote ids than halo_cap / than an owner's pitch, 4: a lookup
- *            missed; STICKY across calls - the caller clears them after looking, so one look per epoch sees every step),
+ *            missed; STICKY across calls - the caller clears them after looking, so one look per epoch sees every step.
+ *            Bit 1 must be CLEARED before the next pcg_halo_collect: while it is set the collect stops walking at once, so
+ *            a window collected behind a table-full report - however small - comes out EMPTY: request list all -1, counts
+ *            zero, every remote id a hole at look-up),
  *            [129] / [130] = the largest number of unique remote ids a window needed so far / needed from one owner
  *   uniq     int32 [halo_cap]: the request list - the unique remote ids grouped by owner in rank order; it doubles as the
  *            halo rows' id column (row halo_base + i holds node uniq[i], -1 = unused)
