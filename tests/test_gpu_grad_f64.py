@@ -38,6 +38,7 @@ import pytest
 import torch
 
 from tests import dense_ref as D
+from tests.grad_check import Tally, check_first_moment
 from tests.util import PARAM_KEYS, build_model
 
 pytestmark = pytest.mark.gpu
@@ -64,32 +65,6 @@ def engine(P, c):
 
 def on_dev(ids, lab):
     return torch.from_numpy(ids.astype(np.int32)).to(dev()), torch.from_numpy(lab.astype(np.int32)).to(dev())
-
-
-class Tally:
-    """every figure is printed before anything is asserted; the misses are asserted together at the end of the test"""
-
-    def __init__(self, tag):
-        self.tag, self.misses, self.ratio, self.of_bound = tag, [], 0.0, 0.0
-
-    def check(self, what, got, ref64, ref32):
-        e_k, e_32 = D.rel_err(got, ref64), D.rel_err(ref32, ref64)
-        tol = D.tolerance(e_32)
-        if e_32 >= 2.0 ** -24:
-            self.ratio = max(self.ratio, e_k / e_32)
-        self.of_bound = max(self.of_bound, e_k / tol)
-        print(f"{self.tag} {what}: e_kernel {e_k:.3e}  e_f32 {e_32:.3e}  bound {tol:.3e}" + ("" if e_k <= tol else "  MISS"))
-        if not e_k <= tol:
-            self.misses.append((what, e_k, e_32, tol))
-
-    def done(self):
-        print(f"RATIO {self.tag}: ratio {self.ratio:.2f}  of bound {self.of_bound:.2f}")
-        assert not self.misses, self.misses
-
-
-def by_name(fz, flat):
-    """a flat [n_params] tensor in theta's layout -> per-parameter tensors under the state-dict names"""
-    return {k: flat[v.storage_offset():v.storage_offset() + v.numel()].view(v.shape) for k, v in fz.views.items()}
 
 
 def reference(c, fz, ids, lab, sets, B, params=None):
@@ -126,31 +101,6 @@ def test_gradients_against_float64(P, shape):
             tally.check(f"B={B} via={via} label-aware logits", center, r64["center"], r32["center"])
     assert int(fz.step_counter.item()) == 0
     tally.done()
-
-
-def adam_first_moment_f32(theta_old, grad32, c, state=None):
-    """float32 torch.optim.Adam on the float32 reference's gradient: the first moment after the step (state: (m, v) of one
-    step taken before it)"""
-    p = torch.nn.Parameter(theta_old.detach().cpu().float().clone())
-    p.grad = grad32.float().clone()
-    opt = torch.optim.Adam([p], lr=c.lr, weight_decay=c.wd, betas=c.betas)
-    if state is not None:
-        opt.state[p] = {"step": torch.tensor(1.0), "exp_avg": state[0].detach().cpu().clone(), "exp_avg_sq": state[1].detach().cpu().clone()}
-    opt.step()
-    return opt.state[p]["exp_avg"]
-
-
-def check_first_moment(tally, c, fz, what, m_new, theta_old, r64, r32, state=None):
-    """the gradient the step took, recovered from Adam's first moment, per parameter; the yardstick goes the same way"""
-    th, mn = by_name(fz, theta_old), by_name(fz, m_new)
-    m_old = None if state is None else by_name(fz, state[0])
-    v_old = None if state is None else by_name(fz, state[1])
-    for k in PARAM_KEYS(c.R):
-        mo = None if state is None else m_old[k]
-        g_dev = D.recover_grad(mn[k], th[k], c.betas[0], c.wd, mo)
-        m32 = adam_first_moment_f32(th[k], r32["grads"][k], c, None if state is None else (m_old[k], v_old[k]))
-        g_32 = D.recover_grad(m32, th[k], c.betas[0], c.wd, mo)
-        tally.check(f"{what} grad {k}", g_dev, r64["grads"][k], g_32)
 
 
 @pytest.mark.parametrize("B", [17, 1024, 1025, 2049])
