@@ -54,7 +54,8 @@ enum {
                                  the mean): its surplus keys were dropped - minority picks of that step may be wrong */
     PCG_ST_EVAL_INPUT = 16,   /* pcg_eval_counts met a label outside {0, 1} or a NaN probability: its counts describe no valid input */
     PCG_ST_RANK_MISMATCH = 32 /* pcg_rank_lists / pcg_chosen_set: a row's kept count on the device is not the extent the caller's
-                                 out_begin gives it (or its list region / extent leaves its array); nothing was written for that row */
+                                 out_begin gives it (or its list region / extent leaves its array); nothing was written for that row.
+                                 pcg_rank_minority: a row's extent is negative, above n_pos or leaves its array; not written */
 };
 
 enum { PCG_NORM_COUNT = 0, PCG_NORM_SQRT_COUNT = 1 };
@@ -75,7 +76,7 @@ typedef struct pcg_graph_desc {
 
 /* library / build identification: "pcgnn_hip gfx950 <abi>" (host pointer, static) */
 const char *pcg_version(void);
-int pcg_abi_version(void);   /* 9 (added: pcg_rank_lists, pcg_chosen_set, pcg_chosen_workspace_bytes, PCG_ST_RANK_MISMATCH) */
+int pcg_abi_version(void);   /* 10 (added: pcg_rank_minority) */
 
 /* ---- label-aware scores -------------------------------------------------------
  * Replaces  batch_scores = self.label_clf(self.features(unique_nodes))
@@ -619,6 +620,24 @@ int64_t pcg_chosen_workspace_bytes(const pcg_graph_desc *g, int32_t chunk_rows, 
 int pcg_chosen_set(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *ids, int32_t n, int32_t chunk_rows,
                    float *s0, const double *thresholds, void *workspace, int64_t list_capacity, const int64_t *out_begin,
                    int32_t *out_ids, float *out_dist, uint32_t *status, void *stream);
+/* The minority picks of TRAIN-mode rows, ranked, with their distances (choose_step_neighs' tail, src/layers.py:675-691; the
+ * minority part of FusedPCGNN.chosen(train_flag=True) / ops.choose_ranked(labels=...)).  The extent of row (r, i),
+ * out_begin[r * n + i + 1] - out_begin[r * n + i], IS that row's m = min(int(k * rho), n_pos) - 0 for a negative centre and for
+ * int(k * rho) == 0 (the caller forms it on the host: pcg_sel_capacity_row's minority term).  The row receives the m training
+ * positives nearest to c = center_s0 ? center_s0[i] : s0[nodes[i]] in ascending order of the unique key
+ * (orderable(|c - s_p|) << 32) | p, p = the position in train_pos - torch.sort(stable = True) over train_pos order, and the
+ * select kernel's tie rule: out_ids = train_pos[p], out_dist = fabsf(c - s_p) (one f32 subtract and abs, s_p from the sorted
+ * key's high word: the bits of torch.abs).  A pick that is also a kept neighbour of the row is reported, not removed (the
+ * reference's samp_score_diff keeps it).  pos_keys: what pcg_pos_sort left for the same s0.  A row whose extent is negative,
+ * above n_pos or leaves [0, out_begin[n_rel * n]] sets PCG_ST_RANK_MISMATCH in *status and is not written; a position read from
+ * a key is clamped below n_pos before train_pos is read, a slot is written only below its row's extent.  One ranking per centre
+ * serves every relation (row (r, i) is the prefix of m_r entries).  Two launches (centres of <= 64 candidates: one wave each;
+ * more: a workgroup per 2048 candidates, counted against all of the centre's candidates - quadratic in the candidate count, so
+ * a tie run of thousands is exact, not fast); no workgroup waits for another.  Never synchronises, never allocates, needs no
+ * workspace and no plan; n == 0 or n_pos == 0: nothing is enqueued. */
+int pcg_rank_minority(const pcg_graph_desc *g, const int32_t *nodes, int32_t n, const float *s0, const float *center_s0,
+                      const uint64_t *pos_keys, const int64_t *out_begin, int32_t *out_ids, float *out_dist, uint32_t *status,
+                      void *stream);
 int pcg_step_front_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, float *s0,
                          uint64_t *pos_keys, const int32_t *nodes, const int32_t *labels, int32_t B,
                          const double *thresholds, const double *rho, int32_t add_self, void *workspace,

@@ -23,6 +23,7 @@
 // sets PCG_ST_RANK_MISMATCH and writes nothing; list ids are clamped to the score table for the read (PCG_ST_LIST_ID_RANGE);
 // a slot is clamped to the row's extent.
 // Reference lines replaced: src/layers.py:713-736 (choose_step_test's samp_scores), :630 (IntraAgg.forward's second value).
+// The second half of the file ranks the minority picks of train-mode rows (pcg_rank_minority; :675-691).
 #include "infer.h"
 
 namespace pcg {
@@ -321,9 +322,246 @@ static int launch_rank_lists(const pcg_graph_desc *g, const int32_t *nodes, int3
     return PCG_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The minority picks of train-mode rows, ranked, with their distances (choose_step_neighs' tail, src/layers.py:675-691).
+//
+// A positive centre's picks are the m training positives nearest to its score c: a function of c, m, the sorted train-pos
+// keys and train_pos - nothing of the row, nothing of the selection list (which stores them in window order, without
+// distances, and turns a duplicate of a kept neighbour into a hole).  Row (r, i)'s m is its extent in out_begin; the order
+// is the unique key (orderable(|c - s_p|) << 32) | p, p = position in train_pos: torch.sort(stable) over train_pos order, and
+// select_rows' tie rule (ties at the m-th distance go to the smallest positions).
+//   window      M = max_r m_r.  pc = the first sorted key whose score is >= c.  Left of pc the distances fall with the index,
+//               from pc on they rise (rounding is monotone), so the M nearest are in [pc - M, pc + M) - once each end is
+//               extended over its run of EQUAL distances (bisected): an element outside then has at least M strictly nearer
+//               ones on its own side, whatever its position.  Nothing outside can precede a candidate of rank < M, so a
+//               candidate's slot is the number of smaller candidate keys; the order does not depend on the relation: row
+//               (r, i) is the prefix slot < m_r, one ranking per centre serves every relation.
+//   rank_minor_short   <= 64 candidates: one wave per centre, lane against lane (readlane)
+//   rank_minor_wg      more: work item = (centre, slice of RANK_SLICE candidates), counted against all of the centre's
+//                      candidates tile by tile in LDS (rank_count_tile).  Quadratic in the candidate count: a tie run of
+//                      thousands (constant scores) is exact, not fast.
+// The keys come from an earlier launch: plain loads.  No workgroup waits for another; the only atomic is the OR into the
+// status word.  Every loop is bounded by P.  A row whose extent is negative, above P or leaves [0, out_begin[R * n]) sets
+// PCG_ST_RANK_MISMATCH and is not written; a position read from a key is clamped below P before train_pos is read; a slot is
+// written only below its row's extent.
+struct MinorArgs {
+    const int32_t *nodes;       // [n]
+    int32_t n, n_rel, P;
+    int64_t n_nodes;
+    const float *s0, *center_s0;
+    const uint64_t *keys;       // [P] sorted (orderable(score) << 32 | position in train_pos)
+    const int32_t *train_pos;   // [P]
+    const int64_t *out_begin;   // [n_rel * n + 1]
+    int32_t *out_ids;
+    float *out_dist;
+    uint32_t *status;
+};
+
+struct MinorWin {
+    int lo, N, M;               // candidates = sorted keys [lo, lo + N); M == 0: nothing to do
+    float c;
+};
+
+// row (r, i)'s extent, checked: m (-1: rejected) and where it begins
+__device__ __forceinline__ int minor_extent(const MinorArgs &a, int r, int i, int64_t &obeg) {
+    const int64_t at = (int64_t)r * a.n + i;
+    const int64_t b = a.out_begin[at], e = a.out_begin[at + 1], cap = a.out_begin[(int64_t)a.n_rel * a.n];
+    obeg = b;
+    const bool ok = e >= b && e - b <= (int64_t)a.P && b >= 0 && e <= cap;
+    return ok ? (int)(e - b) : -1;
+}
+
+__device__ __forceinline__ float minor_score(const MinorArgs &a, int x) { return from_orderable((uint32_t)(a.keys[x] >> 32)); }
+
+// the candidate window of centre i (uniform over the wave / workgroup: every lane reads the same words)
+__device__ __forceinline__ MinorWin minor_window(const MinorArgs &a, int i, bool report) {
+    MinorWin w;
+    w.lo = 0; w.N = 0; w.M = 0; w.c = 0.f;
+    bool bad = false;
+    for (int r = 0; r < a.n_rel; ++r) {
+        int64_t obeg;
+        const int m = minor_extent(a, r, i, obeg);
+        bad |= m < 0;
+        w.M = m > w.M ? m : w.M;
+    }
+    if (bad && report && a.status && (threadIdx.x & (PCG_WAVE - 1)) == 0) atomicOr(a.status, (uint32_t)PCG_ST_RANK_MISMATCH);
+    if (w.M == 0) return w;
+    int64_t node = a.nodes[i];
+    node = node < 0 ? 0 : (node >= a.n_nodes ? a.n_nodes - 1 : node);
+    const float c = a.center_s0 ? a.center_s0[i] : a.s0[node];
+    w.c = c;
+    const int P = a.P, M = w.M;
+    int lo = 0, hi = P;
+    while (lo < hi) {                                                      // pc: <= 31 steps
+        const int mid = lo + ((hi - lo) >> 1);
+        if (minor_score(a, mid) < c) lo = mid + 1; else hi = mid;
+    }
+    const int pc = lo;
+    int wa = pc - M > 0 ? pc - M : 0;
+    int wb = (int64_t)pc + M < (int64_t)P ? pc + M : P;
+    if (wa > 0 && wa < pc) {                                               // the run of distances equal to the left end's
+        const float d = fabsf(c - minor_score(a, wa));
+        lo = 0; hi = wa;
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (fabsf(c - minor_score(a, mid)) > d) lo = mid + 1; else hi = mid;
+        }
+        wa = lo;
+    }
+    if (wb < P && wb > pc) {                                               // ... and to the right end's
+        const float d = fabsf(c - minor_score(a, wb - 1));
+        lo = wb; hi = P;
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (fabsf(c - minor_score(a, mid)) <= d) lo = mid + 1; else hi = mid;
+        }
+        wb = lo;
+    }
+    w.lo = wa;
+    w.N = wb - wa;
+    return w;
+}
+
+// candidate t of a window: its ranking key, its id and its distance
+__device__ __forceinline__ uint64_t minor_key(const MinorArgs &a, const MinorWin &w, int t, bool valid, int32_t &id, float &dist) {
+    const uint64_t k = a.keys[w.lo + (valid ? t : 0)];
+    uint32_t p = (uint32_t)k;
+    dist = fabsf(w.c - from_orderable((uint32_t)(k >> 32)));
+    const uint64_t key = valid ? ((uint64_t)orderable(dist) << 32) | p : ~0ull;
+    p = p < (uint32_t)a.P ? p : (uint32_t)a.P - 1;
+    id = a.train_pos[p];
+    return key;
+}
+
+// one centre per wave, wave-strided; reports the rejected extents of EVERY centre (rank_minor_wg does not)
+__global__ void __launch_bounds__(RANK_THREADS) rank_minor_short(const MinorArgs a) {
+    const int lane = lane_id();
+    const int n_waves = (int)gridDim.x * (RANK_THREADS / PCG_WAVE);
+    const int wave = (int)blockIdx.x * (RANK_THREADS / PCG_WAVE) + ((int)threadIdx.x >> 6);
+    for (int iw = wave; iw < a.n; iw += n_waves) {
+        const int i = __builtin_amdgcn_readfirstlane(iw);
+        const MinorWin w = minor_window(a, i, true);
+        if (w.M == 0 || w.N > PCG_WAVE) continue;                          // (more candidates: rank_minor_wg)
+        const bool have = lane < w.N;
+        int32_t id;
+        float dist;
+        const uint64_t mine = minor_key(a, w, lane, have, id, dist);
+        const uint32_t mh = (uint32_t)(mine >> 32), ml = (uint32_t)mine;
+        int slot = 0;
+        for (int j = 0; j < w.N; ++j) {                                    // N is wave-uniform
+            const uint32_t oh = (uint32_t)__builtin_amdgcn_readlane((int)mh, j), ol = (uint32_t)__builtin_amdgcn_readlane((int)ml, j);
+            slot += (oh < mh) || (oh == mh && ol < ml);
+        }
+        for (int r = 0; r < a.n_rel; ++r) {
+            int64_t obeg;
+            const int m = minor_extent(a, r, i, obeg);
+            if (have && slot < m) {
+                a.out_ids[obeg + slot] = id;
+                a.out_dist[obeg + slot] = dist;
+            }
+        }
+    }
+}
+
+// centres of more than 64 candidates: blockIdx.x strides over the centres, blockIdx.y over a centre's slices of RANK_SLICE
+__global__ void __launch_bounds__(RANK_THREADS) rank_minor_wg(const MinorArgs a) {
+    __shared__ uint64_t tile[RANK_SLICE];
+    const int tid = (int)threadIdx.x;
+    for (int i = (int)blockIdx.x; i < a.n; i += (int)gridDim.x) {
+        const MinorWin w = minor_window(a, i, false);
+        const int n = w.N;
+        if (w.M == 0 || n <= PCG_WAVE) continue;                           // (rank_minor_short)
+        for (int64_t base64 = (int64_t)blockIdx.y * RANK_SLICE; base64 < n; base64 += (int64_t)gridDim.y * RANK_SLICE) {
+            const int base = (int)base64;
+            int32_t id[RANK_KPT];
+            float dist[RANK_KPT];
+            uint64_t key[RANK_KPT];
+            int below[RANK_KPT];
+#pragma unroll
+            for (int x = 0; x < RANK_KPT; ++x) {
+                const int t = base + x * RANK_THREADS + tid;
+                key[x] = minor_key(a, w, t, t < n, id[x], dist[x]);
+                below[x] = 0;
+            }
+            const int mine = n - base < RANK_SLICE ? n - base : RANK_SLICE;          // entries of this slice
+            const int nu = (mine + RANK_THREADS - 1) / RANK_THREADS;                 // key[x], x >= nu: no thread has one
+            for (int t0 = 0; t0 < n; t0 += RANK_SLICE) {
+                __syncthreads();                                                     // (the tile before: its reads)
+                if (t0 == base) {
+#pragma unroll
+                    for (int x = 0; x < RANK_KPT; ++x) tile[x * RANK_THREADS + tid] = key[x];
+                } else {
+#pragma unroll
+                    for (int x = 0; x < RANK_KPT; ++x) {
+                        const int t = t0 + x * RANK_THREADS + tid;
+                        int32_t tid_id;
+                        float td;
+                        tile[x * RANK_THREADS + tid] = minor_key(a, w, t, t < n, tid_id, td);
+                    }
+                }
+                __syncthreads();
+                const int tn = n - t0 < RANK_SLICE ? n - t0 : RANK_SLICE;
+                if (nu <= 1) rank_count_tile<1>(tile, tn, key, below);
+                else if (nu <= 2) rank_count_tile<2>(tile, tn, key, below);
+                else if (nu <= 4) rank_count_tile<4>(tile, tn, key, below);
+                else rank_count_tile<RANK_KPT>(tile, tn, key, below);
+            }
+            for (int r = 0; r < a.n_rel; ++r) {                                      // (uniform: the row's words once)
+                int64_t obeg;
+                const int m = minor_extent(a, r, i, obeg);
+#pragma unroll
+                for (int x = 0; x < RANK_KPT; ++x) {
+                    const int t = base + x * RANK_THREADS + tid;
+                    if (t < n && below[x] < m) {
+                        a.out_ids[obeg + below[x]] = id[x];
+                        a.out_dist[obeg + below[x]] = dist[x];
+                    }
+                }
+            }
+        }
+        __syncthreads();                                                             // (the next centre's first tile)
+    }
+}
+
 }  // namespace pcg
 
 extern "C" {
+
+int pcg_rank_minority(const pcg_graph_desc *g, const int32_t *nodes, int32_t n, const float *s0, const float *center_s0,
+                      const uint64_t *pos_keys, const int64_t *out_begin, int32_t *out_ids, float *out_dist, uint32_t *status,
+                      void *stream) {
+    if (!g || n < 0 || g->n_pos < 0 || g->n_rel < 1 || g->n_rel > PCG_MAX_REL || g->n_nodes < 1) return PCG_E_ARG;
+    if ((int64_t)g->n_rel * n >= (1ll << 31)) return PCG_E_ARG;
+    if (n == 0 || g->n_pos == 0) return PCG_OK;
+    if (!nodes || !s0 || !pos_keys || !g->train_pos || !out_begin || !out_ids || !out_dist || !status) return PCG_E_ARG;
+    pcg::MinorArgs a;
+    a.nodes = nodes;
+    a.n = n;
+    a.n_rel = g->n_rel;
+    a.P = g->n_pos;
+    a.n_nodes = g->n_nodes;
+    a.s0 = s0;
+    a.center_s0 = center_s0;
+    a.keys = pos_keys;
+    a.train_pos = g->train_pos;
+    a.out_begin = out_begin;
+    a.out_ids = out_ids;
+    a.out_dist = out_dist;
+    a.status = status;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t short_blocks = ((int64_t)n + 3) / 4;                     // four waves a workgroup, one centre a wave
+    hipLaunchKernelGGL(pcg::rank_minor_short, dim3((int)(short_blocks < pcg::RANK_SHORT_BLOCKS ? short_blocks : pcg::RANK_SHORT_BLOCKS)),
+                       dim3(pcg::RANK_THREADS), 0, st, a);
+    PCG_LAUNCH_CHECK();
+    if (g->n_pos > PCG_WAVE) {                                             // (a centre has no more candidates than P)
+        int64_t slices = ((int64_t)g->n_pos + pcg::RANK_SLICE - 1) / pcg::RANK_SLICE;
+        slices = slices > 16 ? 16 : slices;                                // (more: a workgroup takes several slices)
+        hipLaunchKernelGGL(pcg::rank_minor_wg, dim3(n < pcg::RANK_WG_BLOCKS ? n : pcg::RANK_WG_BLOCKS, (int)slices),
+                           dim3(pcg::RANK_THREADS), 0, st, a);
+        PCG_LAUNCH_CHECK();
+    }
+    return PCG_OK;
+}
 
 int pcg_rank_lists(const pcg_graph_desc *g, const int32_t *nodes, int32_t B, const float *s0, const float *center_s0,
                    const void *workspace, int64_t list_capacity, const int64_t *out_begin, int32_t *out_ids, float *out_dist,

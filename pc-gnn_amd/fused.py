@@ -1115,7 +1115,7 @@ class FusedPCGNN:
             what.append("the one-launch sort of the train positives met a bucket of more than 4096 keys: minority picks may be wrong")
         if st & _lib.PCG_ST_RANK_MISMATCH:
             what.append("rank_lists: a row's kept count on the device is not the extent its output offsets give it - the row "
-                        "was not written")
+                        "was not written (rank_minority: a row's extent is negative, above n_pos or leaves its array)")
         raise _lib.PcgnnLibraryError("; ".join(what) or f"device status {st}")
 
     def last_loss(self) -> torch.Tensor:
@@ -1193,7 +1193,7 @@ class FusedPCGNN:
         self._infer_status()
         return (logits, center) if want_center else logits
 
-    def chosen(self, ids=None, chunk: Optional[int] = None) -> ChosenLists:
+    def chosen(self, ids=None, chunk: Optional[int] = None, labels=None, train_flag: bool = False) -> ChosenLists:
         """WHY a node scores as it does: for every requested node and relation, the neighbours the test-mode selection kept - the
         selection ``infer`` and a deployed model use - in the reference's order with their distances (choose_step_test's
         samp_neighs / samp_scores, src/layers.py:713-736), on the device (pcg_chosen_set): ONE score pass, then per chunk of ids
@@ -1201,20 +1201,39 @@ class FusedPCGNN:
         allowed; a device tensor, numpy array or list; range-checked on the host).  The output offsets are host arithmetic on
         the degrees (a test-mode row keeps exactly deg > k + 1 ? k : deg entries), so the result is sized exactly.  Returns a
         ``ChosenLists``.  The training engine is left alone exactly as by ``infer`` (a deferred update is applied first).
-        Synchronises once (the status word)."""
+        Synchronises once (the status word).
+        train_flag=True, labels (one per id, 0 / 1): the TRAIN-mode lists (choose_step_neighs, src/layers.py:633-697).  The
+        neighbour part is the one above, unchanged - k and the keep-all rule are the same in both modes -; the result carries
+        the minority part beside it (``minor_row``, ``has_minority``): per row of a positive centre the m = min(int(k * rho),
+        n_pos) training positives nearest to its score, ranked, with their distances (pcg_rank_minority, one more pass over all
+        n ids after the chunks; the train-positive keys of the call's own scores are sorted into a buffer of the call's own -
+        the training engine's keys are neither read nor written)."""
         g, lib, inf = self.g, self.lib, self._inf
+        if train_flag and labels is None:
+            raise ValueError("chosen: train_flag=True needs labels (one per id)")
         self.flush()
         ids_host, ids_dev, n = whole_set_ids(ids, g.n_nodes, self.dev, "chosen: ids", all_ids=inf.get("all_ids"))
         if ids is None:
             inf["all_ids"] = ids_dev
             ids_host = np.arange(n, dtype=np.int64)
+        minor = {}
+        if train_flag:
+            labels_host = (labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)).reshape(-1)
+            if labels_host.size != n:
+                raise ValueError(f"chosen: {labels_host.size} labels for {n} ids")
+            if n and not np.isin(labels_host, (0, 1)).all():
+                raise ValueError("chosen: labels must be 0 or 1")
+            moff = ops.rank_offsets(ops.minority_counts(g, ids_host, labels_host, self.thresholds, self.rho))
+            minor = dict(minor_flat_offsets=torch.from_numpy(moff).to(self.dev), minor_host_offsets=moff,
+                         minor_ids=torch.empty(int(moff[-1]), dtype=torch.int32, device=self.dev),
+                         minor_dist=torch.empty(int(moff[-1]), dtype=torch.float32, device=self.dev))
         caps2 = ops.sel_capacity(g, ids_host, None, self.thresholds, 0.0, False)      # [R, n]: exact in test mode
         off = ops.rank_offsets(caps2)
         total = int(off[-1])
         out_begin = torch.from_numpy(off).to(self.dev)
         out_ids = torch.empty(total, dtype=torch.int32, device=self.dev)
         out_dist = torch.empty(total, dtype=torch.float32, device=self.dev)
-        res = ChosenLists(out_begin, out_ids, out_dist, g.R, n, host_offsets=off)
+        res = ChosenLists(out_begin, out_ids, out_dist, g.R, n, host_offsets=off, **minor)
         if n == 0:
             return res
         ws_bytes = lambda c, cap: int(lib.pcg_chosen_workspace_bytes(g.desc_ref(), c, cap))
@@ -1224,6 +1243,13 @@ class FusedPCGNN:
         _lib.check(lib.pcg_chosen_set(g.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk, _p(inf["s0"]), self._thr,
                                       _p(ws), cap, _p(out_begin), _p(out_ids), _p(out_dist), _p(inf["status"]),
                                       self._stream()), "pcg_chosen_set")
+        if minor and g.n_pos and int(minor["minor_host_offsets"][-1]):
+            cap_keys = int(lib.pcg_pos_sort_capacity(g.n_pos))
+            if inf.get("pos_keys") is None or inf["pos_keys"].numel() < cap_keys:
+                inf["pos_keys"] = torch.empty(cap_keys, dtype=torch.int64, device=self.dev)
+            ops.pos_sort(g, inf["s0"], inf["pos_keys"])
+            ops.rank_minority(g, ids_dev, inf["s0"], inf["pos_keys"], minor["minor_flat_offsets"], minor["minor_ids"],
+                              minor["minor_dist"], inf["status"])
         self._infer_status()
         return res
 

@@ -196,15 +196,28 @@ class ChosenLists:
     (choose_step_test, src/layers.py:713-736).  ``dist`` is ``torch.abs(centre score - neighbour score)`` bit for bit.
 
     offsets int64 [R, n + 1] (a view of the flat [R * n + 1] array: offsets[r, n] == offsets[r + 1, 0]) | ids int32 [total] |
-    dist float32 [total]."""
+    dist float32 [total].
+
+    A train-mode result (``chosen(train_flag=True)``, ``choose_ranked(labels=...)``; the kernel: pcg_rank_minority) carries the
+    MINORITY part beside it, in the same layout - ``minor_offsets`` [R, n + 1] (a view of ``minor_flat_offsets``), ``minor_ids``,
+    ``minor_dist``; ``has_minority`` says so: per row of a positive centre the m = min(int(k * rho), n_pos) training positives
+    nearest to its score, ascending distance, ties by position in train_pos (choose_step_neighs, src/layers.py:675-691); a pick
+    that is also a kept neighbour is listed in both parts, as the reference's samp_score_diff lists it.  ``row`` and the fields
+    above are the neighbour part in either case: it is the same in both modes."""
 
     def __init__(self, flat_offsets: torch.Tensor, ids: torch.Tensor, dist: torch.Tensor, R: int, n: int,
-                 host_offsets: Optional[np.ndarray] = None):
+                 host_offsets: Optional[np.ndarray] = None, minor_flat_offsets: Optional[torch.Tensor] = None,
+                 minor_ids: Optional[torch.Tensor] = None, minor_dist: Optional[torch.Tensor] = None,
+                 minor_host_offsets: Optional[np.ndarray] = None):
         self.R, self.n = int(R), int(n)
         self.flat_offsets = flat_offsets
         self.offsets = flat_offsets.as_strided((self.R, self.n + 1), (self.n, 1))
         self.ids, self.dist = ids, dist
         self._host = host_offsets
+        self.has_minority = minor_flat_offsets is not None
+        self.minor_flat_offsets, self.minor_ids, self.minor_dist = minor_flat_offsets, minor_ids, minor_dist
+        self.minor_offsets = minor_flat_offsets.as_strided((self.R, self.n + 1), (self.n, 1)) if self.has_minority else None
+        self._minor_host = minor_host_offsets
 
     def __iter__(self):
         return iter((self.offsets, self.ids, self.dist))
@@ -215,22 +228,45 @@ class ChosenLists:
             self._host = self.flat_offsets.cpu().numpy()
         return self._host
 
+    def minor_host_offsets(self) -> np.ndarray:
+        """The minority part's flat offsets [R * n + 1] on the host."""
+        if not self.has_minority:
+            raise ValueError("this ChosenLists has no minority part (a test-mode result)")
+        if self._minor_host is None:
+            self._minor_host = self.minor_flat_offsets.cpu().numpy()
+        return self._minor_host
+
     def row(self, r: int, i: int):
         """(ids, dist) of relation r, requested node i: views."""
         h = self.host_offsets()
         lo, hi = int(h[r * self.n + i]), int(h[r * self.n + i + 1])
         return self.ids[lo:hi], self.dist[lo:hi]
 
-    def mean_dist(self) -> torch.Tensor:
-        """The average neighbour distance of every row, [R, n] (the paper's per-relation diagnostic); NaN for an empty row."""
+    def minor_row(self, r: int, i: int):
+        """(ids, dist) of the minority picks of relation r, requested node i: views (empty for a negative centre)."""
+        h = self.minor_host_offsets()
+        lo, hi = int(h[r * self.n + i]), int(h[r * self.n + i + 1])
+        return self.minor_ids[lo:hi], self.minor_dist[lo:hi]
+
+    def mean_dist(self, include_minority: bool = False) -> torch.Tensor:
+        """The average neighbour distance of every row, [R, n] (the paper's per-relation diagnostic); NaN for an empty row.
+        include_minority: over the neighbour and the minority entries together (the mean of the reference's train-mode row)."""
         rows = self.R * self.n
+        dev = self.dist.device
         cnt = (self.flat_offsets[1:] - self.flat_offsets[:-1])
-        seg = torch.repeat_interleave(torch.arange(rows, device=self.dist.device), cnt)
-        tot = torch.zeros(rows, dtype=torch.float64, device=self.dist.device).index_add_(0, seg, self.dist.double())
+        seg = torch.repeat_interleave(torch.arange(rows, device=dev), cnt)
+        tot = torch.zeros(rows, dtype=torch.float64, device=dev).index_add_(0, seg, self.dist.double())
+        if include_minority and self.has_minority:
+            mcnt = (self.minor_flat_offsets[1:] - self.minor_flat_offsets[:-1])
+            seg = torch.repeat_interleave(torch.arange(rows, device=dev), mcnt)
+            tot.index_add_(0, seg, self.minor_dist.double())
+            cnt = cnt + mcnt
         return (tot / cnt.double()).float().view(self.R, self.n)
 
     def to_reference(self, r: int):
-        """Relation r in the reference's return shape: (samp_neighs list[set[int]], samp_scores list[list[float]])."""
+        """Relation r in the reference's return shape: (samp_neighs list[set[int]], samp_scores list[list[float]]).  With a
+        minority part it is the train-mode shape: the set union of neighbour and minority ids, and the neighbour distances
+        followed by the minority distances (src/layers.py:690-695)."""
         h = self.host_offsets()
         lo, hi = int(h[r * self.n]), int(h[(r + 1) * self.n])
         ids = self.ids[lo:hi].cpu().numpy()
@@ -238,6 +274,15 @@ class ChosenLists:
         cut = (h[r * self.n:(r + 1) * self.n + 1] - lo).tolist()
         sets = [set(ids[a:b].tolist()) for a, b in zip(cut[:-1], cut[1:])]
         scores = [dist[a:b].tolist() for a, b in zip(cut[:-1], cut[1:])]
+        if self.has_minority:
+            h = self.minor_host_offsets()
+            lo, hi = int(h[r * self.n]), int(h[(r + 1) * self.n])
+            ids = self.minor_ids[lo:hi].cpu().numpy()
+            dist = self.minor_dist[lo:hi].cpu().numpy()
+            cut = (h[r * self.n:(r + 1) * self.n + 1] - lo).tolist()
+            for i, (a, b) in enumerate(zip(cut[:-1], cut[1:])):
+                sets[i].update(ids[a:b].tolist())
+                scores[i].extend(dist[a:b].tolist())
         return sets, scores
 
 

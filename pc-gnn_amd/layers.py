@@ -44,6 +44,9 @@ class _CenterScores(torch.autograd.Function):
 class IntraAgg(nn.Module):
     """Intra-relation aggregator (reference: src/layers.py:539-630)."""
 
+    # forward(train_flag=True)'s second value: False - None, as before; True - the reference's samp_scores (choose_step_neighs)
+    train_samp_scores = False
+
     def __init__(self, features, feat_dim, embed_dim, train_pos, rho, cuda=False):
         super().__init__()
         self.features = features
@@ -81,8 +84,16 @@ class IntraAgg(nn.Module):
         center = batch_scores.detach()[:, 0].contiguous().to(dev)
         ws = ops.ChooseWorkspace(g, B)
         agg, _ = ops.choose_aggregate(g, rows, labels, s0, keys, [thr], [self.rho], train_flag, center_s0=center, ws=ws)
-        # samp_scores (layers.py:591, 630): test mode only - the lists the call above left in ws, ranked (train mode: None, DESIGN)
-        samp_scores = None if train_flag else _ranked_scores(g, rows, s0, [thr], center, orders, ws=ws)[1]
+        # samp_scores (layers.py:589-591, 630).  Test mode: the lists the call above left in ws, ranked.  Train mode: those lists
+        # have holes (a minority pick that duplicates a kept neighbour) and no order, so the neighbour part is ranked from a
+        # second, test-mode select and the minority part by rank_minority (choose_ranked(labels=...)): a compatibility entry,
+        # not a hot path - and asked for (train_samp_scores): a train-mode call returned None here before and still does
+        if train_flag:
+            samp_scores = None
+            if self.train_samp_scores:
+                samp_scores = _ranked_scores(g, rows, s0, [thr], center, orders, labels=labels, rho=[self.rho], pos_keys=keys)[1]
+        else:
+            samp_scores = _ranked_scores(g, rows, s0, [thr], center, orders, ws=ws)[1]
         self_feats = self.features.weight.detach().to(dev)[torch.as_tensor(np.asarray(nodes), device=dev).long()]
         return self.transform(self_feats, agg[0]), samp_scores
 
@@ -112,12 +123,13 @@ def _pack_explicit_lists(features, n_nodes, neighs_list, neigh_scores, sample_li
     return g, s0, thr, orders
 
 
-def _ranked_scores(g, rows, s0, thresholds, center, orders, ws=None):
+def _ranked_scores(g, rows, s0, thresholds, center, orders, ws=None, labels=None, rho=None, pos_keys=None):
     """(samp_neighs, samp_scores) of relation 0 in the reference's return shape.  ws: a workspace that already holds the rows'
     test-mode lists (else they are selected here).  A keep-all row comes back in the CALLER's list order, as the reference
-    returns it (the kernels see the list sorted by id: orders[b] undoes it); a ranked row by ascending distance."""
+    returns it (the kernels see the list sorted by id: orders[b] undoes it); a ranked row by ascending distance.  labels (and
+    rho): train mode - a positive centre's minority distances follow its neighbour part, its minority ids join its set."""
     if ws is None:
-        ch = ops.choose_ranked(g, rows, s0, thresholds, center_s0=center)
+        ch = ops.choose_ranked(g, rows, s0, thresholds, center_s0=center, labels=labels, rho=rho, pos_keys=pos_keys)
     else:
         B = rows.numel()
         caps = ops.sel_capacity(g, np.arange(B, dtype=np.int64), None, thresholds, 0.0, False)
@@ -129,13 +141,40 @@ def _ranked_scores(g, rows, s0, thresholds, center, orders, ws=None):
         ops.check_status(ws.status)
         ch = ops.ChosenLists(out_begin, ids, dist, g.R, B, host_offsets=off)
     sets, scores = ch.to_reference(0)
+    kept = np.diff(ch.host_offsets()[:len(orders) + 1])
     for b, order in enumerate(orders):
-        if len(scores[b]) == len(order):            # keep-all: entry t of the sorted list is entry order[t] of the caller's
+        if int(kept[b]) == len(order):              # keep-all: entry t of the sorted list is entry order[t] of the caller's
             back = [0.0] * len(order)
             for t, o in enumerate(order.tolist()):
                 back[o] = scores[b][t]
-            scores[b] = back
+            scores[b][:len(order)] = back           # (a minority part, if any, follows)
     return sets, scores
+
+
+def choose_step_neighs(center_scores, center_labels, neigh_scores, neighs_list, minor_scores, minor_list, sample_list,
+                       sample_rate):
+    """The reference's train-mode choose step under its own name, signature and return shape (src/layers.py:633-697) on the HIP
+    path: ``(samp_neighs list[set], samp_scores list[list[float]])``.  Per centre the neighbour part is ``choose_step_test``'s
+    (ascending distance where the reference ranks, the list's own order where it keeps every neighbour); for a centre of label
+    1 the ``int(num_sample * sample_rate)`` nodes of ``minor_list`` nearest to its score (at most all of them) join the set and
+    their distances, ascending, ties by position in ``minor_list``, follow the neighbour distances.  A minority node that is
+    also a kept neighbour is in the set once and in the scores twice, as in the reference.
+    Two differences from the reference.  It extends the CALLER's ``neighs_list[b]`` with the minority ids on a keep-all row
+    (``selected_neighs = neighs_indices`` is the same list object, :669, :690); this leaves the argument alone.  An id that is
+    both a listed neighbour and a minority node carries ONE score here, ``minor_scores``' - as it does in the reference's own
+    callers, which slice both out of one table (:246-253).  ``minor_list`` holds no id twice (pos_neg_split, utils.py:256-271)."""
+    dev = center_scores.device if center_scores.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    B = len(neighs_list)
+    minor_list = [int(v) for v in minor_list]
+    top = max([int(max(l)) for l in neighs_list if len(l)] + [max(minor_list, default=0)], default=0)
+    n_nodes = max(top + 1, B, 1)
+    g, s0, thr, orders = _pack_explicit_lists(torch.zeros(n_nodes, 4), n_nodes, neighs_list, neigh_scores, sample_list, minor_list, dev)
+    if minor_list:
+        s0[torch.as_tensor(minor_list, device=dev)] = minor_scores.detach().reshape(-1, 2)[:, 0].to(dev)
+    rows = torch.arange(B, dtype=torch.int32, device=dev)
+    center = center_scores.detach().reshape(-1, 2)[:, 0].contiguous().to(dev)
+    labels = center_labels.detach().cpu().numpy() if torch.is_tensor(center_labels) else np.asarray(center_labels)
+    return _ranked_scores(g, rows, s0, [thr], center, orders, labels=labels.reshape(-1), rho=[float(sample_rate)])
 
 
 def choose_step_test(center_scores, neigh_scores, neighs_list, sample_list):

@@ -114,17 +114,31 @@ class ChooseWorkspace:
 def sel_capacity(g: DeviceGraph, nodes_host: np.ndarray, labels_host: Optional[np.ndarray],
                  thresholds: Sequence[float], rho, train_flag: bool, add_self: bool = False) -> np.ndarray:
     """Host-side upper bound of every row's chosen-set size, [R, B] (pcg_sel_capacity_row, vectorised)."""
+    minor = minority_counts(g, nodes_host, labels_host, thresholds, rho) if train_flag else None
     caps = []
     for r in range(g.R):
         deg = g.deg_host[r][nodes_host].astype(np.int64)
         k = np.ceil(deg * float(thresholds[r])).astype(np.int64)
         cap = np.where(deg > k + 1, k, deg)
         if train_flag:
-            rr = float(rho) if np.isscalar(rho) else float(rho[r])
-            m = np.minimum((k * rr).astype(np.int64), g.n_pos)
-            cap = cap + np.where(np.asarray(labels_host) == 1, np.maximum(m, 0), 0)
+            cap = cap + minor[r]
         caps.append(cap + (1 if add_self else 0))
     return np.stack(caps)
+
+
+def minority_counts(g: DeviceGraph, nodes_host: np.ndarray, labels_host: np.ndarray, thresholds: Sequence[float],
+                    rho) -> np.ndarray:
+    """The number of minority picks of every train-mode row, int64 [R, n]: m = min(int(k * rho), n_pos) for a positive centre
+    (label 1), 0 otherwise (layers.py:675-691; pcg_sel_capacity_row's minority term, vectorised)."""
+    pos = np.asarray(labels_host) == 1
+    out = []
+    for r in range(g.R):
+        deg = g.deg_host[r][nodes_host].astype(np.int64)
+        k = np.ceil(deg * float(thresholds[r])).astype(np.int64)
+        rr = float(rho) if np.isscalar(rho) else float(rho[r])
+        m = np.minimum((k * rr).astype(np.int64), g.n_pos)
+        out.append(np.where(pos, np.maximum(m, 0), 0).astype(np.int64))
+    return np.stack(out)
 
 
 def _host_arrays(g, thresholds, rho):
@@ -261,26 +275,59 @@ def rank_lists(g: DeviceGraph, nodes: torch.Tensor, s0: torch.Tensor, ws: Choose
                                   _p(out_begin), _p(out_ids), _p(out_dist), _p(ws.status), _stream(g.device)), "pcg_rank_lists")
 
 
+def rank_minority(g: DeviceGraph, nodes: torch.Tensor, s0: torch.Tensor, pos_keys: torch.Tensor, out_begin: torch.Tensor,
+                  out_ids: torch.Tensor, out_dist: torch.Tensor, status: torch.Tensor,
+                  center_s0: Optional[torch.Tensor] = None):
+    """The minority picks of train-mode rows, ranked, with their distances (pcg_rank_minority): row (r, i) - its extent in
+    out_begin (int64 device tensor [R * n + 1], rank_offsets of minority_counts) IS its m - receives the m training positives
+    nearest to the centre's score, ascending distance, ties by position in train_pos.  pos_keys: pos_sort's of the same s0.
+    An extent that is negative, above n_pos or leaves the arrays sets PCG_ST_RANK_MISMATCH in ``status`` and the row is not
+    written.  Needs no workspace and no plan; nothing synchronises."""
+    lib = _lib.load()
+    _lib.check(lib.pcg_rank_minority(g.desc_ref(), _p(nodes), nodes.numel(), _p(s0), _p(center_s0), _p(pos_keys), _p(out_begin),
+                                     _p(out_ids), _p(out_dist), _p(status), _stream(g.device)), "pcg_rank_minority")
+
+
 def choose_ranked(g: DeviceGraph, nodes, s0: torch.Tensor, thresholds: Sequence[float],
-                  center_s0: Optional[torch.Tensor] = None) -> ChosenLists:
+                  center_s0: Optional[torch.Tensor] = None, labels=None, rho=None,
+                  pos_keys: Optional[torch.Tensor] = None) -> ChosenLists:
     """choose_step_test for all relations of a batch, on the device: select (test mode) followed by rank.  Returns a
     ``ChosenLists`` (offsets [R, B + 1], ids, dist - unpacks as ``offsets, ids, dist = choose_ranked(...)``).  The offsets are
-    host arithmetic on the degrees; one read of the status word at the end (synchronises)."""
+    host arithmetic on the degrees; one read of the status word at the end (synchronises).
+    With ``labels`` (one per node, 0 / 1) it is choose_step_neighs - train mode: the neighbour part is the test-mode one
+    unchanged (k and the keep-all rule are the same in both modes), and the result carries the minority part too - per row of a
+    positive centre the m = min(int(k * rho), n_pos) nearest training positives, ranked (``rank_minority``; rho: a scalar or
+    one per relation; pos_keys: ``pos_sort`` of s0, sorted here if not given)."""
     nodes = _i32(nodes, g.device).view(-1)
     B = nodes.numel()
-    caps = sel_capacity(g, nodes.cpu().numpy().astype(np.int64), None, thresholds, 0.0, False)
+    nodes_host = nodes.cpu().numpy().astype(np.int64)
+    caps = sel_capacity(g, nodes_host, None, thresholds, 0.0, False)
     off = rank_offsets(caps)
     total = int(off[-1])
     out_begin = torch.from_numpy(off).to(g.device)
     ids = torch.empty(total, dtype=torch.int32, device=g.device)
     dist = torch.empty(total, dtype=torch.float32, device=g.device)
+    minor = {}
+    if labels is not None:
+        labels_host = (labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)).reshape(-1)
+        if labels_host.size != B:
+            raise ValueError(f"choose_ranked: {labels_host.size} labels for {B} nodes")
+        moff = rank_offsets(minority_counts(g, nodes_host, labels_host, thresholds, 0.0 if rho is None else rho))
+        minor = dict(minor_flat_offsets=torch.from_numpy(moff).to(g.device), minor_host_offsets=moff,
+                     minor_ids=torch.empty(int(moff[-1]), dtype=torch.int32, device=g.device),
+                     minor_dist=torch.empty(int(moff[-1]), dtype=torch.float32, device=g.device))
     if B:
         ws = ChooseWorkspace(g, B, list_capacity=max(total, 1))
         cnt = torch.empty(g.R * B, dtype=torch.int32, device=g.device)
         choose_select(g, nodes, None, s0, None, thresholds, 0.0, False, ws, cnt, center_s0=center_s0)
         rank_lists(g, nodes, s0, ws, out_begin, ids, dist, center_s0=center_s0)
+        if minor and g.n_pos and int(minor["minor_host_offsets"][-1]):
+            if pos_keys is None:
+                pos_keys = pos_sort(g, s0)
+            rank_minority(g, nodes, s0, pos_keys, minor["minor_flat_offsets"], minor["minor_ids"], minor["minor_dist"], ws.status,
+                          center_s0=center_s0)
         check_status(ws.status)
-    return ChosenLists(out_begin, ids, dist, g.R, B, host_offsets=off)
+    return ChosenLists(out_begin, ids, dist, g.R, B, host_offsets=off, **minor)
 
 
 def segment_mean(g: DeviceGraph, begin: torch.Tensor, count: torch.Tensor, idx: torch.Tensor,
