@@ -76,7 +76,7 @@ typedef struct pcg_graph_desc {
 
 /* library / build identification: "pcgnn_hip gfx950 <abi>" (host pointer, static) */
 const char *pcg_version(void);
-int pcg_abi_version(void);   /* 10 (added: pcg_rank_minority) */
+int pcg_abi_version(void);   /* 11 (added: pcg_attr_set, pcg_attr_neighbours) */
 
 /* ---- label-aware scores -------------------------------------------------------
  * Replaces  batch_scores = self.label_clf(self.features(unique_nodes))
@@ -638,6 +638,30 @@ int pcg_chosen_set(const pcg_graph_desc *g, const float *theta, int32_t emb, con
 int pcg_rank_minority(const pcg_graph_desc *g, const int32_t *nodes, int32_t n, const float *s0, const float *center_s0,
                       const uint64_t *pos_keys, const int64_t *out_begin, int32_t *out_ids, float *out_dist, uint32_t *status,
                       void *stream);
+/* Exact input attributions of the gnn logits (FusedPCGNN.attribute, ops.neighbour_contrib).  The gnn path has no bias, so with the
+ * selection held fixed s = w0 * logit0 + w1 * logit1 is positively homogeneous of degree 1 in (x, a_1 .. a_R) - the centre's own
+ * row and the means of its chosen rows - and gradient times input splits it completely:
+ *   s[b] = <x_b, d_self[b]> + sum_r <a_r[b], d_agg[r, b]>,   <a_r[b], d_agg[r, b]> = sum_{j in chosen(r, b)} <X[j], d_agg[r, b]> / |chosen|.
+ * pcg_attr_set: pcg_infer_set's arguments, checks, workspace (pcg_infer_workspace_bytes) and launches - one front, then per chunk
+ * plan (test mode) -> select -> gather -> a dense launch that runs pcg_infer_set's forward phases unchanged (out_logits [n][2] is
+ * bit for bit pcg_infer_set's) and from their LDS state the backward to the inputs (three MFMA phases, exact f32):
+ *   out_d_self [n][feat_dim] = d s / d x;  out_d_agg [n_rel][n][feat_dim] = d s / d a_r;  out_self_contrib [n] = <x, d_self>;
+ *   out_rel_contrib [n_rel][n] = <a_r, d_agg_r>.  w0, w1 must be finite (else PCG_E_ARG).
+ * A row's values depend on the row alone (not on its tile, chunk or position); a row with an empty neighbour set has pcg_infer_set's logits
+ * (its 0 / 0 aggregate included) and unspecified attributions, and disturbs no other row.  Never synchronises, never allocates; n == 0:
+ * nothing is enqueued.
+ * pcg_attr_neighbours: for every entry e of row (r, i) of ranked lists (flat_offsets int64 [n_rel * n + 1], ids int32
+ * [flat_offsets[n_rel * n]]: pcg_chosen_set's out_begin / out_ids) out[e] = <X[ids[e]], d_agg[r, i]> / row length; d_agg any
+ * [n_rel][n][feat_dim] f32 array.  Every dot product is formed by a fixed lane group in a fixed order: the bits do not depend on
+ * the launch geometry.  An id outside [0, n_nodes) is clamped for the read and sets PCG_ST_LIST_ID_RANGE; a row whose offsets
+ * are not 0 <= begin <= end <= flat_offsets[n_rel * n] sets PCG_ST_RANK_MISMATCH and is not written.  One launch; rows longer
+ * than 128 entries are sliced over workgroups.  Never synchronises, never allocates; n == 0: nothing is enqueued. */
+int pcg_attr_set(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *ids, int32_t n, int32_t chunk_rows,
+                 float *s0, const double *thresholds, void *workspace, int64_t list_capacity, float w0, float w1, float *out_logits,
+                 float *out_d_self, float *out_d_agg, float *out_self_contrib, float *out_rel_contrib, uint32_t *status,
+                 void *stream);
+int pcg_attr_neighbours(const pcg_graph_desc *g, const int64_t *flat_offsets, const int32_t *ids, int32_t n_rel, int32_t n,
+                        const float *d_agg, float *out, uint32_t *status, void *stream);
 int pcg_step_front_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, float *s0,
                          uint64_t *pos_keys, const int32_t *nodes, const int32_t *labels, int32_t B,
                          const double *thresholds, const double *rho, int32_t add_self, void *workspace,

@@ -18,7 +18,7 @@ PCG_ST_SORT_OVERFLOW = 8
 PCG_ST_EVAL_INPUT = 16
 PCG_ST_RANK_MISMATCH = 32
 PCG_NORM_COUNT, PCG_NORM_SQRT_COUNT = 0, 1
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class GraphDesc(C.Structure):
@@ -118,6 +118,9 @@ PROTOTYPES = {
     "pcg_rank_minority": (C.c_int, [_G, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pcg_chosen_workspace_bytes": (_I64, [_G, _I32, _I64]),
     "pcg_chosen_set": (C.c_int, [_G, _P, _I32, _P, _I32, _I32, _P, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P, _P]),
+    "pcg_attr_set": (C.c_int, [_G, _P, _I32, _P, _I32, _I32, _P, C.POINTER(_F64), _P, _I64, C.c_float, C.c_float, _P, _P, _P, _P, _P,
+                               _P, _P]),
+    "pcg_attr_neighbours": (C.c_int, [_G, _P, _P, _I32, _I32, _P, _P, _P, _P]),
     "pcg_eval_workspace_bytes": (_I64, [_I64, _I32]),
     "pcg_eval_counts": (C.c_int, [_P, _P, _I64, _P, _I32, _P, _P, _P, _P]),
     "pcg_step_front_train": (C.c_int, [_G, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, C.POINTER(_F64), C.POINTER(_F64), _I32, _P,

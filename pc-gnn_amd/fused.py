@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .graph import ChosenLists, DeviceGraph, QueryBatch
+from .graph import Attribution, ChosenLists, DeviceGraph, QueryBatch
 from .model import PCALayer
 
 _p = ops._p
@@ -1115,7 +1115,8 @@ class FusedPCGNN:
             what.append("the one-launch sort of the train positives met a bucket of more than 4096 keys: minority picks may be wrong")
         if st & _lib.PCG_ST_RANK_MISMATCH:
             what.append("rank_lists: a row's kept count on the device is not the extent its output offsets give it - the row "
-                        "was not written (rank_minority: a row's extent is negative, above n_pos or leaves its array)")
+                        "was not written (rank_minority: a row's extent is negative, above n_pos or leaves its array; "
+                        "neighbour_contrib: a row's offsets are not ascending inside the lists)")
         raise _lib.PcgnnLibraryError("; ".join(what) or f"device status {st}")
 
     def last_loss(self) -> torch.Tensor:
@@ -1251,6 +1252,57 @@ class FusedPCGNN:
             ops.rank_minority(g, ids_dev, inf["s0"], inf["pos_keys"], minor["minor_flat_offsets"], minor["minor_ids"],
                               minor["minor_dist"], inf["status"])
         self._infer_status()
+        return res
+
+    def attribute(self, ids=None, chunk: Optional[int] = None, target=(0.0, 1.0), neighbours: bool = False) -> Attribution:
+        """WHAT pushed a node's score: the exact split of ``target[0] * logit0 + target[1] * logit1`` (default: the fraud logit,
+        whose sigmoid is the probability ``evaluate`` / ``predict_proba`` report; (-1, 1): the margin) into the shares of the
+        node's own features, of every relation and - neighbours=True - of every chosen neighbour (pcg_attr_set,
+        pcg_attr_neighbours).  The gnn path has no bias, so with the test-mode selection held fixed (it is not differentiable; the
+        reference's autograd treats it the same way) the scalar is positively homogeneous of degree 1 in the node's row and the
+        means of its chosen rows: gradient times input adds up to it exactly (``Attribution.completeness_residual``).
+        ids, chunk: as ``infer`` (None = every node; any order, duplicates allowed; a device tensor, numpy array or list;
+        range-checked on the host).  ``infer``'s launches with the backward to the inputs behind each tile's forward: the
+        result's logits are ``infer(ids)`` bit for bit, and a node's values do not depend on its position, chunk or company.
+        neighbours=True calls ``chosen(ids)`` and adds its lists and ``neigh_contrib`` beside them.  The training engine is left
+        alone exactly as by ``infer`` (a deferred update is applied first).  Synchronises once (the status word; once more per
+        ``chosen`` call).  target: two finite floats, else ValueError.
+        Out of scope: ``DistributedPCGNN``, ``infer_new`` queries, the train-mode selection and its minority picks, the
+        GraphSAGE / GCN baselines."""
+        g, lib, inf = self.g, self.lib, self._inf
+        try:
+            w0, w1 = (float(t) for t in target)
+        except (TypeError, ValueError):
+            raise ValueError(f"attribute: target must be two finite floats, got {target!r}") from None
+        if not (np.isfinite(w0) and np.isfinite(w1)):
+            raise ValueError(f"attribute: target must be two finite floats, got {target!r}")
+        self.flush()
+        ids_host, ids_dev, n = whole_set_ids(ids, g.n_nodes, self.dev, "attribute: ids", all_ids=inf.get("all_ids"))
+        if ids is None:
+            inf["all_ids"] = ids_dev
+        F, R, f32 = g.feat_dim, g.R, dict(dtype=torch.float32, device=self.dev)
+        res = Attribution(ids_dev, g.X, F, torch.empty(n, 2, **f32), torch.empty(n, F, **f32), torch.empty(R, n, F, **f32),
+                          torch.empty(n, **f32), torch.empty(R, n, **f32), (w0, w1))
+        if n:
+            ws_bytes = lambda c, cap: int(lib.pcg_infer_workspace_bytes(g.desc_ref(), self.E, c, cap))
+            chunk_rows, cap, ws = whole_set_chunk(inf, "ws", self.dev, ws_bytes, "pcg_infer_workspace_bytes",
+                                                  infer_row_caps(g.deg_host, self.thresholds, ids_host), chunk,
+                                                  self.infer_workspace_bytes)
+            whole_set_buffers(inf, self.dev, "s0", g.n_nodes)
+            _lib.check(lib.pcg_attr_set(g.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk_rows, _p(inf["s0"]), self._thr,
+                                        _p(ws), cap, w0, w1, _p(res.logits), _p(res.d_self), _p(res.d_agg), _p(res.self_contrib),
+                                        _p(res.rel_contrib), _p(inf["status"]), self._stream()), "pcg_attr_set")
+        if neighbours:
+            if n:
+                # (chosen reads the status word itself: the attribution's launches are covered by that read)
+                res.chosen = self.chosen(ids if ids is None else ids_dev, chunk=chunk)
+                res.neigh_contrib = ops.neighbour_contrib(g, res.chosen, res.d_agg, status=inf["status"])
+                self._infer_status()
+            else:
+                res.chosen = self.chosen(ids_dev)
+                res.neigh_contrib = torch.empty(0, **f32)
+        elif n:
+            self._infer_status()
         return res
 
     def _infer_status(self):

@@ -286,6 +286,51 @@ class ChosenLists:
         return sets, scores
 
 
+class Attribution:
+    """Exact input attributions of ``target[0] * logit0 + target[1] * logit1`` for n requested nodes (``FusedPCGNN.attribute``;
+    the kernels: pcg_attr_set, pcg_attr_neighbours) - device tensors.  The gnn path has no bias, so with the selection held fixed
+    the attributed scalar is positively homogeneous of degree 1 in the node's own row x and the means a_r of its chosen rows,
+    and gradient times input splits it completely:  target . logits[i] = self_contrib[i] + sum_r rel_contrib[r, i].
+
+    logits [n, 2] (``infer``'s, bit for bit) | d_self [n, F] = d target / d x | d_agg [R, n, F] = d target / d a_r |
+    self_contrib [n] = <x, d_self> | rel_contrib [R, n] = <a_r, d_agg_r> | target (w0, w1).
+    With neighbours: ``chosen`` - the ``ChosenLists`` of the same ids - and neigh_contrib float32 [total], entry for entry beside
+    ``chosen.ids``: <X[id], d_agg[r, i]> / row length; a row's entries sum to rel_contrib[r, i].
+    A node with an empty neighbour set (a 0 / 0 aggregate) has the logits ``infer`` gives it; its attributions are unspecified."""
+
+    def __init__(self, ids: torch.Tensor, X: torch.Tensor, feat_dim: int, logits, d_self, d_agg, self_contrib, rel_contrib, target,
+                 chosen: Optional[ChosenLists] = None, neigh_contrib: Optional[torch.Tensor] = None):
+        self.ids, self._X, self._F = ids, X, int(feat_dim)
+        self.logits, self.d_self, self.d_agg = logits, d_self, d_agg
+        self.self_contrib, self.rel_contrib = self_contrib, rel_contrib
+        self.target = (float(target[0]), float(target[1]))
+        self.chosen, self.neigh_contrib = chosen, neigh_contrib
+
+    def target_logit(self) -> torch.Tensor:
+        """The attributed scalar of every node, [n]."""
+        return self.target[0] * self.logits[:, 0] + self.target[1] * self.logits[:, 1]
+
+    def feature_contrib(self) -> torch.Tensor:
+        """``X[ids] * d_self`` [n, F]: the share of each of the node's own features (its rows sum to self_contrib)."""
+        return self._X[self.ids.long(), :self._F] * self.d_self
+
+    def completeness_residual(self) -> torch.Tensor:
+        """self_contrib + rel_contrib.sum(0) - target . logits, [n]: rounding error only."""
+        return self.self_contrib + self.rel_contrib.sum(0) - self.target_logit()
+
+    def top_neighbours(self, r: int, i: int, k: Optional[int] = None):
+        """(ids, contributions) of relation r, requested node i, by descending absolute contribution (the first k; None: all)."""
+        if self.chosen is None:
+            raise ValueError("this Attribution has no neighbour part (attribute(neighbours=True))")
+        h = self.chosen.host_offsets()
+        lo, hi = int(h[r * self.chosen.n + i]), int(h[r * self.chosen.n + i + 1])
+        c = self.neigh_contrib[lo:hi]
+        order = torch.argsort(c.abs(), descending=True, stable=True)
+        if k is not None:
+            order = order[:int(k)]
+        return self.chosen.ids[lo:hi][order], c[order]
+
+
 class BaseShape:
     """What a ``QueryBatch`` is validated against: the base graph's node count, feature width and relation count.  A
     ``DeviceGraph`` has the same three attributes; this stands in for one where there is no GPU (host-side checks, tests)."""

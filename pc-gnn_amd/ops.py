@@ -330,6 +330,38 @@ def choose_ranked(g: DeviceGraph, nodes, s0: torch.Tensor, thresholds: Sequence[
     return ChosenLists(out_begin, ids, dist, g.R, B, host_offsets=off, **minor)
 
 
+def neighbour_contrib(g: DeviceGraph, chosen: ChosenLists, d_agg: torch.Tensor, status: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Every chosen neighbour's share of its relation's contribution (pcg_attr_neighbours): for entry e of row (r, i) of
+    ``chosen``, out[e] = <X[chosen.ids[e]], d_agg[r, i]> / row length - float32 [total], beside ``chosen.ids``.  d_agg: any
+    float32 [R, n, F] tensor (``Attribution.d_agg``: a row's entries then sum to rel_contrib[r, i]).  An id outside the table
+    sets PCG_ST_LIST_ID_RANGE in ``status``, a row whose offsets are not ascending inside [0, total] PCG_ST_RANK_MISMATCH (and
+    is not written).  status None: a word of the call's own, read at the end (synchronises) and raised; else nothing
+    synchronises.  out: a contiguous float32 tensor of chosen.ids.numel() entries to write into (None: a new one)."""
+    lib = _lib.load()
+    R, n = chosen.R, chosen.n
+    d_agg = d_agg.detach()
+    if d_agg.dtype != torch.float32 or tuple(d_agg.shape) != (R, n, g.feat_dim):
+        raise ValueError(f"neighbour_contrib: d_agg must be float32 [{R}, {n}, {g.feat_dim}], got {d_agg.dtype} {tuple(d_agg.shape)}")
+    if R != g.R or chosen.flat_offsets.numel() != R * n + 1 or chosen.flat_offsets.dtype != torch.int64:
+        raise ValueError("neighbour_contrib: the lists are not this graph's (relations / offsets)")
+    d_agg = d_agg.to(g.device).contiguous()
+    if out is None:
+        out = torch.empty(chosen.ids.numel(), dtype=torch.float32, device=g.device)
+    elif out.dtype != torch.float32 or out.numel() != chosen.ids.numel() or not out.is_contiguous() or out.device != d_agg.device:
+        raise ValueError("neighbour_contrib: out must be a contiguous float32 device tensor with one entry per list entry")
+    if out.numel() == 0:
+        return out
+    own = status is None
+    if own:
+        status = torch.zeros(1, dtype=torch.int32, device=g.device)
+    _lib.check(lib.pcg_attr_neighbours(g.desc_ref(), _p(chosen.flat_offsets), _p(chosen.ids), R, n, _p(d_agg), _p(out), _p(status),
+                                       _stream(g.device)), "pcg_attr_neighbours")
+    if own:
+        check_status(status)
+    return out
+
+
 def segment_mean(g: DeviceGraph, begin: torch.Tensor, count: torch.Tensor, idx: torch.Tensor,
                  norm: int = _lib.PCG_NORM_COUNT, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Mean of explicit index lists (mask.div(n).mm(X[unique]), layers.py:599-624)."""

@@ -154,14 +154,19 @@ def predict_proba_new(query, model, ids=None, chunk=None) -> np.ndarray:
         return np.ascontiguousarray(torch.sigmoid(model.infer_new(query, ids=ids, chunk=chunk)).float().cpu().numpy()[:, 1])
 
 
-def explain_nodes(engine, ids, labels=None):
+def explain_nodes(engine, ids, labels=None, attribute: bool = False):
     """A flagged node's score and its reason in one call: (``engine.chosen(ids)`` - the neighbours the model listened to, ranked,
     with their distances - , the test-mode class probabilities [n, 2] ``predict_proba`` reports for the same ids), on the device.
     labels (one per id, 0 / 1): the train-mode lists - the training positives a fraud centre is over-sampled with beside its
-    neighbours (``engine.chosen(ids, labels=labels, train_flag=True)``); the probabilities stay the test-mode ones."""
+    neighbours (``engine.chosen(ids, labels=labels, train_flag=True)``); the probabilities stay the test-mode ones.
+    attribute=True: a third value, ``engine.attribute(ids, neighbours=True)`` - how much of the fraud logit each of the node's
+    own features, each relation and each (test-mode) chosen neighbour accounts for."""
     with torch.no_grad():
         ch = engine.chosen(ids) if labels is None else engine.chosen(ids, labels=labels, train_flag=True)
-        return ch, torch.sigmoid(engine.infer(ids)).float()
+        prob = torch.sigmoid(engine.infer(ids)).float()
+        if not attribute:
+            return ch, prob
+        return ch, prob, engine.attribute(ids, neighbours=True)
 
 
 def predict_proba(test_nodes, model, batch_size: int, labels=None) -> np.ndarray:
