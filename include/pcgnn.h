@@ -76,7 +76,72 @@ typedef struct pcg_graph_desc {
 
 /* library / build identification: "pcgnn_hip gfx950 <abi>" (host pointer, static) */
 const char *pcg_version(void);
-int pcg_abi_version(void);   /* 11 (added: pcg_attr_set, pcg_attr_neighbours) */
+int pcg_abi_version(void);   /* 12 (the training entry points take parameter structs; added: pcg_abi_layout) */
+
+/* ---- parameter structs of the training entry points ------------------------------------------
+ * What a training engine owns is handed over as structs, by const pointer: an entry point reads them during the call and keeps
+ * no pointer to them (a temporary will do; a captured graph holds the values, not the struct).  A NULL struct pointer is
+ * PCG_E_ARG before anything else happens.  Pointers and scalars only; a member an entry point does not name is not read by it.
+ * A member that may be NULL means "off" exactly where the entry point says so - a caller that wants it on in one call and off
+ * in another keeps two instances.  pcg_abi_layout reports every struct's size and member offsets (a binding's layout check). */
+
+/* torch.optim.Adam's hyper-parameters (coupled weight decay, src/model_handler.py:124); converted to float once, on entry */
+typedef struct pcg_adam_hyper {
+    double lr, beta1, beta2, eps, weight_decay;
+} pcg_adam_hyper;
+
+/* What a training engine allocates once (again when the batch size it was made for grows). */
+typedef struct pcg_train_state {
+    float *theta, *m, *v;        /* the flat parameter buffer (pcg_dense_param_offset) and Adam's moments, n_params floats each */
+    int32_t *step_counter;       /* int32 [1]: Adam's t, counted on the device */
+    uint32_t *sync_words;        /* pcg_sync_words_count() zero-initialised words: [0] arrival ticket (0 between launches), [1] "an
+                                    update is waiting" (1: gradient slabs, 2: activations), [2] its slab / tile count, [3] and
+                                    the words behind it: pcg_choose_gather_planned's in-kernel sort */
+    float *clf_next;             /* [2 * feat_dim + 2] (W row-major, then b): the label classifier one step ahead of theta's copy -
+                                    the one the next select launch scores by (pcg_choose_gather_train) */
+    float *slabs;                /* [max(pcg_dense_n_tiles(B), 8), n_params]: per-tile gradient slabs, and the classifier step's
+                                    scratch.  NULL in pcg_train_dense: inference (no gradient, no step counted) */
+    float *acts;                 /* [pcg_wgrad_act_rows(...), act_ld], 16-byte aligned: the transposed activations of
+                                    pcg_train_dense(adam_clf = 3 / 4) that the weight-gradient GEMMs read.  NULL: the gradient-slab paths */
+    float *wg_scratch;           /* pcg_wgrad_scratch_bytes(...) zero-initialised bytes; may be NULL for act_ld <= 1024 */
+    int32_t emb;                 /* embedding width E */
+    int32_t act_ld;              /* floats per row of acts: the largest batch rounded up to 16 */
+    float lambda_1;              /* weight of the label classifier's loss term (src/model.py:54-61) */
+    int32_t _pad;
+    pcg_adam_hyper hyper;
+} pcg_train_state;
+
+/* The selection settings and the workspace every training call of an engine shares (the arguments of pcg_choose_select). */
+typedef struct pcg_select_ws {
+    const double *thresholds;    /* HOST double [n_rel] */
+    const double *rho;           /* HOST double [n_rel] */
+    void *workspace;             /* the DATA part (pcg_choose_data_bytes) when the batches carry their plan, else the single buffer */
+    uint32_t *status;            /* the device status word */
+    int64_t list_capacity;
+    int32_t add_self;
+    int32_t _pad;
+} pcg_select_ws;
+
+/* One batch. */
+typedef struct pcg_batch {
+    const int32_t *ids;          /* int32 [B] centre ids (the `nodes` of the selection entry points) */
+    const int32_t *labels;       /* int32 [B] */
+    int32_t *cnt;                /* int32 [n_rel * B]: |chosen set|, written by the batch's select launch, read by its dense launch */
+    const void *plan;            /* the batch's plan part (a slot pcg_plan_batches filled); NULL: it lies inside the workspace */
+    int32_t B;
+    float inv_count;             /* 1 / global batch size: the weight of a row's loss */
+} pcg_batch;
+
+/* What a dense launch writes for its batch: logits [B, 2], center [B, 2]; optional combined [B, E] (not written by the fused
+ * launches pcg_dense_select_*) and row_loss [B] (see pcg_dense_step). */
+typedef struct pcg_dense_out {
+    float *logits, *center, *combined, *row_loss;
+} pcg_dense_out;
+
+/* Layout of struct `which` (0 pcg_adam_hyper, 1 pcg_train_state, 2 pcg_select_ws, 3 pcg_batch, 4 pcg_dense_out) as this library
+ * was compiled: out[0] = sizeof, out[1 ..] = offsetof of every member in declaration order (padding members included).
+ * Returns the number of values written, or PCG_E_ARG (unknown struct, out NULL, cap too small).  Host only: no device call. */
+int32_t pcg_abi_layout(int32_t which, int64_t *out, int32_t cap);
 
 /* ---- label-aware scores -------------------------------------------------------
  * Replaces  batch_scores = self.label_clf(self.features(unique_nodes))
@@ -271,33 +336,26 @@ int pcg_step_scores(const pcg_graph_desc *g, const float *W, const float *b, int
  *     only the rows that byte map marks; n_pos > 16384: the bucket sort's launches follow).  It zeroes sync_words[3].
  * Nothing waits inside a launch for any of this.  On entry s0 / pos_keys hold THIS step's scores / unsorted keys (from the
  * previous step's call with score_next = 1, or from pcg_step_scores(W = clf_next, b = clf_next + 2 * feat_dim)).
- * pcg_adam_flush(..., clf_next) afterwards brings theta up to date (deferred update + the stepped classifier).
- * acts != NULL (with act_ld; `slabs` is then only the classifier step's scratch, >= 8 * n_params floats): the previous step ran
+ * pcg_adam_flush(st) afterwards brings theta up to date (deferred update + the stepped classifier).
+ * batch: ids, labels, cnt, plan, B, inv_count;  sel: all of it;  st: every member (lambda_1 weighs the classifier's loss).
+ * st->acts != NULL (with act_ld; `slabs` is then only the classifier step's scratch, >= 8 * n_params floats): the previous step ran
  * pcg_train_dense(adam_clf = 3) - no gradient slabs exist; the deferred update's workgroups are the weight-gradient GEMMs over
  * that step's batch, each 16 x 16 output tile's workgroup applying Adam to its own parameters (pcg_wgrad below).
  * keys_sorted != 0: pos_keys' first half holds THIS step's train-pos keys SORTED already (the previous step's
  * pcg_train_dense(adam_clf = 3, sort_keys) sorted them on CUs its tiles leave idle, or pcg_pos_sort behind pcg_step_scores): the
  * select launch sorts nothing, no row waits, and a positive hub row's minority window search runs on one of its waves beside the
  * others' key pass.  Same lists either way, bit for bit.
- * inv_count = 1 / global batch size.  Selection, lists and aggregates: exactly pcg_choose_gather_planned(train_flag = 1). */
-int pcg_choose_gather_train(const pcg_graph_desc *g, const int32_t *nodes, const int32_t *labels, int32_t B, float *s0,
-                            uint64_t *pos_keys, const double *thresholds, const double *rho, int32_t add_self, float *agg,
-                            int32_t agg_stride, int32_t *cnt, void *workspace, const void *plan, int64_t list_capacity,
-                            uint32_t *status, uint32_t *sync_words, float *theta, float *m, float *v, int32_t emb, float *clf_next,
-                            const float *slabs, const int32_t *step_counter, float lambda_1, float inv_count, double lr, double beta1,
-                            double beta2, double eps, double weight_decay, int32_t score_next, const uint8_t *next_touched,
-                            const float *acts, int32_t act_ld, float *wg_scratch, int32_t keys_sorted, void *stream);
+ * Selection, lists and aggregates: exactly pcg_choose_gather_planned(train_flag = 1). */
+int pcg_choose_gather_train(const pcg_graph_desc *g, const pcg_batch *batch, float *s0, uint64_t *pos_keys,
+                            const pcg_select_ws *sel, float *agg, int32_t agg_stride, const pcg_train_state *st,
+                            int32_t score_next, const uint8_t *next_touched, int32_t keys_sorted, void *stream);
 /* The same two launches one at a time, for the pipelined step (pcg_dense_select_train): part 1 = the select launch only (clf_out,
  * if not NULL, gets a copy of the classifier's in-value [2 * feat_dim + 2] beside theta's - the dense tiles of a fused launch
  * read it from there), part 2 = the gather launch only (+ the sort of the next step's keys where that is a launch of its own).
  * Arguments otherwise as pcg_choose_gather_train's; the weight-gradient workgroups always ride in the gather launch. */
-int pcg_choose_train_part(int32_t part, const pcg_graph_desc *g, const int32_t *nodes, const int32_t *labels, int32_t B, float *s0,
-                          uint64_t *pos_keys, const double *thresholds, const double *rho, int32_t add_self, float *agg,
-                          int32_t agg_stride, int32_t *cnt, void *workspace, const void *plan, int64_t list_capacity,
-                          uint32_t *status, uint32_t *sync_words, float *theta, float *m, float *v, int32_t emb, float *clf_next,
-                          const float *slabs, const int32_t *step_counter, float lambda_1, float inv_count, double lr, double beta1,
-                          double beta2, double eps, double weight_decay, int32_t score_next, const uint8_t *next_touched,
-                          const float *acts, int32_t act_ld, float *wg_scratch, int32_t keys_sorted, float *clf_out, void *stream);
+int pcg_choose_train_part(int32_t part, const pcg_graph_desc *g, const pcg_batch *batch, float *s0, uint64_t *pos_keys,
+                          const pcg_select_ws *sel, float *agg, int32_t agg_stride, const pcg_train_state *st,
+                          int32_t score_next, const uint8_t *next_touched, int32_t keys_sorted, float *clf_out, void *stream);
 /* The pipelined training step.  Batch t + 1's selection needs nothing batch t's dense tiles compute, so a sequence of steps
  * runs as
  *     pcg_choose_train_part(1, batch 0, clf_out = slot 0)
@@ -307,16 +365,13 @@ int pcg_choose_train_part(int32_t part, const pcg_graph_desc *g, const int32_t *
  * and leaves bit for bit what pcg_choose_gather_train + pcg_train_dense(adam_clf = 3) per step leave.  The fused launch: batch
  * t's tiles as pcg_train_dense(adam_clf = 3) (no key sort; the step is counted by the select half's classifier workgroup; the
  * label classifier read from clf_in = the slot batch t's select filled), batch t + 1's select as pcg_choose_train_part(1) with
- * unsorted keys (sorted inside the launch) and clf_out = the other slot.  cnt / next_cnt: two different buffers.
+ * unsorted keys (sorted inside the launch) and clf_out = the other slot.  batch->cnt / next->cnt: two different buffers.
+ * batch: batch t (everything);  next: batch t + 1 (everything);  st: every member but wg_scratch (acts: written by the tiles);
+ * sel: all of it;  out: logits, center, row_loss.
  * PCG_E_UNSUPPORTED where pcg_dense_select_blocks(g, emb, B) is 0. */
-int pcg_dense_select_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
-                           const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt, const void *plan,
-                           float inv_count, const float *clf_in, float *logits, float *center, float *row_loss, float *acts,
-                           int32_t act_ld, const int32_t *next_ids, const int32_t *next_labels, int32_t next_B, int32_t *next_cnt,
-                           const void *next_plan, float next_inv_count, float *clf_out, float *s0, uint64_t *pos_keys,
-                           const double *thresholds, const double *rho, int32_t add_self, void *workspace, int64_t list_capacity,
-                           uint32_t *status, uint32_t *sync_words, float *clf_next, const float *slabs, int32_t *step_counter,
-                           float lambda_1, double lr, double beta1, double beta2, double eps, double weight_decay, void *stream);
+int pcg_dense_select_train(const pcg_graph_desc *g, const pcg_train_state *st, const pcg_select_ws *sel, const pcg_batch *batch,
+                           const pcg_batch *next, const float *agg, int32_t agg_stride, const float *clf_in,
+                           const pcg_dense_out *out, float *clf_out, float *s0, uint64_t *pos_keys, void *stream);
 /* select workgroups of the fused launch for a dense batch of B rows (on the current device), or 0: that batch's steps keep three
  * launches (more than PCG_PIPE_MAX_TILES = 128 tiles of 16 rows by default, rows beyond the select kernel's LDS keys, feature
  * rows of more than 256 floats, a dense shape that does not fit). */
@@ -332,32 +387,25 @@ int32_t pcg_dense_select_blocks(const pcg_graph_desc *g, int32_t emb, int32_t B)
  *             pcg_dense_select_ahead(batch t, batch t + 1, classifier batch t + 2)
  *     last:   pcg_choose_train_part(2, last, score_next = 0), pcg_train_dense(adam_clf = 3, last, sort_keys = NULL)
  * The fused launch: batch t's tiles (clf_in = slot t % 3), batch t + 1's select as pcg_choose_train_part(1) with keys_sorted = 1
- * (s0 / pos_keys: batch t + 1's buffers), the classifier step of batch clf_ids / clf_labels / clf_B (Adam's t = count + 3; it
+ * (s0 / pos_keys: batch t + 1's buffers), the classifier step of clf_batch (its ids, labels, B, inv_count; Adam's t = count + 3; it
  * counts the step for the tiles; clf_out = slot (t + 2) % 3), and riders that rank-sort sort_keys' raw half - formed by the
- * gather launch in front - into its sorted half (sort_keys != pos_keys; nothing in the launch reads them).  clf_ids == NULL: no
+ * gather launch in front - into its sorted half (sort_keys != pos_keys; nothing in the launch reads them).  clf_batch->ids == NULL: no
  * classifier step (the end of a sequence) - the tiles count the step; sort_keys == NULL: no riders (n_pos <= 16384 with them).
  * PCG_E_UNSUPPORTED where pcg_dense_select_blocks(g, emb, B) is 0; pcg_dense_select_ahead_ok(g, emb, largest B of the sequence)
  * is the caller's test for choosing this schedule. */
-int pcg_dense_select_ahead(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
-                           const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt, const void *plan,
-                           float inv_count, const float *clf_in, float *logits, float *center, float *row_loss, float *acts,
-                           int32_t act_ld, const int32_t *next_ids, const int32_t *next_labels, int32_t next_B, int32_t *next_cnt,
-                           const void *next_plan, float next_inv_count, float *clf_out, float *s0, uint64_t *pos_keys,
-                           const double *thresholds, const double *rho, int32_t add_self, void *workspace, int64_t list_capacity,
-                           uint32_t *status, uint32_t *sync_words, float *clf_next, const float *slabs, int32_t *step_counter,
-                           float lambda_1, double lr, double beta1, double beta2, double eps, double weight_decay,
-                           const int32_t *clf_ids, const int32_t *clf_labels, int32_t clf_B, float clf_inv_count, uint64_t *sort_keys,
-                           void *stream);
+int pcg_dense_select_ahead(const pcg_graph_desc *g, const pcg_train_state *st, const pcg_select_ws *sel, const pcg_batch *batch,
+                           const pcg_batch *next, const pcg_batch *clf_batch, const float *agg, int32_t agg_stride,
+                           const float *clf_in, const pcg_dense_out *out, float *clf_out, float *s0, uint64_t *pos_keys,
+                           uint64_t *sort_keys, void *stream);
 /* 1: the fused launch of a batch of B rows has room for the sort riders (a workgroup per 64 train positives, at most four per
  * tile: they start on the CUs the tiles leave) beside the tiles and pcg_dense_select_blocks' select workgroups; a graph
  * without train positives needs none.  0: the sequence keeps pcg_dense_select_train's schedule. */
 int32_t pcg_dense_select_ahead_ok(const pcg_graph_desc *g, int32_t emb, int32_t B);
 /* The label classifier's step for one batch as a launch of its own (select_rows' classifier workgroup alone): clf_next <- the
  * classifier after the step; theta's classifier and clf_out (if not NULL) <- the one before it; Adam's t = step_counter[0] +
- * t_ahead (>= 1); the count is left as it is.  slabs / sync_words: as pcg_choose_gather_train's (batches of more than 1024 rows). */
-int pcg_clf_step(const pcg_graph_desc *g, const int32_t *ids, const int32_t *labels, int32_t B, float *theta, float *m, float *v,
-                 int32_t emb, float *clf_next, float *clf_out, const float *slabs, const int32_t *step_counter, uint32_t *sync_words,
-                 float lambda_1, float inv_count, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t t_ahead,
+ * t_ahead (>= 1); the count is left as it is.  batch: ids, labels, B, inv_count;  st: theta, m, v, step_counter, clf_next, emb,
+ * lambda_1, hyper, and slabs / sync_words as pcg_choose_gather_train uses them (batches of more than 1024 rows). */
+int pcg_clf_step(const pcg_graph_desc *g, const pcg_batch *batch, const pcg_train_state *st, float *clf_out, int32_t t_ahead,
                  void *stream);
 int32_t pcg_sync_words_count(void);                 /* uint32 words of a `sync_words` buffer (zero-initialised ONCE by the caller; the
                                                         kernels leave every word but [1], [2] zero between launches) */
@@ -451,35 +499,33 @@ int pcg_dense_step(const pcg_graph_desc *g, const float *theta, int32_t emb,
                    float *logits, float *center, float *combined, float *row_loss,
                    float *slabs, int32_t *step_counter, void *stream);
 int pcg_adam_step(float *theta, float *m, float *v, const float *slabs, int32_t n_slabs, int64_t n_params,
-                  const int32_t *step_counter, double lr, double beta1, double beta2, double eps,
-                  double weight_decay, float *grad_out, int32_t apply, void *stream);
+                  const int32_t *step_counter, const pcg_adam_hyper *hyper, float *grad_out, int32_t apply, void *stream);
 
 /* The training step's tail and front with Adam taken off the critical path (src/model_handler.py:149-153).
  *
- * pcg_train_dense = pcg_dense_step, plus
- *   - workspace != NULL (with cnt, plan, list_capacity as given to pcg_choose_gather_planned): aggregates of rows the gather
- *     left as partial sums are added up here (no combine launch);
+ * pcg_train_dense = pcg_dense_step over st (theta, emb, lambda_1, slabs, step_counter), batch and out, plus
+ *   - sel->workspace != NULL (with batch->cnt, batch->plan, sel->list_capacity as given to pcg_choose_gather_planned; nothing
+ *     else of sel is read): aggregates of rows the gather left as partial sums are added up here (no combine launch);
  *   - adam_clf == 2 (training; slabs, sync_words required): gradient slabs only, marked as waiting (sync_words[1] = 1,
  *     sync_words[2] = #slabs) for the deferred update of the next pcg_choose_gather_train / pcg_adam_flush; the label
  *     classifier's own step is pcg_choose_gather_train's (its share of the slabs is written but not used);
- *   - adam_clf == 3 (training; acts, act_ld, sync_words required; slabs unused): NO gradient slabs.  The launch - one workgroup
+ *   - adam_clf == 3 (training; st->acts, act_ld, sync_words required; slabs unused): NO gradient slabs.  The launch - one workgroup
  *     per 16 batch rows - runs forward, loss and the activation gradients and leaves, TRANSPOSED (one batch row per column,
  *     act_ld floats per row, act_ld >= B rounded up to 16, a multiple of 4; acts 16-byte aligned, pcg_wgrad_act_rows(...) rows):
  *     [self | h_r] , agg_r, dcomb, dh_r, combined, dlogits, dcentre - what every weight gradient is a GEMM over the batch of
  *     (src/layers.py:625-629, 284-289; src/model.py:54-61).  It marks them as waiting (sync_words[1] = 2, sync_words[2] = B / 16
- *     rounded up) for the next pcg_choose_gather_train(acts) / pcg_adam_flush(acts), whose workgroups run those GEMMs (f32 MFMA,
+ *     rounded up) for the next pcg_choose_gather_train / pcg_adam_flush over the same acts, whose workgroups run those GEMMs (f32 MFMA,
  *     fixed summation order) and apply Adam tile by tile.  adam_clf == 4: the same without marking (pcg_wgrad follows).
  *     sort_keys != NULL (adam_clf == 3 only; the pos_keys buffer whose scratch half holds the NEXT step's unsorted train-pos keys,
  *     formed by the pcg_choose_gather_train(score_next) before this launch): if pcg_dense_sorts_keys(B, n_pos) the launch carries
  *     ceil(n_pos / 64) more workgroups that rank-sort them into the first half (src/layers.py:683-691's order) - one workgroup
  *     per 16 rows leaves most CUs of a batch of <= ~3000 rows idle; the next pcg_choose_gather_train is then told keys_sorted;
- *   - adam_clf == 1 (training: slabs, m, v, sync_words required): the workgroup that arrives last (device-scope ticket,
+ *   - adam_clf == 1 (training: slabs, m, v, sync_words, hyper required): the workgroup that arrives last (device-scope ticket,
  *     write-through partial gradients) sums the label classifier's gradient over the tiles in tile order and applies
  *     Adam to those 2 * feat_dim + 2 parameters - the only ones the next step's score pass reads - and the launch marks the
  *     slabs as holding a gradient the OTHER parameters have not seen yet: sync_words[1] = 1, sync_words[2] = #slabs.
- *   sync_words: pcg_sync_words_count() zero-initialised uint32 device words owned by the caller ([0] arrival ticket, 0 between
- *     launches; [3] and the words behind it belong to pcg_choose_gather_planned's in-kernel sort).
- * pcg_step_front_train = pcg_step_front(train_flag = 1) reading the label classifier from theta, with that deferred update
+ * pcg_step_front_train = pcg_step_front(train_flag = 1; batch: ids, labels, B; sel: all of it) reading the label classifier from
+ *   st->theta, with that deferred update (st: theta, m, v, emb, slabs, step_counter, sync_words, hyper; pcg_step_scores_train: the same)
  *   (parameters [0, offset of label_clf.weight), same arithmetic and summation order as pcg_adam_step) applied by extra
  *   workgroups beside the score pass when sync_words[1] is set; its second launch clears sync_words[1].
  * pcg_step_scores_train = the front of a training step whose plan exists already (pcg_plan_batches), ONE launch:
@@ -490,13 +536,11 @@ int pcg_adam_step(float *theta, float *m, float *v, const float *slabs, int32_t 
  *   scored (bit for bit the scores pcg_score_table gives them); the other entries of s0 keep whatever they held - the batch's
  *   selection never reads them.  For graphs whose feature table is far larger than what a batch touches.
  * pcg_adam_flush applies a still-deferred update now (two or three small launches) - before parameters are read or saved
- *   (slabs may be NULL when acts is given: a step of adam_clf = 3 is applied by the weight-gradient GEMMs, sync_words[1] == 2);
- *   clf_next != NULL (the pcg_choose_gather_train step): the stepped label classifier is copied into theta [p_end, n_params) too,
+ *   (st: every member but lambda_1; slabs may be NULL when acts is given: a step of adam_clf = 3 is applied by the weight-gradient
+ *   GEMMs, sync_words[1] == 2); st->clf_next != NULL (the pcg_choose_gather_train step): the stepped label classifier is copied into theta [p_end, n_params) too,
  *   if an update was pending. */
-int pcg_step_scores_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, float *s0,
-                          uint64_t *pos_keys, const float *slabs, const int32_t *step_counter, uint32_t *sync_words,
-                          double lr, double beta1, double beta2, double eps, double weight_decay, const uint8_t *touched,
-                          void *stream);
+int pcg_step_scores_train(const pcg_graph_desc *g, const pcg_train_state *st, float *s0, uint64_t *pos_keys,
+                          const uint8_t *touched, void *stream);
 /* Which rows the batches nodes[s * B, min((s + 1) * B, n_total)) can read the score of (src/layers.py:226-237 scores exactly
  * `unique_nodes` = batch + neighbours): one byte map per batch at maps + s * map_stride (map_stride >= pcg_touched_bytes(n_nodes),
  * a multiple of 16; maps 16-byte aligned) - zeroed, then 1 for every centre of the batch, every neighbour it has in any
@@ -514,12 +558,9 @@ int pcg_mark_touched(const pcg_graph_desc *g, const int32_t *nodes, int32_t n_to
  * centres and the train positives are marked afterwards.  Two launches; the same maps as pcg_mark_touched, bit for bit. */
 int pcg_mark_touched_planned(const pcg_graph_desc *g, const int32_t *nodes, int32_t n_total, int32_t B, const void *plans,
                              int64_t plan_stride, int64_t list_capacity, uint8_t *maps, int64_t map_stride, void *stream);
-int pcg_train_dense(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
-                    const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt,
-                    const void *workspace, const void *plan, int64_t list_capacity, float lambda_1, float inv_count, float *logits,
-                    float *center, float *combined, float *row_loss, float *slabs, int32_t *step_counter,
-                    uint32_t *sync_words, double lr, double beta1, double beta2, double eps, double weight_decay,
-                    int32_t adam_clf, float *acts, int32_t act_ld, uint64_t *sort_keys, void *stream);
+int pcg_train_dense(const pcg_graph_desc *g, const pcg_train_state *st, const pcg_batch *batch, const float *agg,
+                    int32_t agg_stride, const pcg_select_ws *sel, const pcg_dense_out *out, int32_t adam_clf, uint64_t *sort_keys,
+                    void *stream);
 int32_t pcg_dense_sorts_keys(int32_t B, int32_t n_pos);   /* 1: the launch above (adam_clf = 3, sort_keys) sorts n_pos keys at batch B */
 /* Whole-set inference (test mode, forward only): gnn logits of nodes ids[0 .. n) -> out_logits [n][2] and, if out_center is not
  * NULL, the label-aware (centre) logits -> out_center [n][2].  ONE call enqueues everything: one score pass of theta's label
@@ -662,12 +703,8 @@ int pcg_attr_set(const pcg_graph_desc *g, const float *theta, int32_t emb, const
                  void *stream);
 int pcg_attr_neighbours(const pcg_graph_desc *g, const int64_t *flat_offsets, const int32_t *ids, int32_t n_rel, int32_t n,
                         const float *d_agg, float *out, uint32_t *status, void *stream);
-int pcg_step_front_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, float *s0,
-                         uint64_t *pos_keys, const int32_t *nodes, const int32_t *labels, int32_t B,
-                         const double *thresholds, const double *rho, int32_t add_self, void *workspace,
-                         int64_t list_capacity, uint32_t *status, const float *slabs, const int32_t *step_counter,
-                         uint32_t *sync_words, double lr, double beta1, double beta2, double eps, double weight_decay,
-                         void *stream);
+int pcg_step_front_train(const pcg_graph_desc *g, const pcg_train_state *st, float *s0, uint64_t *pos_keys, const pcg_batch *batch,
+                         const pcg_select_ws *sel, void *stream);
 /* The optimizer of a data-parallel / partitioned step, whose gradient passes through an all-reduce: pcg_grad_reduce sums the
  * slabs (tile order) into grad_out and sets flag[0] ("a gradient is waiting"); after the collective, pcg_adam_apply_pending - at
  * the head of the NEXT step's launches, or on its own before parameters are read - applies torch.optim.Adam's update from grad to
@@ -676,10 +713,10 @@ int pcg_step_front_train(const pcg_graph_desc *g, float *theta, float *m, float 
  * flag: one zero-initialised uint32 device word. */
 int pcg_grad_reduce(const float *slabs, int32_t n_slabs, int64_t n_params, float *grad_out, uint32_t *flag, void *stream);
 int pcg_adam_apply_pending(float *theta, float *m, float *v, const float *grad, int64_t n_params, const int32_t *step_counter,
-                           uint32_t *flag, int32_t clear, double lr, double beta1, double beta2, double eps, double weight_decay,
-                           void *stream);
+                           uint32_t *flag, int32_t clear, const pcg_adam_hyper *hyper, void *stream);
 /* The partitioned step's front and gather (pc-gnn_amd/dist.py; the reference has no distributed code).
- * pcg_step_scores_dist = pcg_step_scores with the optimizer riding in it, ONE launch behind the gradient all-reduce: if
+ * pcg_step_scores_dist = pcg_step_scores with the optimizer riding in it (st: theta, m, v, emb, step_counter, sync_words, hyper),
+ *   ONE launch behind the gradient all-reduce: if
  *   sync_words[1] == 1 (pcg_wgrad(flag_set) / pcg_grad_reduce) torch.optim.Adam's update from grad [n_params] (the all-reduced
  *   gradient) is applied to EVERY parameter by some workgroups while the others score rows [row_begin, row_end) ->
  *   s0_out[row_ids[row]] and form the train positives' unsorted keys (rows pos_row_base + i; pos_keys may be NULL) with the label
@@ -690,23 +727,21 @@ int pcg_adam_apply_pending(float *theta, float *m, float *v, const float *grad, 
  *   [ owned | train-pos | halo ] as they are read (table / counts / pos_ids / pos_idx as pcg_halo_lookup; the list is left as it
  *   is; an id in none of the three is skipped and sets overflow bit 4 in counts[128]); snap_dst != NULL: the launch also copies
  *   theta / m / v [clf_offset, clf_offset + clf_n) to snap_dst [3 * clf_n] - the snapshot the NEXT step's pcg_step_scores_dist reads. */
-int pcg_step_scores_dist(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const float *grad,
-                         const float *clf_snap, int64_t row_begin, int64_t row_end, float *s0_out, const int32_t *row_ids,
-                         uint64_t *pos_keys, int64_t pos_row_base, const int32_t *step_counter, uint32_t *sync_words, double lr,
-                         double beta1, double beta2, double eps, double weight_decay, void *stream);
+int pcg_step_scores_dist(const pcg_graph_desc *g, const pcg_train_state *st, const float *grad, const float *clf_snap,
+                         int64_t row_begin, int64_t row_end, float *s0_out, const int32_t *row_ids, uint64_t *pos_keys,
+                         int64_t pos_row_base, void *stream);
 int pcg_gather_lists_dist(const float *X, int32_t feat_dim, int32_t feat_stride, int64_t table_rows, int32_t n_rows,
                           const int32_t *cnt, const pcg_graph_desc *g, int32_t B, void *workspace, const void *plan,
                           int64_t list_capacity, float *agg, int32_t agg_stride, uint32_t *status, int32_t lo, int32_t hi,
                           int32_t n_local, const int32_t *pos_ids, const int32_t *pos_idx, int32_t n_pos, const uint32_t *table,
                           int64_t table_slots, uint32_t *counts, int32_t halo_cap, int32_t halo_base, const float *theta,
                           const float *m, const float *v, int64_t clf_offset, int32_t clf_n, float *snap_dst, void *stream);
-int pcg_adam_flush(float *theta, float *m, float *v, const float *slabs, int32_t n_slabs, int64_t n_params, int64_t p_end,
-                   const int32_t *step_counter, uint32_t *sync_words, double lr, double beta1, double beta2, double eps,
-                   double weight_decay, const float *clf_next, const float *acts, int32_t act_ld, int32_t feat_dim, int32_t emb,
-                   int32_t n_rel, float *wg_scratch, void *stream);
+int pcg_adam_flush(const pcg_train_state *st, int32_t n_slabs, int64_t n_params, int64_t p_end, int32_t feat_dim, int32_t n_rel,
+                   void *stream);
 /* The weight gradients of pcg_train_dense(adam_clf = 3 / 4)'s transposed activations as GEMMs over the batch (B rows; one
  * 256-thread workgroup per 16 x 16 tile of a weight matrix, its four waves a quarter of the batch each, partial tiles added in
- * wave order): grad_out [n_params] (may be NULL) gets the gradient, apply != 0 applies torch.optim.Adam's update (coupled weight
+ * wave order; st: acts, act_ld, emb, wg_scratch, hyper, and - required only if apply - theta, m, v, step_counter): grad_out
+ * [n_params] (may be NULL) gets the gradient, apply != 0 applies torch.optim.Adam's update (coupled weight
  * decay; t = step_counter[0]) to the tile's parameters.  with_clf == 0 leaves the label classifier's 2 * feat_dim + 2 entries
  * alone (its step is pcg_choose_gather_train's).  Batches beyond 1024 rows: a tile is shared by one workgroup per 1024 rows, whose
  * partial tiles meet in wg_scratch (pcg_wgrad_scratch_bytes(feat_dim, emb, n_rel, largest B), zero-initialised ONCE by the caller:
@@ -716,9 +751,8 @@ int pcg_adam_flush(float *theta, float *m, float *v, const float *slabs, int32_t
  * is waiting" for pcg_step_scores_dist / pcg_adam_apply_pending.  Replaces src/model_handler.py:152-153 for those parameters. */
 int64_t pcg_wgrad_act_rows(int32_t feat_dim, int32_t emb, int32_t n_rel);
 int64_t pcg_wgrad_scratch_bytes(int32_t feat_dim, int32_t emb, int32_t n_rel, int32_t B);
-int pcg_wgrad(const float *acts, int32_t act_ld, int32_t B, int32_t feat_dim, int32_t emb, int32_t n_rel, float *theta, float *m,
-              float *v, const int32_t *step_counter, double lr, double beta1, double beta2, double eps, double weight_decay,
-              float *grad_out, int32_t apply, int32_t with_clf, float *wg_scratch, uint32_t *flag_set, void *stream);
+int pcg_wgrad(const pcg_train_state *st, int32_t B, int32_t feat_dim, int32_t n_rel, float *grad_out, int32_t apply,
+              int32_t with_clf, uint32_t *flag_set, void *stream);
 
 /* ---- multi-GPU halo exchange helpers (no counterpart in the reference) ----------
  * A rank of a partitioned run holds the table [ owned rows | train-pos rows | halo ]; CSR rows and selection lists hold

@@ -18,7 +18,7 @@ PCG_ST_SORT_OVERFLOW = 8
 PCG_ST_EVAL_INPUT = 16
 PCG_ST_RANK_MISMATCH = 32
 PCG_NORM_COUNT, PCG_NORM_SQRT_COUNT = 0, 1
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class GraphDesc(C.Structure):
@@ -40,10 +40,41 @@ class GraphDesc(C.Structure):
 _P, _I32, _I64, _U64, _F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double
 _G = C.POINTER(GraphDesc)
 
+
+# The parameter structs of the training entry points (include/pcgnn.h documents every member).  They hold raw addresses: whoever
+# builds one keeps the tensors and ctypes arrays it points into alive.  tests/test_cabi_exports.py checks each layout against
+# pcg_abi_layout.
+class AdamHyper(C.Structure):
+    _fields_ = [("lr", _F64), ("beta1", _F64), ("beta2", _F64), ("eps", _F64), ("weight_decay", _F64)]
+
+
+class TrainState(C.Structure):
+    _fields_ = [("theta", _P), ("m", _P), ("v", _P), ("step_counter", _P), ("sync_words", _P), ("clf_next", _P), ("slabs", _P),
+                ("acts", _P), ("wg_scratch", _P), ("emb", _I32), ("act_ld", _I32), ("lambda_1", C.c_float), ("_pad", _I32),
+                ("hyper", AdamHyper)]
+
+
+class SelectWs(C.Structure):
+    _fields_ = [("thresholds", C.POINTER(_F64)), ("rho", C.POINTER(_F64)), ("workspace", _P), ("status", _P),
+                ("list_capacity", _I64), ("add_self", _I32), ("_pad", _I32)]
+
+
+class Batch(C.Structure):
+    _fields_ = [("ids", _P), ("labels", _P), ("cnt", _P), ("plan", _P), ("B", _I32), ("inv_count", C.c_float)]
+
+
+class DenseOut(C.Structure):
+    _fields_ = [("logits", _P), ("center", _P), ("combined", _P), ("row_loss", _P)]
+
+
+ABI_STRUCTS = (AdamHyper, TrainState, SelectWs, Batch, DenseOut)     # pcg_abi_layout's `which`, in order
+_H, _ST, _SEL, _B, _OUT = (C.POINTER(t) for t in ABI_STRUCTS)
+
 # name -> (restype, argtypes); must list every symbol include/pcgnn.h declares
 PROTOTYPES = {
     "pcg_version": (C.c_char_p, []),
     "pcg_abi_version": (C.c_int, []),
+    "pcg_abi_layout": (_I32, [_I32, C.POINTER(_I64), _I32]),
     "pcg_score_table": (C.c_int, [_G, _P, _P, _I64, _I64, _P, _P]),
     "pcg_score_rows": (C.c_int, [_G, _P, _P, _P, _I32, _P, _P]),
     "pcg_pos_sort_capacity": (_I64, [_I32]),
@@ -64,23 +95,13 @@ PROTOTYPES = {
     "pcg_choose_select_planned": (C.c_int, [_G, _P, _P, _I32, _P, _P, _P, C.POINTER(_F64), C.POINTER(_F64), _I32, _I32,
                                             _P, _P, _P, _I64, _P, _P, _I64, _P]),
     "pcg_step_scores": (C.c_int, [_G, _P, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P]),
-    "pcg_choose_gather_train": (C.c_int, [_G, _P, _P, _I32, _P, _P, C.POINTER(_F64), C.POINTER(_F64), _I32, _P, _I32, _P, _P, _P,
-                                          _I64, _P, _P, _P, _P, _P, _I32, _P, _P, _P, C.c_float, C.c_float, _F64, _F64, _F64, _F64,
-                                          _F64, _I32, _P, _P, _I32, _P, _I32, _P]),
-    "pcg_choose_train_part": (C.c_int, [_I32, _G, _P, _P, _I32, _P, _P, C.POINTER(_F64), C.POINTER(_F64), _I32, _P, _I32, _P, _P, _P,
-                                        _I64, _P, _P, _P, _P, _P, _I32, _P, _P, _P, C.c_float, C.c_float, _F64, _F64, _F64, _F64,
-                                        _F64, _I32, _P, _P, _I32, _P, _I32, _P, _P]),
-    "pcg_dense_select_train": (C.c_int, [_G, _P, _P, _P, _I32, _P, _P, _I32, _P, _I32, _P, _P, C.c_float, _P, _P, _P, _P, _P, _I32,
-                                         _P, _P, _I32, _P, _P, C.c_float, _P, _P, _P, C.POINTER(_F64), C.POINTER(_F64), _I32, _P,
-                                         _I64, _P, _P, _P, _P, _P, C.c_float, _F64, _F64, _F64, _F64, _F64, _P]),
+    "pcg_choose_gather_train": (C.c_int, [_G, _B, _P, _P, _SEL, _P, _I32, _ST, _I32, _P, _I32, _P]),
+    "pcg_choose_train_part": (C.c_int, [_I32, _G, _B, _P, _P, _SEL, _P, _I32, _ST, _I32, _P, _I32, _P, _P]),
+    "pcg_dense_select_train": (C.c_int, [_G, _ST, _SEL, _B, _B, _P, _I32, _P, _OUT, _P, _P, _P, _P]),
     "pcg_dense_select_blocks": (_I32, [_G, _I32, _I32]),
-    "pcg_dense_select_ahead": (C.c_int, [_G, _P, _P, _P, _I32, _P, _P, _I32, _P, _I32, _P, _P, C.c_float, _P, _P, _P, _P, _P, _I32,
-                                         _P, _P, _I32, _P, _P, C.c_float, _P, _P, _P, C.POINTER(_F64), C.POINTER(_F64), _I32, _P,
-                                         _I64, _P, _P, _P, _P, _P, C.c_float, _F64, _F64, _F64, _F64, _F64, _P, _P, _I32, C.c_float,
-                                         _P, _P]),
+    "pcg_dense_select_ahead": (C.c_int, [_G, _ST, _SEL, _B, _B, _B, _P, _I32, _P, _OUT, _P, _P, _P, _P, _P]),
     "pcg_dense_select_ahead_ok": (_I32, [_G, _I32, _I32]),
-    "pcg_clf_step": (C.c_int, [_G, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, C.c_float, C.c_float, _F64, _F64, _F64, _F64,
-                               _F64, _I32, _P]),
+    "pcg_clf_step": (C.c_int, [_G, _B, _ST, _P, _I32, _P]),
     "pcg_choose_plan_bytes": (_I64, [_G, _I32, _I64]),
     "pcg_choose_data_bytes": (_I64, [_G, _I32, _I64]),
     "pcg_plan_batches": (C.c_int, [_G, _P, _P, _I32, _I32, C.POINTER(_F64), C.POINTER(_F64), _I32, _I32, _P, _I64, _I64, _P, _P,
@@ -94,7 +115,7 @@ PROTOTYPES = {
     "pcg_sync_words_count": (_I32, []),
     "pcg_aggregate_lists_planned": (C.c_int, [_P, _I32, _I32, _I64, _I32, _P, _G, _I32, _P, _P, _I64, _I32, _P, _I32, _P, _P]),
     "pcg_gather_lists_planned": (C.c_int, [_P, _I32, _I32, _I64, _I32, _P, _G, _I32, _P, _P, _I64, _P, _I32, _P, _P]),
-    "pcg_step_scores_train": (C.c_int, [_G, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _F64, _F64, _F64, _F64, _F64, _P, _P]),
+    "pcg_step_scores_train": (C.c_int, [_G, _ST, _P, _P, _P, _P]),
     "pcg_touched_bytes": (_I64, [_I64]),
     "pcg_mark_touched": (C.c_int, [_G, _P, _I32, _I32, _P, _I64, _P, _P]),
     "pcg_mark_touched_planned": (C.c_int, [_G, _P, _I32, _I32, _P, _I64, _I64, _P, _I64, _P]),
@@ -103,8 +124,7 @@ PROTOTYPES = {
     "pcg_choose_gather_planned": (C.c_int, [_G, _P, _P, _I32, _P, _P, _P, C.POINTER(_F64), C.POINTER(_F64), _I32, _I32,
                                             _P, _I32, _P, _P, _P, _I64, _P, _P, _P]),
     "pcg_gather_lists": (C.c_int, [_P, _I32, _I32, _I64, _I32, _P, _G, _I32, _P, _I64, _P, _I32, _P, _P]),
-    "pcg_train_dense": (C.c_int, [_G, _P, _P, _P, _I32, _P, _P, _I32, _P, _I32, _P, _P, _P, _I64, C.c_float, C.c_float, _P, _P, _P,
-                                  _P, _P, _P, _P, _F64, _F64, _F64, _F64, _F64, _I32, _P, _I32, _P, _P]),
+    "pcg_train_dense": (C.c_int, [_G, _ST, _B, _P, _I32, _SEL, _OUT, _I32, _P, _P]),
     "pcg_dense_sorts_keys": (_I32, [_I32, _I32]),
     "pcg_infer_workspace_bytes": (_I64, [_G, _I32, _I32, _I64]),
     "pcg_infer_set": (C.c_int, [_G, _P, _I32, _P, _I32, _I32, _P, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P]),
@@ -123,17 +143,14 @@ PROTOTYPES = {
     "pcg_attr_neighbours": (C.c_int, [_G, _P, _P, _I32, _I32, _P, _P, _P, _P]),
     "pcg_eval_workspace_bytes": (_I64, [_I64, _I32]),
     "pcg_eval_counts": (C.c_int, [_P, _P, _I64, _P, _I32, _P, _P, _P, _P]),
-    "pcg_step_front_train": (C.c_int, [_G, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, C.POINTER(_F64), C.POINTER(_F64), _I32, _P,
-                                       _I64, _P, _P, _P, _P, _F64, _F64, _F64, _F64, _F64, _P]),
+    "pcg_step_front_train": (C.c_int, [_G, _ST, _P, _P, _B, _SEL, _P]),
     "pcg_grad_reduce": (C.c_int, [_P, _I32, _I64, _P, _P, _P]),
-    "pcg_adam_apply_pending": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _I32, _F64, _F64, _F64, _F64, _F64, _P]),
-    "pcg_adam_flush": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _I64, _P, _P, _F64, _F64, _F64, _F64, _F64, _P, _P, _I32, _I32, _I32,
-                                 _I32, _P, _P]),
+    "pcg_adam_apply_pending": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _I32, _H, _P]),
+    "pcg_adam_flush": (C.c_int, [_ST, _I32, _I64, _I64, _I32, _I32, _P]),
     "pcg_wgrad_act_rows": (_I64, [_I32, _I32, _I32]),
     "pcg_wgrad_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
-    "pcg_wgrad": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _F64, _F64, _F64, _F64, _F64, _P, _I32, _I32, _P, _P, _P]),
-    "pcg_step_scores_dist": (C.c_int, [_G, _P, _P, _P, _I32, _P, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _F64, _F64, _F64, _F64, _F64,
-                                       _P]),
+    "pcg_wgrad": (C.c_int, [_ST, _I32, _I32, _I32, _P, _I32, _I32, _P, _P]),
+    "pcg_step_scores_dist": (C.c_int, [_G, _ST, _P, _P, _I64, _I64, _P, _P, _P, _I64, _P]),
     "pcg_gather_lists_dist": (C.c_int, [_P, _I32, _I32, _I64, _I32, _P, _G, _I32, _P, _P, _I64, _P, _I32, _P, _I32, _I32, _I32, _P, _P,
                                         _I32, _P, _I64, _P, _I32, _I32, _P, _P, _P, _I64, _I32, _P, _P]),
     "pcg_debug_set_stamps": (None, [_P]),
@@ -153,7 +170,7 @@ PROTOTYPES = {
     "pcg_dense_n_tiles": (_I32, [_I32]),
     "pcg_dense_step": (C.c_int, [_G, _P, _I32, _P, _P, _I32, _P, _I32, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P,
                                  _P]),
-    "pcg_adam_step": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _P, _F64, _F64, _F64, _F64, _F64, _P, _I32, _P]),
+    "pcg_adam_step": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _P, _H, _P, _I32, _P]),
 }
 
 _lib = None

@@ -929,53 +929,43 @@ int pcg_step_front_b(const pcg_graph_desc *g, const float *s0, uint64_t *pos_key
                    list_capacity, status, nullptr, center_s0_out, center_id_offset, stream);
 }
 
+// the deferred Adam update of parameters [0, p_end) from `slabs` (per-tile gradient slabs, or ONE all-reduced gradient) over an
+// engine's state; pending = sync_words + 1
+static pcg::DeferredAdam deferred_adam(const pcg_train_state *st, const float *slabs, int64_t n_params, int64_t p_end) {
+    return {st->theta, st->m, st->v, slabs, n_params, p_end, st->step_counter, st->sync_words + 1, pcg::adam_hyper(st->hyper)};
+}
+
 /* pcg_step_front of a TRAINING step, with the previous step's deferred Adam update riding along the score pass */
-int pcg_step_front_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, float *s0, uint64_t *pos_keys,
-                         const int32_t *nodes, const int32_t *labels, int32_t B, const double *thresholds, const double *rho,
-                         int32_t add_self, void *workspace, int64_t list_capacity, uint32_t *status, const float *slabs,
-                         const int32_t *step_counter, uint32_t *sync_words, double lr, double beta1, double beta2, double eps,
-                         double weight_decay, void *stream) {
-    if (!g || !theta || !m || !v || !slabs || !step_counter || !sync_words || B < 1) return PCG_E_ARG;
-    const int64_t n_params = pcg_dense_n_params(g->feat_dim, emb, g->n_rel);
-    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, emb, g->n_rel, 3, 0), o_b = pcg_dense_param_offset(g->feat_dim, emb, g->n_rel, 4, 0);
+int pcg_step_front_train(const pcg_graph_desc *g, const pcg_train_state *st, float *s0, uint64_t *pos_keys, const pcg_batch *batch,
+                         const pcg_select_ws *sel, void *stream) {
+    if (!g || !st || !batch || !sel) return PCG_E_ARG;
+    if (!st->theta || !st->m || !st->v || !st->slabs || !st->step_counter || !st->sync_words || batch->B < 1) return PCG_E_ARG;
+    const int64_t n_params = pcg_dense_n_params(g->feat_dim, st->emb, g->n_rel);
+    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 3, 0), o_b = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 4, 0);
     if (n_params < 0 || o_clf < 0) return PCG_E_ARG;
-    pcg::DeferredAdam ad;
-    ad.theta = theta; ad.m = m; ad.v = v;
-    ad.slabs = slabs;
-    ad.n_params = n_params;
-    ad.p_end = o_clf;
-    ad.step_counter = step_counter;
-    ad.pending = sync_words + 1;
-    ad.h = {(float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay};
-    const int rc = front_a(g, theta + o_clf, theta + o_b, 0, g->n_nodes, s0, nullptr, pos_keys, nodes, labels, B, thresholds, rho, 1, add_self,
-                           workspace, list_capacity, status, &ad, stream);
+    const pcg::DeferredAdam ad = deferred_adam(st, st->slabs, n_params, o_clf);
+    const int rc = front_a(g, st->theta + o_clf, st->theta + o_b, 0, g->n_nodes, s0, nullptr, pos_keys, batch->ids, batch->labels, batch->B,
+                           sel->thresholds, sel->rho, 1, sel->add_self, sel->workspace, sel->list_capacity, sel->status, &ad, stream);
     if (rc != PCG_OK) return rc;
-    return front_b(g, s0, pos_keys, 1, nodes, labels, B, thresholds, rho, 1, add_self, workspace, list_capacity, status,
-                   sync_words + 1, nullptr, 0, stream);
+    return front_b(g, s0, pos_keys, 1, batch->ids, batch->labels, batch->B, sel->thresholds, sel->rho, 1, sel->add_self, sel->workspace,
+                   sel->list_capacity, sel->status, st->sync_words + 1, nullptr, 0, stream);
 }
 
 /* The front of a training step whose plan exists already (pcg_plan_batches): ONE launch
  *   [train-pos keys from their feature rows || the previous step's deferred Adam update || score pass over the table]
  * and no sort: pcg_choose_gather_planned(..., sync_words) sorts the keys inside the select kernel.  More than RANK_MAX train
  * positives: the bucket sort's own launches follow here and the keys are sorted on return. */
-int pcg_step_scores_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, float *s0, uint64_t *pos_keys,
-                          const float *slabs, const int32_t *step_counter, uint32_t *sync_words, double lr, double beta1,
-                          double beta2, double eps, double weight_decay, const uint8_t *touched, void *stream) {
-    if (!g || !theta || !m || !v || !slabs || !step_counter || !sync_words) return PCG_E_ARG;
+int pcg_step_scores_train(const pcg_graph_desc *g, const pcg_train_state *st, float *s0, uint64_t *pos_keys, const uint8_t *touched,
+                          void *stream) {
+    if (!g || !st) return PCG_E_ARG;
+    if (!st->theta || !st->m || !st->v || !st->slabs || !st->step_counter || !st->sync_words) return PCG_E_ARG;
     if (g->n_pos > 0 && (!pos_keys || !g->train_pos)) return PCG_E_ARG;
-    const int64_t n_params = pcg_dense_n_params(g->feat_dim, emb, g->n_rel);
-    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, emb, g->n_rel, 3, 0), o_b = pcg_dense_param_offset(g->feat_dim, emb, g->n_rel, 4, 0);
+    const int64_t n_params = pcg_dense_n_params(g->feat_dim, st->emb, g->n_rel);
+    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 3, 0), o_b = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 4, 0);
     if (n_params < 0 || o_clf < 0) return PCG_E_ARG;
-    pcg::DeferredAdam ad;
-    ad.theta = theta; ad.m = m; ad.v = v;
-    ad.slabs = slabs;
-    ad.n_params = n_params;
-    ad.p_end = o_clf;
-    ad.step_counter = step_counter;
-    ad.pending = sync_words + 1;
-    ad.h = {(float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay};
-    const int rc = front_a(g, theta + o_clf, theta + o_b, 0, g->n_nodes, s0, nullptr, pos_keys, nullptr, nullptr, 0, nullptr, nullptr, 1, 0,
-                           nullptr, 1, nullptr, &ad, stream, true, sync_words + 3, -1, touched);
+    const pcg::DeferredAdam ad = deferred_adam(st, st->slabs, n_params, o_clf);
+    const int rc = front_a(g, st->theta + o_clf, st->theta + o_b, 0, g->n_nodes, s0, nullptr, pos_keys, nullptr, nullptr, 0, nullptr, nullptr, 1, 0,
+                           nullptr, 1, nullptr, &ad, stream, true, st->sync_words + 3, -1, touched);
     if (rc != PCG_OK) return rc;
     if (g->n_pos > pcg::RANK_MAX) return pcg_pos_sort(g, s0, pos_keys, stream);
     return PCG_OK;
@@ -1006,17 +996,17 @@ int pcg_step_scores(const pcg_graph_desc *g, const float *W, const float *b, int
  * parameters, m, v as of the last applied update (pcg_gather_lists_dist refreshes it every step; the caller after a flush) -
  * and the gradient.  The flag is cleared by the step's select launch (pcg_choose_select_planned(sync_words)); the launch zeroes
  * sync_words[3].  n_pos > 16384: pos_keys must be NULL (the caller sorts by its own launches). */
-int pcg_step_scores_dist(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const float *grad,
-                         const float *clf_snap, int64_t row_begin, int64_t row_end, float *s0_out, const int32_t *row_ids,
-                         uint64_t *pos_keys, int64_t pos_row_base, const int32_t *step_counter, uint32_t *sync_words, double lr,
-                         double beta1, double beta2, double eps, double weight_decay, void *stream) {
-    if (!g || !g->X || !theta || !m || !v || !grad || !clf_snap || !s0_out || !step_counter || !sync_words) return PCG_E_ARG;
+int pcg_step_scores_dist(const pcg_graph_desc *g, const pcg_train_state *st, const float *grad, const float *clf_snap,
+                         int64_t row_begin, int64_t row_end, float *s0_out, const int32_t *row_ids, uint64_t *pos_keys,
+                         int64_t pos_row_base, void *stream) {
+    if (!g || !st) return PCG_E_ARG;
+    if (!g->X || !st->theta || !st->m || !st->v || !grad || !clf_snap || !s0_out || !st->step_counter || !st->sync_words) return PCG_E_ARG;
     if (g->feat_dim < 1 || g->feat_dim > 512 || g->feat_stride < g->feat_dim || g->feat_stride % 4 != 0) return PCG_E_ARG;
     if ((reinterpret_cast<uintptr_t>(g->X) & 15u) != 0) return PCG_E_ARG;
     if (row_begin < 0 || row_end > g->n_nodes || row_begin > row_end) return PCG_E_ARG;
     if (pos_keys && (pos_row_base < 0 || pos_row_base + g->n_pos > g->n_nodes || g->n_pos > pcg::RANK_MAX)) return PCG_E_ARG;
-    const int64_t n_params = pcg_dense_n_params(g->feat_dim, emb, g->n_rel);
-    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, emb, g->n_rel, 3, 0);
+    const int64_t n_params = pcg_dense_n_params(g->feat_dim, st->emb, g->n_rel);
+    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 3, 0);
     if (n_params < 0 || o_clf < 0) return PCG_E_ARG;
     pcg::FrontDist f;
     f.g = *g;
@@ -1031,17 +1021,11 @@ int pcg_step_scores_dist(const pcg_graph_desc *g, float *theta, float *m, float 
     int n_key = raw ? (g->n_pos + rows_per_block - 1) / rows_per_block : 0;
     f.n_key_blocks = n_key > 256 ? 256 : n_key;
     f.n_adam_blocks = (int)((n_params + PCG_WAVE - 1) / PCG_WAVE);
-    f.ad.theta = theta; f.ad.m = m; f.ad.v = v;
-    f.ad.slabs = grad;
-    f.ad.n_params = n_params;
-    f.ad.p_end = n_params;
-    f.ad.step_counter = step_counter;
-    f.ad.pending = sync_words + 1;
-    f.ad.h = {(float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay};
+    f.ad = deferred_adam(st, grad, n_params, n_params);
     f.snap = clf_snap;
     f.nc = 2 * g->feat_dim + 2;
     f.off_clf = o_clf;
-    f.zero_word = sync_words + 3;
+    f.zero_word = st->sync_words + 3;
     const int n_score = (int)pcg::score_table_blocks(row_end - row_begin, g->feat_stride);
     hipLaunchKernelGGL(pcg::front_dist_kernel, dim3(f.n_adam_blocks + f.n_key_blocks + n_score), dim3(pcg::FRONT_COUNT_THREADS), 0,
                        static_cast<hipStream_t>(stream), f);
@@ -1106,26 +1090,47 @@ struct TrainParts {
     bool rank, one_launch;
     int64_t cap;
 };
-#define PCG_TRAIN_PARAMS const pcg_graph_desc *g, const int32_t *nodes, const int32_t *labels, int32_t B, float *s0, uint64_t *pos_keys, const double *thresholds, const double *rho, int32_t add_self, float *agg, int32_t agg_stride, int32_t *cnt, void *workspace, const void *plan, int64_t list_capacity, uint32_t *status, uint32_t *sync_words, float *theta, float *m, float *v, int32_t emb, float *clf_next, const float *slabs, const int32_t *step_counter, float lambda_1, float inv_count, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t score_next, const uint8_t *next_touched, const float *acts, int32_t act_ld, float *wg_scratch, int32_t keys_sorted
-#define PCG_TRAIN_ARGS g, nodes, labels, B, s0, pos_keys, thresholds, rho, add_self, agg, agg_stride, cnt, workspace, plan, list_capacity, status, sync_words, theta, m, v, emb, clf_next, slabs, step_counter, lambda_1, inv_count, lr, beta1, beta2, eps, weight_decay, score_next, next_touched, acts, act_ld, wg_scratch, keys_sorted
+
+// the label classifier's step for `batch` over an engine's state: everything of a ClfStep but who runs it and for whom
+// (clf_out, count_step, nodes / labels / B, t_ahead)
+static void clf_step_of(pcg::ClfStep &c, const pcg_train_state *st, const pcg_batch *batch, int64_t o_clf, int64_t n_params) {
+    c.clf_next = st->clf_next;
+    c.theta_clf = st->theta + o_clf;
+    c.m = st->m + o_clf;
+    c.v = st->v + o_clf;
+    c.step_counter = st->step_counter;
+    c.scale = batch->inv_count * st->lambda_1;
+    c.h = pcg::adam_hyper(st->hyper);
+    // (a slice of <= 1024 rows per workgroup, at most 8 of them; their gradients meet in the first slabs' classifier entries -
+    //  free until this step's dense launch writes them -, the arrival ticket is the dense kernel's unused one)
+    c.n_wg = (batch->B + 1023) / 1024 > 8 ? 8 : (batch->B + 1023) / 1024;
+    c.part = st->slabs + o_clf;
+    c.part_stride = n_params;
+    c.ticket = st->sync_words;
+}
 
 // wgrad_in_select: the A/B option PCG_WGRAD_IN_SELECT may move the weight-gradient workgroups into the select launch - only
 // when one call makes both launches (the split calls keep them in the gather launch)
-static int train_parts(TrainParts &t, bool wgrad_in_select, PCG_TRAIN_PARAMS) {
-    if (!g || B < 0) return PCG_E_ARG;
-    if (B == 0) return PCG_OK;
-    if (!g->X || !agg || !s0 || !sync_words || !theta || !m || !v || !clf_next || !slabs || !step_counter || !labels) return PCG_E_ARG;
-    if (acts && (act_ld < 16 || act_ld % 16 != 0 || (reinterpret_cast<uintptr_t>(acts) & 15u) != 0 || emb % 16 != 0)) return PCG_E_ARG;
-    if (acts && pcg::wgrad_kparts(act_ld / 16) > 1 && !wg_scratch) return PCG_E_ARG;
+// (the caller has checked g, batch, sel, st; B >= 1)
+static int train_parts(TrainParts &t, bool wgrad_in_select, const pcg_graph_desc *g, const pcg_batch *batch, float *s0,
+                       uint64_t *pos_keys, const pcg_select_ws *sel, const float *agg, const pcg_train_state *st, int32_t score_next,
+                       const uint8_t *next_touched, int32_t keys_sorted) {
+    const int32_t B = batch->B;
+    if (!g->X || !agg || !s0 || !st->sync_words || !st->theta || !st->m || !st->v || !st->clf_next || !st->slabs || !st->step_counter ||
+        !batch->labels)
+        return PCG_E_ARG;
+    if (st->acts && (st->act_ld < 16 || st->act_ld % 16 != 0 || (reinterpret_cast<uintptr_t>(st->acts) & 15u) != 0 || st->emb % 16 != 0))
+        return PCG_E_ARG;
+    if (st->acts && pcg::wgrad_kparts(st->act_ld / 16) > 1 && !st->wg_scratch) return PCG_E_ARG;
     if (g->feat_stride > 512) return PCG_E_UNSUPPORTED;
-    const int64_t n_params = pcg_dense_n_params(g->feat_dim, emb, g->n_rel);
-    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, emb, g->n_rel, 3, 0);
+    const int64_t n_params = pcg_dense_n_params(g->feat_dim, st->emb, g->n_rel);
+    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 3, 0);
     if (n_params < 0 || o_clf < 0) return PCG_E_ARG;
     pcg::ChooseArgs &a = t.a;
-    int rc = choose_args(a, g, nodes, labels, B, s0, nullptr, pos_keys, thresholds, rho, 1, add_self, cnt, workspace, list_capacity,
-                         status, false, plan);
+    int rc = choose_args(a, g, batch->ids, batch->labels, B, s0, nullptr, pos_keys, sel->thresholds, sel->rho, 1, sel->add_self, batch->cnt,
+                         sel->workspace, sel->list_capacity, sel->status, false, batch->plan);
     if (rc != PCG_OK) return rc;
-    if (!cnt) return PCG_E_ARG;
+    if (!batch->cnt) return PCG_E_ARG;
     const bool rank = t.rank = g->n_pos > 0 && g->n_pos <= pcg::RANK_MAX;
     const int64_t cap = t.cap = g->n_pos > 0 ? pcg_pos_sort_capacity(g->n_pos) / 2 : 0;
     // keys_sorted: pos_keys' first half holds THIS step's keys sorted already (the previous step's pcg_train_dense(sort_keys), or
@@ -1135,44 +1140,32 @@ static int train_parts(TrainParts &t, bool wgrad_in_select, PCG_TRAIN_PARAMS) {
         a.raw_keys = pos_keys + cap;
         a.sort_cap = (int32_t)cap;
         a.n_sort = (g->n_pos + PCG_WAVE - 1) / PCG_WAVE;
-        a.sort_done = sync_words + 3;
-        a.rank_acc = sync_words + 4;
-        a.group_ticket = sync_words + 4 + pcg::RANK_MAX;
+        a.sort_done = st->sync_words + 3;
+        a.rank_acc = st->sync_words + 4;
+        a.group_ticket = st->sync_words + 4 + pcg::RANK_MAX;
     }
-    const pcg::AdamHyper h = {(float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay};
-    a.clf.clf_next = clf_next;
-    a.clf.theta_clf = theta + o_clf;
-    a.clf.m = m + o_clf;
-    a.clf.v = v + o_clf;
-    a.clf.step_counter = step_counter;
-    a.clf.scale = inv_count * lambda_1;
-    a.clf.h = h;
-    // (a slice of <= 1024 rows per workgroup, at most 8 of them; their gradients meet in the first slabs' classifier entries -
-    //  free until this step's dense launch writes them -, the arrival ticket is the dense kernel's unused one)
-    a.clf.n_wg = (B + 1023) / 1024 > 8 ? 8 : (B + 1023) / 1024;
-    a.clf.part = const_cast<float *>(slabs) + o_clf;
-    a.clf.part_stride = n_params;
-    a.clf.ticket = sync_words;
+    clf_step_of(a.clf, st, batch, o_clf, n_params);
+    const pcg::AdamHyper h = a.clf.h;
     // the deferred update's weight-gradient workgroups (acts): in the gather launch (where they cost ~3 us of its ~10) - or, an
     // option that measured slower, as the first units of the select launch
     pcg::WgradArgs wga = {};
     int wg_tiles = 0;
-    if (acts) {
-        wga.acts = acts; wga.ld = act_ld;
-        wga.F = g->feat_dim; wga.E = emb; wga.R = g->n_rel;
-        wga.theta = theta; wga.m = m; wga.v = v;
-        wga.step_counter = step_counter;
+    if (st->acts) {
+        wga.acts = st->acts; wga.ld = st->act_ld;
+        wga.F = g->feat_dim; wga.E = st->emb; wga.R = g->n_rel;
+        wga.theta = st->theta; wga.m = st->m; wga.v = st->v;
+        wga.step_counter = st->step_counter;
         wga.h = h;
-        wga.pending = sync_words + 1;
-        wga.n_kblocks = act_ld / 16;             // (the batch size the engine's buffers were made for: the expected one)
-        wga.kparts = pcg::wgrad_kparts(act_ld / 16);
-        wga.tickets = reinterpret_cast<uint32_t *>(wg_scratch);
-        wga.partials = wg_scratch ? wg_scratch + (pcg::wgrad_tiles(g->feat_dim, emb, g->n_rel, 1) + 63) / 64 * 64 : nullptr;
+        wga.pending = st->sync_words + 1;
+        wga.n_kblocks = st->act_ld / 16;         // (the batch size the engine's buffers were made for: the expected one)
+        wga.kparts = pcg::wgrad_kparts(st->act_ld / 16);
+        wga.tickets = reinterpret_cast<uint32_t *>(st->wg_scratch);
+        wga.partials = st->wg_scratch ? st->wg_scratch + (pcg::wgrad_tiles(g->feat_dim, st->emb, g->n_rel, 1) + 63) / 64 * 64 : nullptr;
         wga.grad_out = nullptr;
         wga.flag_set = nullptr;
         wga.apply = 1;
         wga.with_clf = 0;
-        wg_tiles = pcg::wgrad_tiles(g->feat_dim, emb, g->n_rel, 0);
+        wg_tiles = pcg::wgrad_tiles(g->feat_dim, st->emb, g->n_rel, 0);
         // (A/B knob PCG_WGRAD_IN_SELECT=1.  Measured, YelpChi-like batch 1024: select_rows 16.2 -> 19.9 us, gather launch 10.5 -> 8.2:
         //  43.8 vs 42.9 us per step - the workgroups that start on their rows ~7 us late end the launch later than the gather's
         //  riders cost.  Off; profiles/r04/x_wgrad_in_select_yelp_bench.log)
@@ -1187,18 +1180,12 @@ static int train_parts(TrainParts &t, bool wgrad_in_select, PCG_TRAIN_PARAMS) {
         }
     }
     pcg::SideJob &sd = t.sd;
-    sd.ad.theta = theta; sd.ad.m = m; sd.ad.v = v;
-    sd.ad.slabs = slabs;
-    sd.ad.n_params = n_params;
-    sd.ad.p_end = o_clf;
-    sd.ad.step_counter = step_counter;
-    sd.ad.pending = sync_words + 1;
-    sd.ad.h = h;
-    sd.n_adam_blocks = acts ? 0 : (int)((o_clf + PCG_WAVE - 1) / PCG_WAVE);
+    sd.ad = deferred_adam(st, st->slabs, n_params, o_clf);
+    sd.n_adam_blocks = st->acts ? 0 : (int)((o_clf + PCG_WAVE - 1) / PCG_WAVE);
     // acts: the previous step's pcg_train_dense(adam_clf = 3) left activations, not slabs - the weight gradients are GEMMs over
     // its batch, each output tile's workgroup applying Adam to its own parameters (wgrad.h) - here unless the select launch did it
     sd.wg = wga;
-    sd.n_wgrad_blocks = (acts && a.n_wg_units == 0) ? wg_tiles * wga.kparts : 0;
+    sd.n_wgrad_blocks = (st->acts && a.n_wg_units == 0) ? wg_tiles * wga.kparts : 0;
     {
         static int prio = -1, off = -1;          // A/B knobs (timing experiments only: PCG_WGRAD_OFF=1 skips the update)
         if (prio < 0) {
@@ -1209,8 +1196,8 @@ static int train_parts(TrainParts &t, bool wgrad_in_select, PCG_TRAIN_PARAMS) {
         sd.wg_prio = prio;
         if (off) sd.n_wgrad_blocks = 0;
     }
-    sd.W = score_next ? clf_next : nullptr;
-    sd.bias = clf_next + 2 * g->feat_dim;
+    sd.W = score_next ? st->clf_next : nullptr;
+    sd.bias = st->clf_next + 2 * g->feat_dim;
     sd.s0 = s0;
     sd.touched = next_touched;
     // (the one-launch bucket sort - 16384 < n_pos <= 131072 - works on raw keys formed here too)
@@ -1220,27 +1207,30 @@ static int train_parts(TrainParts &t, bool wgrad_in_select, PCG_TRAIN_PARAMS) {
     int n_key = sd.raw_keys ? (g->n_pos + rows_per_block - 1) / rows_per_block : 0;
     sd.n_key_blocks = n_key > 256 ? 256 : n_key;
     sd.n_score_blocks = score_next ? (int)pcg::score_table_blocks(g->n_nodes, g->feat_stride) : 0;
-    sd.zero_word = sync_words + 3;
+    sd.zero_word = st->sync_words + 3;
     return PCG_OK;
 }
 
 // parts: 1 = the select launch, 2 = the gather launch (+ the sort of the next step's keys where that is a launch of its own), 3 = both
-static int train_launch(int parts, float *clf_out, PCG_TRAIN_PARAMS, void *stream) {
-    if (!g || B < 0) return PCG_E_ARG;
-    if (B == 0) return PCG_OK;
+static int train_launch(int parts, float *clf_out, const pcg_graph_desc *g, const pcg_batch *batch, float *s0, uint64_t *pos_keys,
+                        const pcg_select_ws *sel, float *agg, int32_t agg_stride, const pcg_train_state *st, int32_t score_next,
+                        const uint8_t *next_touched, int32_t keys_sorted, void *stream) {
+    if (!g || !batch || !sel || !st || batch->B < 0) return PCG_E_ARG;
+    if (batch->B == 0) return PCG_OK;
     TrainParts t;
-    int rc = train_parts(t, parts == 3, PCG_TRAIN_ARGS);
+    int rc = train_parts(t, parts == 3, g, batch, s0, pos_keys, sel, agg, st, score_next, next_touched, keys_sorted);
     if (rc != PCG_OK) return rc;
     t.a.clf.clf_out = clf_out;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipStream_t stm = static_cast<hipStream_t>(stream);
     if (parts & 1) {
-        rc = pcg::launch_select(t.a, st, true);
+        rc = pcg::launch_select(t.a, stm, true);
         if (rc != PCG_OK) return rc;
     }
     if (!(parts & 2)) return PCG_OK;
-    rc = pcg::launch_gather_train(g->X, g->feat_dim, g->feat_stride, g->n_nodes, cnt, g, B, t.a.w, agg, agg_stride, status, t.sd, st);
+    rc = pcg::launch_gather_train(g->X, g->feat_dim, g->feat_stride, g->n_nodes, batch->cnt, g, batch->B, t.a.w, agg, agg_stride, sel->status,
+                                  t.sd, stm);
     if (rc != PCG_OK) return rc;
-    if (score_next && t.one_launch) return pcg::launch_bk_onepass(pos_keys + t.cap, g->n_pos, pos_keys, (int)t.cap, status, st);
+    if (score_next && t.one_launch) return pcg::launch_bk_onepass(pos_keys + t.cap, g->n_pos, pos_keys, (int)t.cap, sel->status, stm);
     if (score_next && g->n_pos > pcg::RANK_MAX) return pcg_pos_sort(g, s0, pos_keys, stream);
     return PCG_OK;
 }
@@ -1251,111 +1241,102 @@ static int train_launch(int parts, float *clf_out, PCG_TRAIN_PARAMS, void *strea
  *                          score pass and unsorted train-pos keys with clf_next]
  * followed by pcg_train_dense(adam_clf = 2).  s0 / pos_keys: read by the select launch (this step's scores; unsorted keys in the
  * scratch half), rewritten by the gather launch for the next step. */
-int pcg_choose_gather_train(PCG_TRAIN_PARAMS, void *stream) {
-    return train_launch(3, nullptr, PCG_TRAIN_ARGS, stream);
+int pcg_choose_gather_train(const pcg_graph_desc *g, const pcg_batch *batch, float *s0, uint64_t *pos_keys, const pcg_select_ws *sel,
+                            float *agg, int32_t agg_stride, const pcg_train_state *st, int32_t score_next,
+                            const uint8_t *next_touched, int32_t keys_sorted, void *stream) {
+    return train_launch(3, nullptr, g, batch, s0, pos_keys, sel, agg, agg_stride, st, score_next, next_touched, keys_sorted, stream);
 }
 
-int pcg_choose_train_part(int32_t part, PCG_TRAIN_PARAMS, float *clf_out, void *stream) {
+int pcg_choose_train_part(int32_t part, const pcg_graph_desc *g, const pcg_batch *batch, float *s0, uint64_t *pos_keys,
+                          const pcg_select_ws *sel, float *agg, int32_t agg_stride, const pcg_train_state *st, int32_t score_next,
+                          const uint8_t *next_touched, int32_t keys_sorted, float *clf_out, void *stream) {
     if (part != 1 && part != 2) return PCG_E_ARG;
-    return train_launch(part, clf_out, PCG_TRAIN_ARGS, stream);
+    return train_launch(part, clf_out, g, batch, s0, pos_keys, sel, agg, agg_stride, st, score_next, next_touched, keys_sorted, stream);
 }
 
 int32_t pcg_dense_select_blocks(const pcg_graph_desc *g, int32_t emb, int32_t B) {
     return g ? pcg::dense_select_blocks(*g, emb, B) : 0;
 }
 
-// what pcg_dense_select_ahead adds to the fused launch (all null / 0: pcg_dense_select_train, the select half stepping its own
-// batch's classifier and sorting its own keys)
-struct AheadExtra {
-    bool on = false;
-    const int32_t *clf_ids = nullptr, *clf_labels = nullptr;   // the batch whose classifier step rides here (null: none - the tiles count the step)
-    int32_t clf_B = 0;
-    float clf_inv_count = 0.f;
-    uint64_t *sort_keys = nullptr;                             // [sorted half | raw half]: the riders sort the raw half into the sorted one
-};
-
-static int dense_select_launch(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
-                               const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt, const void *plan,
-                               float inv_count, const float *clf_in, float *logits, float *center, float *row_loss, float *acts,
-                               int32_t act_ld, const int32_t *next_ids, const int32_t *next_labels, int32_t next_B, int32_t *next_cnt,
-                               const void *next_plan, float next_inv_count, float *clf_out, float *s0, uint64_t *pos_keys,
-                               const double *thresholds, const double *rho, int32_t add_self, void *workspace, int64_t list_capacity,
-                               uint32_t *status, uint32_t *sync_words, float *clf_next, const float *slabs, int32_t *step_counter,
-                               float lambda_1, double lr, double beta1, double beta2, double eps, double weight_decay,
-                               const AheadExtra &x2, void *stream) {
-    if (!g || B < 1 || next_B < 1 || !clf_in || !acts || !cnt || !next_cnt || !workspace || !sync_words || !step_counter)
+// The fused launch.  clf_batch / sort_keys: what pcg_dense_select_ahead adds (ahead == false: pcg_dense_select_train, the select
+// half stepping its own batch's classifier and sorting its own keys).  clf_batch->ids: the batch whose classifier step rides here
+// (null: none - the tiles count the step); sort_keys [sorted half | raw half]: the riders sort the raw half into the sorted one
+static int dense_select_launch(const pcg_graph_desc *g, const pcg_train_state *st, const pcg_select_ws *sel, const pcg_batch *batch,
+                               const pcg_batch *next, const float *agg, int32_t agg_stride, const float *clf_in,
+                               const pcg_dense_out *out, float *clf_out, float *s0, uint64_t *pos_keys, bool ahead,
+                               const pcg_batch *clf_batch, uint64_t *sort_keys, void *stream) {
+    if (!g || !st || !sel || !batch || !next || !out || (ahead && !clf_batch)) return PCG_E_ARG;
+    if (batch->B < 1 || next->B < 1 || !clf_in || !st->acts || !batch->cnt || !next->cnt || !sel->workspace || !st->sync_words ||
+        !st->step_counter)
         return PCG_E_ARG;
-    const bool clf_on = !x2.on || x2.clf_ids != nullptr;
+    const bool clf_on = !ahead || clf_batch->ids != nullptr;
     if (clf_on && !clf_out) return PCG_E_ARG;
-    if (x2.on && x2.clf_ids && (!x2.clf_labels || x2.clf_B < 1)) return PCG_E_ARG;
-    if (list_capacity < 1 || list_capacity >= (1ll << 31)) return PCG_E_ARG;
-    const int n_sel = pcg::dense_select_blocks(*g, emb, B);
+    if (ahead && clf_batch->ids && (!clf_batch->labels || clf_batch->B < 1)) return PCG_E_ARG;
+    if (sel->list_capacity < 1 || sel->list_capacity >= (1ll << 31)) return PCG_E_ARG;
+    const int n_sel = pcg::dense_select_blocks(*g, st->emb, batch->B);
     if (n_sel <= 0) return PCG_E_UNSUPPORTED;
-    // batch t + 1's select launch as pcg_choose_train_part(1) sets it up.  pcg_dense_select_train: its train-pos keys unsorted (it
-    // sorts them itself); pcg_dense_select_ahead: sorted a launch earlier (keys_sorted = 1)
+    // batch t + 1's select launch as pcg_choose_train_part(1) sets it up (no weight-gradient workgroups: the gather launch's).
+    // pcg_dense_select_train: its train-pos keys unsorted (it sorts them itself); pcg_dense_select_ahead: sorted a launch
+    // earlier (keys_sorted = 1)
+    pcg_train_state sel_st = *st;
+    sel_st.acts = nullptr;
+    sel_st.act_ld = 0;
+    sel_st.wg_scratch = nullptr;
     TrainParts t;
-    int rc = train_parts(t, false, g, next_ids, next_labels, next_B, s0, pos_keys, thresholds, rho, add_self, const_cast<float *>(agg),
-                         agg_stride, next_cnt, workspace, next_plan, list_capacity, status, sync_words, theta, m, v, emb, clf_next, slabs,
-                         step_counter, lambda_1, next_inv_count, lr, beta1, beta2, eps, weight_decay, 1, nullptr, nullptr, 0, nullptr,
-                         x2.on ? 1 : 0);
+    int rc = train_parts(t, false, g, next, s0, pos_keys, sel, agg, &sel_st, 1, nullptr, ahead ? 1 : 0);
     if (rc != PCG_OK) return rc;
     t.a.clf.clf_out = clf_out;
-    t.a.clf.count_step = step_counter;
-    if (x2.on && !x2.clf_ids) {
+    t.a.clf.count_step = st->step_counter;
+    if (ahead && !clf_batch->ids) {
         t.a.clf.clf_next = nullptr;               // no classifier step in this launch: every select workgroup is a row workgroup
         t.a.clf.count_step = nullptr;
-    } else if (x2.on) {
+    } else if (ahead) {
         // the step of batch t + 2: the dense launches of t (beside it) and t + 1 have not counted themselves
-        t.a.clf.nodes = x2.clf_ids;
-        t.a.clf.labels = x2.clf_labels;
-        t.a.clf.B = x2.clf_B;
-        t.a.clf.scale = x2.clf_inv_count * lambda_1;
-        t.a.clf.n_wg = (x2.clf_B + 1023) / 1024 > 8 ? 8 : (x2.clf_B + 1023) / 1024;
+        t.a.clf.nodes = clf_batch->ids;
+        t.a.clf.labels = clf_batch->labels;
+        t.a.clf.B = clf_batch->B;
+        t.a.clf.scale = clf_batch->inv_count * st->lambda_1;
+        t.a.clf.n_wg = (clf_batch->B + 1023) / 1024 > 8 ? 8 : (clf_batch->B + 1023) / 1024;
         t.a.clf.t_ahead = 3;
     }
     // batch t's tiles as pcg_train_dense(adam_clf = 3) sets them up - without the riding key sort, without counting the step,
     // with the classifier the select launch of batch t left in clf_in
     pcg::DenseExtra x;
     pcg::Workspace w;
-    pcg::carve1(g, B, list_capacity, static_cast<unsigned char *>(workspace), &w, static_cast<unsigned char *>(const_cast<void *>(plan)));
+    pcg::carve1(g, batch->B, sel->list_capacity, static_cast<unsigned char *>(sel->workspace), &w,
+                static_cast<unsigned char *>(const_cast<void *>(batch->plan)));
     x.chunk_begin = w.chunk_begin;
     x.partial = w.partial;
-    x.cnt = cnt;
+    x.cnt = batch->cnt;
     x.partial_stride = g->feat_stride;
-    x.pending = sync_words + 1;
-    x.acts = acts;
-    x.act_ld = act_ld;
+    x.pending = st->sync_words + 1;
+    x.acts = st->acts;
+    x.act_ld = st->act_ld;
     pcg::DenseArgs d;
     int n_sort_blocks = 0;
     // (no classifier step beside the tiles: nothing in the launch reads the count, the tiles count the step themselves)
-    rc = pcg::dense_args(d, n_sort_blocks, g, theta, emb, ids, labels, B, agg, agg_stride, lambda_1, inv_count, logits, center, nullptr,
-                         row_loss, const_cast<float *>(slabs), t.a.clf.clf_next ? nullptr : step_counter, x);
+    rc = pcg::dense_args(d, n_sort_blocks, g, st->theta, st->emb, batch->ids, batch->labels, batch->B, agg, agg_stride, st->lambda_1,
+                         batch->inv_count, out->logits, out->center, nullptr, out->row_loss, st->slabs,
+                         t.a.clf.clf_next ? nullptr : st->step_counter, x);
     if (rc != PCG_OK) return rc;
     d.W_clf = clf_in;
     d.b_clf = clf_in + 2 * g->feat_dim;
     d.stamps = nullptr;
-    if (x2.on && x2.sort_keys && g->n_pos > 0) {
+    if (ahead && sort_keys && g->n_pos > 0) {
         const int64_t cap = pcg_pos_sort_capacity(g->n_pos) / 2;
-        d.sort_out = x2.sort_keys;
-        d.sort_raw = x2.sort_keys + cap;
+        d.sort_out = sort_keys;
+        d.sort_raw = sort_keys + cap;
         d.sort_n = g->n_pos;
         d.sort_cap = (int32_t)cap;
     }
     return pcg::launch_dense_select(d, t.a, n_sel, static_cast<hipStream_t>(stream));
 }
 
-int pcg_dense_select_train(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
-                           const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt, const void *plan,
-                           float inv_count, const float *clf_in, float *logits, float *center, float *row_loss, float *acts,
-                           int32_t act_ld, const int32_t *next_ids, const int32_t *next_labels, int32_t next_B, int32_t *next_cnt,
-                           const void *next_plan, float next_inv_count, float *clf_out, float *s0, uint64_t *pos_keys,
-                           const double *thresholds, const double *rho, int32_t add_self, void *workspace, int64_t list_capacity,
-                           uint32_t *status, uint32_t *sync_words, float *clf_next, const float *slabs, int32_t *step_counter,
-                           float lambda_1, double lr, double beta1, double beta2, double eps, double weight_decay, void *stream) {
-    return dense_select_launch(g, theta, m, v, emb, ids, labels, B, agg, agg_stride, cnt, plan, inv_count, clf_in, logits, center, row_loss,
-                               acts, act_ld, next_ids, next_labels, next_B, next_cnt, next_plan, next_inv_count, clf_out, s0, pos_keys,
-                               thresholds, rho, add_self, workspace, list_capacity, status, sync_words, clf_next, slabs, step_counter,
-                               lambda_1, lr, beta1, beta2, eps, weight_decay, AheadExtra(), stream);
+int pcg_dense_select_train(const pcg_graph_desc *g, const pcg_train_state *st, const pcg_select_ws *sel, const pcg_batch *batch,
+                           const pcg_batch *next, const float *agg, int32_t agg_stride, const float *clf_in,
+                           const pcg_dense_out *out, float *clf_out, float *s0, uint64_t *pos_keys, void *stream) {
+    return dense_select_launch(g, st, sel, batch, next, agg, agg_stride, clf_in, out, clf_out, s0, pos_keys, false, nullptr, nullptr,
+                               stream);
 }
 
 /* 1: the fused launch of a batch of B rows has room for pcg_dense_select_ahead's sort riders beside the tiles and the select
@@ -1369,58 +1350,33 @@ int32_t pcg_dense_select_ahead_ok(const pcg_graph_desc *g, int32_t emb, int32_t 
     return riders <= 4 * tiles ? 1 : 0;
 }
 
-int pcg_dense_select_ahead(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
-                           const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt, const void *plan,
-                           float inv_count, const float *clf_in, float *logits, float *center, float *row_loss, float *acts,
-                           int32_t act_ld, const int32_t *next_ids, const int32_t *next_labels, int32_t next_B, int32_t *next_cnt,
-                           const void *next_plan, float next_inv_count, float *clf_out, float *s0, uint64_t *pos_keys,
-                           const double *thresholds, const double *rho, int32_t add_self, void *workspace, int64_t list_capacity,
-                           uint32_t *status, uint32_t *sync_words, float *clf_next, const float *slabs, int32_t *step_counter,
-                           float lambda_1, double lr, double beta1, double beta2, double eps, double weight_decay,
-                           const int32_t *clf_ids, const int32_t *clf_labels, int32_t clf_B, float clf_inv_count, uint64_t *sort_keys,
-                           void *stream) {
-    AheadExtra x2;
-    x2.on = true;
-    x2.clf_ids = clf_ids;
-    x2.clf_labels = clf_labels;
-    x2.clf_B = clf_B;
-    x2.clf_inv_count = clf_inv_count;
-    x2.sort_keys = sort_keys;
+int pcg_dense_select_ahead(const pcg_graph_desc *g, const pcg_train_state *st, const pcg_select_ws *sel, const pcg_batch *batch,
+                           const pcg_batch *next, const pcg_batch *clf_batch, const float *agg, int32_t agg_stride,
+                           const float *clf_in, const pcg_dense_out *out, float *clf_out, float *s0, uint64_t *pos_keys,
+                           uint64_t *sort_keys, void *stream) {
     if (sort_keys && sort_keys == pos_keys) return PCG_E_ARG;       // (the select half reads pos_keys while the riders write)
-    return dense_select_launch(g, theta, m, v, emb, ids, labels, B, agg, agg_stride, cnt, plan, inv_count, clf_in, logits, center, row_loss,
-                               acts, act_ld, next_ids, next_labels, next_B, next_cnt, next_plan, next_inv_count, clf_out, s0, pos_keys,
-                               thresholds, rho, add_self, workspace, list_capacity, status, sync_words, clf_next, slabs, step_counter,
-                               lambda_1, lr, beta1, beta2, eps, weight_decay, x2, stream);
+    return dense_select_launch(g, st, sel, batch, next, agg, agg_stride, clf_in, out, clf_out, s0, pos_keys, true, clf_batch, sort_keys,
+                               stream);
 }
 
 /* The label classifier's step for one batch as a launch of its own: clf_next <- the classifier after the step, theta's classifier
  * and clf_out (if given) <- the one before it; Adam's t = step_counter[0] + t_ahead (the count is not changed). */
-int pcg_clf_step(const pcg_graph_desc *g, const int32_t *ids, const int32_t *labels, int32_t B, float *theta, float *m, float *v,
-                 int32_t emb, float *clf_next, float *clf_out, const float *slabs, const int32_t *step_counter, uint32_t *sync_words,
-                 float lambda_1, float inv_count, double lr, double beta1, double beta2, double eps, double weight_decay, int32_t t_ahead,
+int pcg_clf_step(const pcg_graph_desc *g, const pcg_batch *batch, const pcg_train_state *st, float *clf_out, int32_t t_ahead,
                  void *stream) {
-    if (!g || !g->X || !ids || !labels || B < 1 || !theta || !m || !v || !clf_next || !slabs || !step_counter || !sync_words || t_ahead < 1)
+    if (!g || !batch || !st) return PCG_E_ARG;
+    if (!g->X || !batch->ids || !batch->labels || batch->B < 1 || !st->theta || !st->m || !st->v || !st->clf_next || !st->slabs ||
+        !st->step_counter || !st->sync_words || t_ahead < 1)
         return PCG_E_ARG;
-    const int64_t n_params = pcg_dense_n_params(g->feat_dim, emb, g->n_rel);
-    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, emb, g->n_rel, 3, 0);
+    const int64_t n_params = pcg_dense_n_params(g->feat_dim, st->emb, g->n_rel);
+    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 3, 0);
     if (n_params < 0 || o_clf < 0) return PCG_E_ARG;
     pcg::ClfStep c;
-    c.clf_next = clf_next;
-    c.theta_clf = theta + o_clf;
-    c.m = m + o_clf;
-    c.v = v + o_clf;
-    c.step_counter = step_counter;
-    c.scale = inv_count * lambda_1;
-    c.h = {(float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay};
-    c.n_wg = (B + 1023) / 1024 > 8 ? 8 : (B + 1023) / 1024;
-    c.part = const_cast<float *>(slabs) + o_clf;
-    c.part_stride = n_params;
-    c.ticket = sync_words;
+    clf_step_of(c, st, batch, o_clf, n_params);
     c.clf_out = clf_out;
     c.count_step = nullptr;
-    c.nodes = ids;
-    c.labels = labels;
-    c.B = B;
+    c.nodes = batch->ids;
+    c.labels = batch->labels;
+    c.B = batch->B;
     c.t_ahead = t_ahead;
     return pcg::launch_clf_step(c, *g, static_cast<hipStream_t>(stream));
 }

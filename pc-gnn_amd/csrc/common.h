@@ -438,6 +438,10 @@ __device__ __forceinline__ void rank_sort_body(const float *__restrict__ s0, con
 struct AdamHyper {
     float lr, beta1, beta2, eps, wd;
 };
+// the ABI's doubles -> what the kernels compute with (host; the one place that narrows them)
+static inline AdamHyper adam_hyper(const pcg_adam_hyper &h) {
+    return {(float)h.lr, (float)h.beta1, (float)h.beta2, (float)h.eps, (float)h.weight_decay};
+}
 // torch.optim.Adam's update of one parameter (coupled L2 weight decay; t = the step's number, 1-based): ONE statement of the
 // arithmetic, for every place that applies it - two workgroups that work out the same parameter's update from the same inputs
 // (the partitioned path's score pass recomputes the label classifier's while other workgroups of its launch store it) must

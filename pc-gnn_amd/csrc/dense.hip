@@ -258,58 +258,56 @@ int pcg_dense_step(const pcg_graph_desc *g, const float *theta, int32_t emb, con
                              row_loss, slabs, step_counter, pcg::DenseExtra(), stream);
 }
 
-int pcg_train_dense(const pcg_graph_desc *g, float *theta, float *m, float *v, int32_t emb, const int32_t *ids,
-                    const int32_t *labels, int32_t B, const float *agg, int32_t agg_stride, const int32_t *cnt,
-                    const void *workspace, const void *plan, int64_t list_capacity, float lambda_1, float inv_count, float *logits, float *center,
-                    float *combined, float *row_loss, float *slabs, int32_t *step_counter, uint32_t *sync_words, double lr,
-                    double beta1, double beta2, double eps, double weight_decay, int32_t adam_clf, float *acts, int32_t act_ld,
-                    uint64_t *sort_keys, void *stream) {
-    if (!g || B < 0) return PCG_E_ARG;
+int pcg_train_dense(const pcg_graph_desc *g, const pcg_train_state *st, const pcg_batch *batch, const float *agg,
+                    int32_t agg_stride, const pcg_select_ws *sel, const pcg_dense_out *out, int32_t adam_clf, uint64_t *sort_keys,
+                    void *stream) {
+    if (!g || !st || !batch || !sel || !out || batch->B < 0) return PCG_E_ARG;
+    const int32_t B = batch->B;
+    uint32_t *const sync_words = st->sync_words;
     pcg::DenseExtra x;
-    if (workspace) {
-        if (!cnt || list_capacity < 1) return PCG_E_ARG;
+    if (sel->workspace) {
+        if (!batch->cnt || sel->list_capacity < 1) return PCG_E_ARG;
         pcg::Workspace w;
-        pcg::carve1(g, B, list_capacity, static_cast<unsigned char *>(const_cast<void *>(workspace)), &w,
-                    static_cast<unsigned char *>(const_cast<void *>(plan)));
+        pcg::carve1(g, B, sel->list_capacity, static_cast<unsigned char *>(sel->workspace), &w,
+                    static_cast<unsigned char *>(const_cast<void *>(batch->plan)));
         x.chunk_begin = w.chunk_begin;
         x.partial = w.partial;
-        x.cnt = cnt;
+        x.cnt = batch->cnt;
         x.partial_stride = g->feat_stride;
     }
     if (adam_clf == 3) {                     // no slabs: transposed activations for the weight-gradient GEMMs of a later launch
-        if (!acts || !sync_words) return PCG_E_ARG;
+        if (!st->acts || !sync_words) return PCG_E_ARG;
         x.pending = sync_words + 1;
-        x.acts = acts;
-        x.act_ld = act_ld;
+        x.acts = st->acts;
+        x.act_ld = st->act_ld;
         x.sort_keys = sort_keys;             // (only this mode has one workgroup per tile: CUs to spare for the riding sort)
     } else if (adam_clf == 4) {              // the same without marking anything as waiting (pcg_wgrad follows: gradients only)
-        if (!acts) return PCG_E_ARG;
-        x.acts = acts;
-        x.act_ld = act_ld;
+        if (!st->acts) return PCG_E_ARG;
+        x.acts = st->acts;
+        x.act_ld = st->act_ld;
     } else if (adam_clf == 2) {              // the label classifier is stepped elsewhere (pcg_choose_gather_train): slabs + "pending" only
-        if (!slabs || !sync_words) return PCG_E_ARG;
+        if (!st->slabs || !sync_words) return PCG_E_ARG;
         x.pending = sync_words + 1;
     } else if (adam_clf) {
-        if (!slabs || !m || !v || !sync_words) return PCG_E_ARG;
-        x.theta_rw = theta;
-        x.m = m;
-        x.v = v;
+        if (!st->slabs || !st->m || !st->v || !sync_words) return PCG_E_ARG;
+        x.theta_rw = st->theta;
+        x.m = st->m;
+        x.v = st->v;
         x.ticket = sync_words;
         x.staged = sync_words + pcg_sync_words_count() - 4;
         x.pending = sync_words + 1;
-        x.h = {(float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay};
+        x.h = pcg::adam_hyper(st->hyper);
     }
-    return pcg::launch_dense(g, theta, emb, ids, labels, B, agg, agg_stride, lambda_1, inv_count, logits, center, combined,
-                             row_loss, slabs, step_counter, x, stream);
+    return pcg::launch_dense(g, st->theta, st->emb, batch->ids, batch->labels, B, agg, agg_stride, st->lambda_1, batch->inv_count,
+                             out->logits, out->center, out->combined, out->row_loss, st->slabs, st->step_counter, x, stream);
 }
 
 int pcg_adam_step(float *theta, float *m, float *v, const float *slabs, int32_t n_slabs, int64_t n_params,
-                  const int32_t *step_counter, double lr, double beta1, double beta2, double eps, double weight_decay,
-                  float *grad_out, int32_t apply, void *stream) {
-    if (!slabs || n_slabs < 0 || n_params < 1) return PCG_E_ARG;
+                  const int32_t *step_counter, const pcg_adam_hyper *hyper, float *grad_out, int32_t apply, void *stream) {
+    if (!hyper || !slabs || n_slabs < 0 || n_params < 1) return PCG_E_ARG;
     if (apply && (!theta || !m || !v || !step_counter)) return PCG_E_ARG;
     if (!apply && !grad_out) return PCG_E_ARG;
-    const pcg::AdamHyper h = {(float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay};
+    const pcg::AdamHyper h = pcg::adam_hyper(*hyper);
     hipLaunchKernelGGL(pcg::adam_reduce_kernel, dim3((unsigned)((n_params + PCG_WAVE - 1) / PCG_WAVE)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), theta, m, v, slabs, n_slabs, n_params, (int64_t)0, n_params,
                        step_counter, h, grad_out, apply, (const uint32_t *)nullptr);
@@ -326,10 +324,9 @@ int pcg_grad_reduce(const float *slabs, int32_t n_slabs, int64_t n_params, float
 }
 
 int pcg_adam_apply_pending(float *theta, float *m, float *v, const float *grad, int64_t n_params, const int32_t *step_counter,
-                           uint32_t *flag, int32_t clear, double lr, double beta1, double beta2, double eps, double weight_decay,
-                           void *stream) {
-    if (!theta || !m || !v || !grad || n_params < 1 || !step_counter || !flag) return PCG_E_ARG;
-    const pcg::AdamHyper h = {(float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay};
+                           uint32_t *flag, int32_t clear, const pcg_adam_hyper *hyper, void *stream) {
+    if (!hyper || !theta || !m || !v || !grad || n_params < 1 || !step_counter || !flag) return PCG_E_ARG;
+    const pcg::AdamHyper h = pcg::adam_hyper(*hyper);
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(pcg::apply_pending_kernel, dim3((unsigned)((n_params + PCG_WAVE - 1) / PCG_WAVE)), dim3(256), 0, st, theta, m, v,
                        grad, n_params, step_counter, h, flag);
@@ -341,8 +338,11 @@ int pcg_adam_apply_pending(float *theta, float *m, float *v, const float *grad, 
     return PCG_OK;
 }
 
-static int wgrad_args(pcg::WgradArgs &w, const float *acts, int32_t act_ld, int32_t feat_dim, int32_t emb, int32_t n_rel,
-                      int32_t n_kblocks, float *scratch) {
+// the GEMMs over st->acts and the parameters they may update; what the launch does with them is the caller's to set
+static int wgrad_args(pcg::WgradArgs &w, const pcg_train_state *st, int32_t feat_dim, int32_t n_rel, int32_t n_kblocks) {
+    const float *const acts = st->acts;
+    float *const scratch = st->wg_scratch;
+    const int32_t act_ld = st->act_ld, emb = st->emb;
     if (!acts || act_ld < 16 || act_ld % 16 != 0 || (reinterpret_cast<uintptr_t>(acts) & 15u) != 0) return PCG_E_ARG;
     if (feat_dim < 1 || emb < 16 || emb % 16 != 0 || n_rel < 1 || n_rel > PCG_MAX_REL) return PCG_E_UNSUPPORTED;
     if (n_kblocks < 1 || n_kblocks * 16 > act_ld) return PCG_E_ARG;
@@ -361,6 +361,9 @@ static int wgrad_args(pcg::WgradArgs &w, const float *acts, int32_t act_ld, int3
         w.tickets = reinterpret_cast<uint32_t *>(scratch);
         w.partials = scratch + (t + 63) / 64 * 64;
     }
+    w.theta = st->theta; w.m = st->m; w.v = st->v;
+    w.step_counter = st->step_counter;
+    w.h = pcg::adam_hyper(st->hyper);
     return PCG_OK;
 }
 
@@ -374,66 +377,58 @@ int64_t pcg_wgrad_scratch_bytes(int32_t feat_dim, int32_t emb, int32_t n_rel, in
     return 4 * pcg::wgrad_scratch_floats(feat_dim, emb, n_rel, (B + 15) / 16);
 }
 
-int pcg_wgrad(const float *acts, int32_t act_ld, int32_t B, int32_t feat_dim, int32_t emb, int32_t n_rel, float *theta, float *m,
-              float *v, const int32_t *step_counter, double lr, double beta1, double beta2, double eps, double weight_decay,
-              float *grad_out, int32_t apply, int32_t with_clf, float *scratch, uint32_t *flag_set, void *stream) {
+int pcg_wgrad(const pcg_train_state *st, int32_t B, int32_t feat_dim, int32_t n_rel, float *grad_out, int32_t apply,
+              int32_t with_clf, uint32_t *flag_set, void *stream) {
     pcg::WgradArgs w;
-    if (B < 1) return PCG_E_ARG;
-    const int rc = wgrad_args(w, acts, act_ld, feat_dim, emb, n_rel, (B + 15) / 16, scratch);
+    if (!st || B < 1) return PCG_E_ARG;
+    const int rc = wgrad_args(w, st, feat_dim, n_rel, (B + 15) / 16);
     if (rc != PCG_OK) return rc;
-    if (apply && (!theta || !m || !v || !step_counter)) return PCG_E_ARG;
+    if (apply && (!st->theta || !st->m || !st->v || !st->step_counter)) return PCG_E_ARG;
     if (!apply && !grad_out) return PCG_E_ARG;
-    w.theta = theta; w.m = m; w.v = v;
-    w.step_counter = step_counter;
-    w.h = {(float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay};
     w.pending = nullptr;
     w.grad_out = grad_out;
     w.flag_set = flag_set;
     w.apply = apply;
     w.with_clf = with_clf ? 1 : 0;
-    hipLaunchKernelGGL(pcg::wgrad_adam_kernel, dim3((unsigned)(pcg::wgrad_tiles(feat_dim, emb, n_rel, w.with_clf) * w.kparts)), dim3(256), 0,
+    hipLaunchKernelGGL(pcg::wgrad_adam_kernel, dim3((unsigned)(pcg::wgrad_tiles(feat_dim, st->emb, n_rel, w.with_clf) * w.kparts)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), w);
     PCG_LAUNCH_CHECK();
     return PCG_OK;
 }
 
-int pcg_adam_flush(float *theta, float *m, float *v, const float *slabs, int32_t n_slabs, int64_t n_params, int64_t p_end,
-                   const int32_t *step_counter, uint32_t *sync_words, double lr, double beta1, double beta2, double eps,
-                   double weight_decay, const float *clf_next, const float *acts, int32_t act_ld, int32_t feat_dim, int32_t emb,
-                   int32_t n_rel, float *wg_scratch, void *stream) {
-    if (!theta || !m || !v || (!slabs && !acts) || !step_counter || !sync_words || n_slabs < 0 || n_params < 1 || p_end < 0 ||
-        p_end > n_params)
+int pcg_adam_flush(const pcg_train_state *st, int32_t n_slabs, int64_t n_params, int64_t p_end, int32_t feat_dim, int32_t n_rel,
+                   void *stream) {
+    if (!st || !st->theta || !st->m || !st->v || (!st->slabs && !st->acts) || !st->step_counter || !st->sync_words || n_slabs < 0 ||
+        n_params < 1 || p_end < 0 || p_end > n_params)
         return PCG_E_ARG;
-    const pcg::AdamHyper h = {(float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (acts) {                              // a step of pcg_train_dense(adam_clf = 3) waiting (sync_words[1] == 2): weight-gradient GEMMs + Adam
+    const pcg::AdamHyper h = pcg::adam_hyper(st->hyper);
+    uint32_t *const pending = st->sync_words + 1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (st->acts) {                          // a step of pcg_train_dense(adam_clf = 3) waiting (sync_words[1] == 2): weight-gradient GEMMs + Adam
         pcg::WgradArgs w;
-        const int rc = wgrad_args(w, acts, act_ld, feat_dim, emb, n_rel, act_ld / 16, wg_scratch);
+        const int rc = wgrad_args(w, st, feat_dim, n_rel, st->act_ld / 16);
         if (rc != PCG_OK) return rc;
-        if (pcg::n_params_of(feat_dim, emb, n_rel) != n_params) return PCG_E_ARG;
-        w.theta = theta; w.m = m; w.v = v;
-        w.step_counter = step_counter;
-        w.h = h;
-        w.pending = sync_words + 1;
+        if (pcg::n_params_of(feat_dim, st->emb, n_rel) != n_params) return PCG_E_ARG;
+        w.pending = pending;
         w.grad_out = nullptr;
         w.flag_set = nullptr;
         w.apply = 1;
-        w.with_clf = p_end > pcg::off_clf(feat_dim, emb, n_rel) ? 1 : 0;
-        hipLaunchKernelGGL(pcg::wgrad_adam_kernel, dim3((unsigned)(pcg::wgrad_tiles(feat_dim, emb, n_rel, w.with_clf) * w.kparts)), dim3(256), 0, st, w);
+        w.with_clf = p_end > pcg::off_clf(feat_dim, st->emb, n_rel) ? 1 : 0;
+        hipLaunchKernelGGL(pcg::wgrad_adam_kernel, dim3((unsigned)(pcg::wgrad_tiles(feat_dim, st->emb, n_rel, w.with_clf) * w.kparts)), dim3(256), 0, s, w);
         PCG_LAUNCH_CHECK();
     }
-    if (p_end > 0 && slabs) {
-        hipLaunchKernelGGL(pcg::adam_reduce_kernel, dim3((unsigned)((p_end + PCG_WAVE - 1) / PCG_WAVE)), dim3(256), 0, st, theta, m,
-                           v, slabs, n_slabs, n_params, (int64_t)0, p_end, step_counter, h, (float *)nullptr, 1,
-                           (const uint32_t *)(sync_words + 1));
+    if (p_end > 0 && st->slabs) {
+        hipLaunchKernelGGL(pcg::adam_reduce_kernel, dim3((unsigned)((p_end + PCG_WAVE - 1) / PCG_WAVE)), dim3(256), 0, s, st->theta, st->m,
+                           st->v, (const float *)st->slabs, n_slabs, n_params, (int64_t)0, p_end, (const int32_t *)st->step_counter, h,
+                           (float *)nullptr, 1, (const uint32_t *)pending);
         PCG_LAUNCH_CHECK();
     }
-    if (clf_next && p_end < n_params) {      // (pcg_choose_gather_train keeps the stepped label classifier outside theta until now)
-        hipLaunchKernelGGL(pcg::copy_if_pending_kernel, dim3(1), dim3(256), 0, st, theta + p_end, clf_next, (int)(n_params - p_end),
-                           (const uint32_t *)(sync_words + 1));
+    if (st->clf_next && p_end < n_params) {  // (pcg_choose_gather_train keeps the stepped label classifier outside theta until now)
+        hipLaunchKernelGGL(pcg::copy_if_pending_kernel, dim3(1), dim3(256), 0, s, st->theta + p_end, (const float *)st->clf_next,
+                           (int)(n_params - p_end), (const uint32_t *)pending);
         PCG_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(pcg::clear_word_kernel, dim3(1), dim3(1), 0, st, sync_words + 1);
+    hipLaunchKernelGGL(pcg::clear_word_kernel, dim3(1), dim3(1), 0, s, pending);
     PCG_LAUNCH_CHECK();
     return PCG_OK;
 }

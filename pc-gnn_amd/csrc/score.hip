@@ -2,6 +2,8 @@
 // score_table streams the whole feature table once per step (weights change every
 // step): 64/lpr rows per wave-instruction, float4 per lane, rows adjacent in
 // memory => every wave-instruction is one fully coalesced 1 KiB read.
+#include <stddef.h>
+
 #include "common.h"
 
 namespace pcg {
@@ -286,7 +288,35 @@ int pcg_gather_rows(const pcg_graph_desc *g, const int32_t *ids, int32_t n_ids, 
     return PCG_OK;
 }
 
-const char *pcg_version(void) { return "pcgnn_hip gfx950 abi11"; }
-int pcg_abi_version(void) { return 11; }
+const char *pcg_version(void) { return "pcgnn_hip gfx950 abi12"; }
+int pcg_abi_version(void) { return 12; }
+
+/* sizeof, then offsetof of every member in declaration order, of the ABI's parameter structs: what a binding checks its mirror
+ * of the header against.  Host only. */
+int32_t pcg_abi_layout(int32_t which, int64_t *out, int32_t cap) {
+#define PCG_OFF(T, member) (int64_t)offsetof(T, member)
+    static const int64_t hyper[] = {sizeof(pcg_adam_hyper), PCG_OFF(pcg_adam_hyper, lr), PCG_OFF(pcg_adam_hyper, beta1),
+                                    PCG_OFF(pcg_adam_hyper, beta2), PCG_OFF(pcg_adam_hyper, eps), PCG_OFF(pcg_adam_hyper, weight_decay)};
+    static const int64_t state[] = {sizeof(pcg_train_state), PCG_OFF(pcg_train_state, theta), PCG_OFF(pcg_train_state, m),
+                                    PCG_OFF(pcg_train_state, v), PCG_OFF(pcg_train_state, step_counter),
+                                    PCG_OFF(pcg_train_state, sync_words), PCG_OFF(pcg_train_state, clf_next),
+                                    PCG_OFF(pcg_train_state, slabs), PCG_OFF(pcg_train_state, acts), PCG_OFF(pcg_train_state, wg_scratch),
+                                    PCG_OFF(pcg_train_state, emb), PCG_OFF(pcg_train_state, act_ld), PCG_OFF(pcg_train_state, lambda_1),
+                                    PCG_OFF(pcg_train_state, _pad), PCG_OFF(pcg_train_state, hyper)};
+    static const int64_t sel[] = {sizeof(pcg_select_ws), PCG_OFF(pcg_select_ws, thresholds), PCG_OFF(pcg_select_ws, rho),
+                                  PCG_OFF(pcg_select_ws, workspace), PCG_OFF(pcg_select_ws, status), PCG_OFF(pcg_select_ws, list_capacity),
+                                  PCG_OFF(pcg_select_ws, add_self), PCG_OFF(pcg_select_ws, _pad)};
+    static const int64_t batch[] = {sizeof(pcg_batch), PCG_OFF(pcg_batch, ids), PCG_OFF(pcg_batch, labels), PCG_OFF(pcg_batch, cnt),
+                                    PCG_OFF(pcg_batch, plan), PCG_OFF(pcg_batch, B), PCG_OFF(pcg_batch, inv_count)};
+    static const int64_t dense_out[] = {sizeof(pcg_dense_out), PCG_OFF(pcg_dense_out, logits), PCG_OFF(pcg_dense_out, center),
+                                        PCG_OFF(pcg_dense_out, combined), PCG_OFF(pcg_dense_out, row_loss)};
+#undef PCG_OFF
+#define PCG_ROW(a) {a, (int32_t)(sizeof(a) / sizeof(a[0]))}
+    static const struct { const int64_t *v; int32_t n; } all[] = {PCG_ROW(hyper), PCG_ROW(state), PCG_ROW(sel), PCG_ROW(batch), PCG_ROW(dense_out)};
+#undef PCG_ROW
+    if (which < 0 || which >= (int32_t)(sizeof(all) / sizeof(all[0])) || !out || cap < all[which].n) return PCG_E_ARG;
+    for (int32_t i = 0; i < all[which].n; ++i) out[i] = all[which].v[i];
+    return all[which].n;
+}
 
 }  // extern "C"

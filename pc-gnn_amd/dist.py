@@ -541,6 +541,19 @@ class DistributedPCGNN:
         self.off_clf = int(o3)
         self.clf_snap = torch.zeros(3 * self.n_clf, dtype=torch.float32, device=self.dev)
         self._snap_refresh()
+        # the parameter structs of the training calls (include/pcgnn.h), over the buffers above.  A member that one call wants
+        # NULL and another set: an instance each - the optimizer's, the dense launch's (no moments, no slabs, nothing marked as
+        # waiting), the weight gradients' (the gradient only: no parameter is read)
+        L, _p = self._libmod, ops._p
+        self._hyper = L.AdamHyper(cfg["lr"], 0.9, 0.999, 1e-8, cfg["weight_decay"])
+        self._st = L.TrainState(theta=_p(self.theta), m=_p(self.m), v=_p(self.v), step_counter=_p(self.step_counter),
+                                sync_words=_p(self.sync), emb=self.E, hyper=self._hyper)
+        self._st_dense = L.TrainState(theta=_p(self.theta), step_counter=_p(self.step_counter), acts=_p(self.acts), emb=self.E,
+                                      act_ld=self.act_ld, lambda_1=float(cfg["alpha"]), hyper=self._hyper)
+        self._st_wgrad = L.TrainState(acts=_p(self.acts), wg_scratch=_p(self.wg_scratch), emb=self.E, act_ld=self.act_ld,
+                                      hyper=self._hyper)
+        self._sel = L.SelectWs(self._thr, self._rhos, _p(self.data), _p(self.status), self.list_capacity, 0)
+        self._out = L.DenseOut(_p(self.logits), _p(self.center), None, _p(self.row_loss))
         self.thresholds, self.rho = [0.5] * g.R, [cfg["rho"]] * g.R
         self.sampler = PickSampler(sh["idx_train_local"] - part.lo, y_loc, sh["homo_deg_train"],
                                    self.dev, seed=cfg["seed"] + 7919 * self.rank)
@@ -683,14 +696,12 @@ class DistributedPCGNN:
         (round 3: seven - apply_pending, front, select, halo_lookup, gather, dense, grad_reduce)."""
         import ctypes as C
         ops, g, part, lib, _p = self.ops, self.g, self.part, self.lib, self.ops._p
-        check, c = self._libmod.check, self.cfg
+        check = self._libmod.check
         st = ops._stream(self.dev)
         P = g.n_pos
         in_select = P > 0 and bool(lib.pcg_pos_sort_in_select(P))
-        check(lib.pcg_step_scores_dist(g.desc_ref(), _p(self.theta), _p(self.m), _p(self.v), self.E, _p(self.grad), _p(self.clf_snap), 0,
-                                       g.n_nodes, _p(self.s0_full), _p(self.row_gid), _p(self.keys) if in_select else None,
-                                       part.n_local, _p(self.step_counter), _p(self.sync), c["lr"], 0.9, 0.999, 1e-8,
-                                       c["weight_decay"], st), "pcg_step_scores_dist")
+        check(lib.pcg_step_scores_dist(g.desc_ref(), self._st, _p(self.grad), _p(self.clf_snap), 0, g.n_nodes, _p(self.s0_full),
+                                       _p(self.row_gid), _p(self.keys) if in_select else None, part.n_local, st), "pcg_step_scores_dist")
         if P > 0 and not in_select:          # too many positives for the in-kernel sort: the bucket sort's launches
             ops.pos_sort(g, self.s0_full, self.keys)
         check(lib.pcg_choose_select_planned(
@@ -704,21 +715,18 @@ class DistributedPCGNN:
             self.list_capacity, _p(agg), agg.stride(1), _p(self.status), part.lo, part.hi, part.n_local, _p(h.pos_ids32),
             _p(h.pos_idx32), h.P, _p(h.table), h.slots, _p(h.counts), h.halo_cap, h.halo_base, _p(self.theta), _p(self.m), _p(self.v),
             self.off_clf, self.n_clf, _p(self.clf_snap), st), "pcg_gather_lists_dist")
-        check(lib.pcg_train_dense(g.desc_ref(), _p(self.theta), None, None, self.E, _p(ids_local), _p(labels), B, _p(agg),
-                                  agg.stride(1), _p(self.cnt), _p(self.data), C.c_void_p(plan), self.list_capacity, float(c["alpha"]),
-                                  1.0 / (B * self.world), _p(self.logits), _p(self.center), None, _p(self.row_loss),
-                                  None, _p(self.step_counter), None, c["lr"], 0.9, 0.999, 1e-8, c["weight_decay"], 4,
-                                  _p(self.acts), self.act_ld, None, st), "pcg_train_dense")
-        check(lib.pcg_wgrad(_p(self.acts), self.act_ld, B, self.F, self.E, self.R, None, None, None, None, c["lr"], 0.9, 0.999, 1e-8,
-                            c["weight_decay"], _p(self.grad), 0, 1, _p(self.wg_scratch), _p(self.opt_flag), st), "pcg_wgrad")
+        batch = self._libmod.Batch(_p(ids_local), _p(labels), _p(self.cnt), plan, B, 1.0 / (B * self.world))
+        check(lib.pcg_train_dense(g.desc_ref(), self._st_dense, batch, _p(agg), agg.stride(1), self._sel, self._out, 4, None, st),
+              "pcg_train_dense")
+        check(lib.pcg_wgrad(self._st_wgrad, B, self.F, self.R, _p(self.grad), 0, 1, _p(self.opt_flag), st), "pcg_wgrad")
 
     def _enqueue_apply(self, clear: bool = False):
         """Adam from self.grad on every parameter if a gradient is waiting (device flag; a no-op launch otherwise).  Inside a
         step the flag is cleared by the step's select launch; clear=True adds a one-thread launch that does it."""
-        c, lib, _p = self.cfg, self.lib, self.ops._p
+        lib, _p = self.lib, self.ops._p
         self._libmod.check(lib.pcg_adam_apply_pending(_p(self.theta), _p(self.m), _p(self.v), _p(self.grad), self.n_params,
-                                                      _p(self.step_counter), _p(self.opt_flag), 1 if clear else 0, c["lr"], 0.9, 0.999,
-                                                      1e-8, c["weight_decay"], self.ops._stream(self.dev)), "pcg_adam_apply_pending")
+                                                      _p(self.step_counter), _p(self.opt_flag), 1 if clear else 0, self._hyper,
+                                                      self.ops._stream(self.dev)), "pcg_adam_apply_pending")
 
     def flush(self):
         """Apply the last step's Adam update now (it otherwise rides at the head of the next step's launches): call before

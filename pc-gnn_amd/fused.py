@@ -230,11 +230,11 @@ class FusedPCGNN:
         self._ep_graphs = {}
         self._ep_sets = None       # two sets of epoch buffers: ids | labels | plan slots (stage_epoch)
         self._cur, self._cur_ready, self._ep_stride = 0, False, 0
+        self._thr, self._rhos = ops._host_arrays(g, self.thresholds, self.rho)
+        self._hyper = _lib.AdamHyper(lr, betas[0], betas[1], eps, weight_decay)
         self._alloc(max_batch)
         self._prof = None          # bench.py: list of (start, end) events around the choose+aggregate launch
         self.last_counts = None
-        thr, rhos = ops._host_arrays(g, self.thresholds, self.rho)
-        self._thr, self._rhos = thr, rhos
         # infer(): a workspace of its own (score table, plan slots, data part, aggregates, counts, status word), grown on demand;
         # its default chunk keeps the workspace within infer_workspace_bytes
         self.infer_workspace_bytes = int(infer_workspace_bytes)
@@ -304,6 +304,24 @@ class FusedPCGNN:
         self.presort = bool(lib.pcg_dense_sorts_keys(B, g.n_pos)) and os.environ.get("PCG_PRESORT", "1") != "0"
         self.ids_buf = torch.zeros(B, dtype=torch.int32, device=dev)
         self.lab_buf = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._bind()
+
+    def _bind(self):
+        """The parameter structs of the training calls (include/pcgnn.h), built where the buffers they point to are allocated;
+        a call fills only its batch.  A member that one call wants NULL and another set: two instances."""
+        own = dict(theta=_p(self.theta), m=_p(self.m), v=_p(self.v), sync_words=_p(self.sync), emb=self.E, act_ld=self.act_ld,
+                   lambda_1=self.lambda_1, hyper=self._hyper)
+        self._st = _lib.TrainState(step_counter=_p(self.step_counter), clf_next=_p(self.clf_next), slabs=_p(self.slabs),
+                                   acts=_p(self.acts), wg_scratch=_p(self.wg_scratch), **own)
+        self._st_fwd = _lib.TrainState(**own)       # pcg_train_dense forward only: no gradient, no step counted
+        # pcg_wgrad(apply = 0): the gradient of the activations at hand, no parameter is read or written
+        self._st_grad = _lib.TrainState(acts=_p(self.acts), wg_scratch=_p(self.wg_scratch), emb=self.E, act_ld=self.act_ld,
+                                        hyper=self._hyper)
+        self._sel = _lib.SelectWs(self._thr, self._rhos, _p(self.data), _p(self.status), self.list_capacity, 0)
+        self._out = _lib.DenseOut(_p(self.logits), _p(self.center), None, _p(self.row_loss))
+
+    def _batch(self, ids, labels, B, plan: Optional[int] = None, cnt=None) -> _lib.Batch:
+        return _lib.Batch(_p(ids), _p(labels), _p(cnt), plan, B, 1.0 / (max(B, 1) * self.scale))
 
     def _stream(self):
         return ops._stream(self.dev)
@@ -361,11 +379,9 @@ class FusedPCGNN:
         """the front of a training step: score pass || train-pos keys (unsorted) || the previous step's deferred Adam update.
         touched: address of the batch's byte map - only the rows it marks are scored."""
         g = self.g
-        b1, b2 = self.betas
         self._fresh = False                         # (the four-launch step: scores of theta's classifier, every step)
         _lib.check(self.lib.pcg_step_scores_train(
-            g.desc_ref(), _p(self.theta), _p(self.m), _p(self.v), self.E, _p(self.s0), _p(self.keys) if g.n_pos else None,
-            _p(self.slabs), _p(self.step_counter), _p(self.sync), self.lr, b1, b2, self.eps, self.wd,
+            g.desc_ref(), self._st, _p(self.s0), _p(self.keys) if g.n_pos else None,
             None if touched is None else C.c_void_p(touched), self._stream()), "pcg_step_scores_train")
         return self.keys if g.n_pos else None
 
@@ -405,18 +421,15 @@ class FusedPCGNN:
         g = self.g
         agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
         cnt = self.cnt.view(-1)[:g.R * B].view(g.R, B)
-        b1, b2 = self.betas
         timed = self._prof is not None and not torch.cuda.is_current_stream_capturing()
         if timed:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
         _lib.check(self.lib.pcg_choose_gather_train(
-            g.desc_ref(), _p(ids), _p(labels), B, _p(self.s0), _p(self.keys) if g.n_pos else None, self._thr, self._rhos, 0,
-            _p(agg), agg.stride(-2), _p(cnt), _p(self.data), C.c_void_p(plan), self.list_capacity, _p(self.status), _p(self.sync),
-            _p(self.theta), _p(self.m), _p(self.v), self.E, _p(self.clf_next), _p(self.slabs), _p(self.step_counter),
-            self.lambda_1, 1.0 / (B * self.scale), self.lr, b1, b2, self.eps, self.wd, 1 if score_next else 0,
-            None if next_touched is None else C.c_void_p(next_touched), _p(self.acts), self.act_ld, _p(self.wg_scratch),
-            1 if self.presort else 0, self._stream()), "pcg_choose_gather_train")
+            g.desc_ref(), self._batch(ids, labels, B, plan, cnt), _p(self.s0), _p(self.keys) if g.n_pos else None, self._sel,
+            _p(agg), agg.stride(-2), self._st, 1 if score_next else 0,
+            None if next_touched is None else C.c_void_p(next_touched), 1 if self.presort else 0, self._stream()),
+            "pcg_choose_gather_train")
         if timed:
             ev[1].record()
             self._prof.append(ev)
@@ -455,14 +468,11 @@ class FusedPCGNN:
         pcg_step_scores_train); 4: transposed activations only, nothing marked as waiting (gradients())."""
         g = self.g
         cnt = self.cnt.view(-1)[:g.R * B] if cnt is None else cnt
-        b1, b2 = self.betas
         adam_clf = (3 if train else 0) if adam_clf is None else int(adam_clf)
+        out = _lib.DenseOut(_p(self.logits), _p(self.center), _p(combined), _p(self.row_loss) if labels is not None else None)
         _lib.check(self.lib.pcg_train_dense(
-            g.desc_ref(), _p(self.theta), _p(self.m), _p(self.v), self.E, _p(ids), _p(labels), B, _p(agg), agg.stride(1),
-            _p(cnt), _p(self.data), C.c_void_p(plan), self.list_capacity, self.lambda_1, 1.0 / (B * self.scale), _p(self.logits),
-            _p(self.center), _p(combined), _p(self.row_loss) if labels is not None else None, _p(self.slabs) if train else None,
-            _p(self.step_counter) if train else None, _p(self.sync), self.lr, b1, b2, self.eps, self.wd, adam_clf,
-            _p(self.acts) if adam_clf in (3, 4) else None, self.act_ld,
+            g.desc_ref(), self._st if train else self._st_fwd, self._batch(ids, labels, B, plan, cnt), _p(agg), agg.stride(1),
+            self._sel, out, adam_clf,
             # (the next step's keys: formed by the gather launch before this one if it scored ahead - then sorted here)
             _p(self.keys) if (adam_clf == 3 and self.presort and self._fresh) else None, self._stream()), "pcg_train_dense")
         if adam_clf == 1:                           # (the four-launch step updates theta's classifier in place)
@@ -473,18 +483,17 @@ class FusedPCGNN:
         return (self.pipeline and not self.touched_on and len(batches) >= 2 and self._pipe_blocks > 0
                 and max(B for _, B in batches) <= self.maxB)
 
-    def _train_args(self, ids, labels, B, plan: int, cnt, keys_sorted: int, bufs=None, score_next: bool = True):
-        """pcg_choose_gather_train's arguments (without the stream) for a whole-table engine's step that scores the next one.
+    def _enqueue_part(self, part: int, ids, labels, B, plan: int, cnt, keys_sorted: int, clf_out=None, bufs=None,
+                      score_next: bool = True):
+        """one launch of a whole-table engine's pcg_choose_gather_train (pcg_choose_train_part): part 1 = the select launch
+        (clf_out: the classifier slot it fills), 2 = the gather launch.
         bufs: the (s0, keys) pair the launch reads (select) or writes (the gather launch's score pass), default the engine's own"""
         g = self.g
         agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
-        b1, b2 = self.betas
         s0, keys = (self.s0, self.keys) if bufs is None else bufs
-        return (g.desc_ref(), _p(ids), _p(labels), B, _p(s0), _p(keys) if g.n_pos else None, self._thr, self._rhos, 0,
-                _p(agg), agg.stride(-2), _p(cnt), _p(self.data), C.c_void_p(plan), self.list_capacity, _p(self.status), _p(self.sync),
-                _p(self.theta), _p(self.m), _p(self.v), self.E, _p(self.clf_next), _p(self.slabs), _p(self.step_counter),
-                self.lambda_1, 1.0 / (B * self.scale), self.lr, b1, b2, self.eps, self.wd, 1 if score_next else 0, None,
-                _p(self.acts), self.act_ld, _p(self.wg_scratch), keys_sorted)
+        _lib.check(self.lib.pcg_choose_train_part(
+            part, g.desc_ref(), self._batch(ids, labels, B, plan, cnt), _p(s0), _p(keys) if g.n_pos else None, self._sel, _p(agg),
+            agg.stride(-2), self._st, 1 if score_next else 0, None, keys_sorted, _p(clf_out), self._stream()), "pcg_choose_train_part")
 
     def _ahead(self, steps) -> bool:
         """whether a pipelined sequence [(ids, labels, B, plan)] steps the label classifier two batches ahead
@@ -512,26 +521,21 @@ class FusedPCGNN:
         if not self._fresh:
             self._enqueue_refresh()
         R, F = g.R, g.feat_dim
-        b1, b2 = self.betas
         st = self._stream()
         cnt = lambda p, B: self.cnt2[p].view(-1)[:R * B]
         own, alt = (self.s0, self.keys), (self.s0_alt, self.keys_alt)
         buf = lambda t: own if (n - t) % 2 == 0 else alt
         slot = lambda t: self.clf_slots[t % 3]
         ids, lab, B, plan = steps[0]
-        _lib.check(lib.pcg_choose_train_part(1, *self._train_args(ids, lab, B, plan, cnt(0, B), 1), _p(slot(0)), st),
-                   "pcg_choose_train_part")
+        self._enqueue_part(1, ids, lab, B, plan, cnt(0, B), 1, clf_out=slot(0))
         self._fresh = False
         self._enqueue_refresh(into=buf(1))
         ids1, lab1, B1, _ = steps[1]
-        _lib.check(lib.pcg_clf_step(g.desc_ref(), _p(ids1), _p(lab1), B1, _p(self.theta), _p(self.m), _p(self.v), self.E,
-                                    _p(self.clf_next), _p(slot(1)), _p(self.slabs), _p(self.step_counter), _p(self.sync),
-                                    self.lambda_1, 1.0 / (B1 * self.scale), self.lr, b1, b2, self.eps, self.wd, 2, st), "pcg_clf_step")
+        _lib.check(lib.pcg_clf_step(g.desc_ref(), self._batch(ids1, lab1, B1), self._st, _p(slot(1)), 2, st), "pcg_clf_step")
         p = 0
         for t, (ids, lab, B, plan) in enumerate(steps):
             # (the gather launch's score pass writes batch t + 2's buffers with the classifier the launch before has stepped)
-            _lib.check(lib.pcg_choose_train_part(2, *self._train_args(ids, lab, B, plan, cnt(p, B), 0, bufs=buf(t + 2),
-                                                                      score_next=t + 2 <= n), None, st), "pcg_choose_train_part")
+            self._enqueue_part(2, ids, lab, B, plan, cnt(p, B), 0, bufs=buf(t + 2), score_next=t + 2 <= n)
             agg = self.agg.view(-1)[:R * B * F].view(R, B, F)
             if t + 1 == n:
                 self._enqueue_tail(ids, lab, B, agg, plan, True, cnt=cnt(p, B))       # (_fresh is off: no key sort rides here)
@@ -540,14 +544,10 @@ class FusedPCGNN:
             s0n, keysn = buf(t + 1)
             cids, clab, cB = steps[t + 2][:3] if t + 2 < n else (None, None, 0)
             _lib.check(lib.pcg_dense_select_ahead(
-                g.desc_ref(), _p(self.theta), _p(self.m), _p(self.v), self.E, _p(ids), _p(lab), B, _p(agg), agg.stride(1),
-                _p(cnt(p, B)), C.c_void_p(plan), 1.0 / (B * self.scale), _p(slot(t)), _p(self.logits), _p(self.center),
-                _p(self.row_loss), _p(self.acts), self.act_ld, _p(nids), _p(nlab), nB, _p(cnt(p ^ 1, nB)), C.c_void_p(nplan),
-                1.0 / (nB * self.scale), _p(slot(t + 2)) if cB else None, _p(s0n), _p(keysn) if g.n_pos else None, self._thr,
-                self._rhos, 0, _p(self.data), self.list_capacity, _p(self.status), _p(self.sync), _p(self.clf_next), _p(self.slabs),
-                _p(self.step_counter), self.lambda_1, self.lr, b1, b2, self.eps, self.wd, _p(cids), _p(clab), cB,
-                1.0 / (max(cB, 1) * self.scale), _p(buf(t + 2)[1]) if (g.n_pos and t + 2 <= n) else None, st),
-                "pcg_dense_select_ahead")
+                g.desc_ref(), self._st, self._sel, self._batch(ids, lab, B, plan, cnt(p, B)),
+                self._batch(nids, nlab, nB, nplan, cnt(p ^ 1, nB)), self._batch(cids, clab, cB), _p(agg), agg.stride(1), _p(slot(t)),
+                self._out, _p(slot(t + 2)) if cB else None, _p(s0n), _p(keysn) if g.n_pos else None,
+                _p(buf(t + 2)[1]) if (g.n_pos and t + 2 <= n) else None, st), "pcg_dense_select_ahead")
             p ^= 1
         self.last_counts = self.cnt2[p].view(-1)[:R * B].view(R, B)
         self._fresh = True
@@ -565,15 +565,13 @@ class FusedPCGNN:
         if not self._fresh:
             self._enqueue_refresh()
         R, F = g.R, g.feat_dim
-        b1, b2 = self.betas
         st = self._stream()
         cnt = lambda p, B: self.cnt2[p].view(-1)[:R * B]
         ids, lab, B, plan = steps[0]
-        _lib.check(lib.pcg_choose_train_part(1, *self._train_args(ids, lab, B, plan, cnt(0, B), 1 if self.presort else 0),
-                                             _p(self.clf_slots[0]), st), "pcg_choose_train_part")
+        self._enqueue_part(1, ids, lab, B, plan, cnt(0, B), 1 if self.presort else 0, clf_out=self.clf_slots[0])
         p = 0
         for t, (ids, lab, B, plan) in enumerate(steps):
-            _lib.check(lib.pcg_choose_train_part(2, *self._train_args(ids, lab, B, plan, cnt(p, B), 0), None, st), "pcg_choose_train_part")
+            self._enqueue_part(2, ids, lab, B, plan, cnt(p, B), 0)
             agg = self.agg.view(-1)[:R * B * F].view(R, B, F)
             if t + 1 == len(steps):
                 self._fresh = True
@@ -581,26 +579,19 @@ class FusedPCGNN:
                 break
             nids, nlab, nB, nplan = steps[t + 1]
             _lib.check(lib.pcg_dense_select_train(
-                g.desc_ref(), _p(self.theta), _p(self.m), _p(self.v), self.E, _p(ids), _p(lab), B, _p(agg), agg.stride(1),
-                _p(cnt(p, B)), C.c_void_p(plan), 1.0 / (B * self.scale), _p(self.clf_slots[p]), _p(self.logits), _p(self.center),
-                _p(self.row_loss), _p(self.acts), self.act_ld, _p(nids), _p(nlab), nB, _p(cnt(p ^ 1, nB)), C.c_void_p(nplan),
-                1.0 / (nB * self.scale), _p(self.clf_slots[p ^ 1]), _p(self.s0), _p(self.keys) if g.n_pos else None, self._thr,
-                self._rhos, 0, _p(self.data), self.list_capacity, _p(self.status), _p(self.sync), _p(self.clf_next), _p(self.slabs),
-                _p(self.step_counter), self.lambda_1, self.lr, b1, b2, self.eps, self.wd, st), "pcg_dense_select_train")
+                g.desc_ref(), self._st, self._sel, self._batch(ids, lab, B, plan, cnt(p, B)),
+                self._batch(nids, nlab, nB, nplan, cnt(p ^ 1, nB)), _p(agg), agg.stride(1), _p(self.clf_slots[p]), self._out,
+                _p(self.clf_slots[p ^ 1]), _p(self.s0), _p(self.keys) if g.n_pos else None, st), "pcg_dense_select_train")
             p ^= 1
         self.last_counts = self.cnt2[p].view(-1)[:R * B].view(R, B)
         self._fresh = True
 
     def flush(self):
         """Apply a deferred Adam update now (no-op on the device if none is pending).  Enqueued, not synchronised."""
-        b1, b2 = self.betas
         if self._theta_dirty:                        # (a training call since the last flush: an update may be pending)
             self._param_version += 1
             self._theta_dirty = False
-        _lib.check(self.lib.pcg_adam_flush(
-            _p(self.theta), _p(self.m), _p(self.v), _p(self.slabs), 0, self.n_params, self.n_rest, _p(self.step_counter),
-            _p(self.sync), self.lr, b1, b2, self.eps, self.wd, _p(self.clf_next), _p(self.acts), self.act_ld, self.F, self.E, self.R,
-            _p(self.wg_scratch), self._stream()), "pcg_adam_flush")
+        _lib.check(self.lib.pcg_adam_flush(self._st, 0, self.n_params, self.n_rest, self.F, self.R, self._stream()), "pcg_adam_flush")
 
     def _enqueue_step(self, ids, labels, B, plan: int, defer: bool, touched: Optional[int] = None,
                       next_touched: Optional[int] = None):
@@ -617,12 +608,10 @@ class FusedPCGNN:
 
     def _enqueue_adam(self, B, apply=True, want_grad=False, from_grad=False):
         """from_grad: the (all-reduced) flat gradient in self.grad is the single slab."""
-        b1, b2 = self.betas
         slabs, n_slabs = (self.grad, 1) if from_grad else (self.slabs, self.lib.pcg_dense_n_tiles(B))
         _lib.check(self.lib.pcg_adam_step(
-            _p(self.theta), _p(self.m), _p(self.v), _p(slabs), n_slabs, self.n_params,
-            _p(self.step_counter), self.lr, b1, b2, self.eps, self.wd, _p(self.grad) if want_grad else None,
-            1 if apply else 0, self._stream()), "pcg_adam_step")
+            _p(self.theta), _p(self.m), _p(self.v), _p(slabs), n_slabs, self.n_params, _p(self.step_counter), self._hyper,
+            _p(self.grad) if want_grad else None, 1 if apply else 0, self._stream()), "pcg_adam_step")
 
     def _enqueue_grad_slabs(self, ids, labels, B):
         """plan, scores, sort, select, gather, dense forward + backward partials: the gradient is left in the slabs (no Adam)."""
@@ -1142,9 +1131,7 @@ class FusedPCGNN:
             agg, _ = self._enqueue_choose(ids, labels, B, keys, True, plan, sort_in_kernel=False)
             self._enqueue_tail(ids, labels, B, agg, plan, True, adam_clf=4)
             self.step_counter -= 1
-            b1, b2 = self.betas
-            _lib.check(self.lib.pcg_wgrad(_p(self.acts), self.act_ld, B, self.F, self.E, self.R, None, None, None, None, self.lr,
-                                          b1, b2, self.eps, self.wd, _p(self.grad), 0, 1, _p(self.wg_scratch), None, self._stream()), "pcg_wgrad")
+            _lib.check(self.lib.pcg_wgrad(self._st_grad, B, self.F, self.R, _p(self.grad), 0, 1, None, self._stream()), "pcg_wgrad")
         self._lastB = B
         out = {}
         for name, view in self.views.items():

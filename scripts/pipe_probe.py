@@ -34,7 +34,7 @@ ids_all, lab_all = fz._ep_ids[:n], fz._ep_lab[:n]
 data = [fz.data, torch.zeros_like(fz.data)]
 cnt = [torch.empty_like(fz.cnt), torch.empty_like(fz.cnt)]
 agg = [torch.empty_like(fz.agg), torch.empty_like(fz.agg)]
-b1, b2 = fz.betas
+sel = [_lib.SelectWs(fz._thr, fz._rhos, _p(d), _p(fz.status), fz.list_capacity, 0) for d in data]
 
 
 def st(s):
@@ -70,10 +70,8 @@ def gather(t, s):
 def dense(t, s):
     ids, lab, Bt, plan = batch(t)
     a = agg[t & 1].view(-1)[:g.R * Bt * g.feat_dim].view(g.R, Bt, g.feat_dim)
-    _lib.check(lib.pcg_train_dense(g.desc_ref(), _p(fz.theta), _p(fz.m), _p(fz.v), fz.E, _p(ids), _p(lab), Bt, _p(a), a.stride(1),
-                                   _p(cnt[t & 1]), _p(data[t & 1]), C.c_void_p(plan), fz.list_capacity, fz.lambda_1, 1.0 / Bt, _p(fz.logits),
-                                   _p(fz.center), None, _p(fz.row_loss), _p(fz.slabs), _p(fz.step_counter), _p(fz.sync), fz.lr, b1, b2,
-                                   fz.eps, fz.wd, 2, None, 0, None, st(s)), "dense")
+    _lib.check(lib.pcg_train_dense(g.desc_ref(), fz._st, _lib.Batch(_p(ids), _p(lab), _p(cnt[t & 1]), plan, Bt, 1.0 / Bt), _p(a),
+                                   a.stride(1), sel[t & 1], fz._out, 2, None, st(s)), "dense")
 
 
 def seq(T, main):
@@ -175,7 +173,7 @@ def gather_k(t, k, s):
 
 def adam_only(s):
     _lib.check(lib.pcg_adam_step(_p(fz.theta), _p(fz.m), _p(fz.v), _p(fz.slabs), lib.pcg_dense_n_tiles(B), fz.n_params,
-                                 _p(fz.step_counter), fz.lr, b1, b2, fz.eps, fz.wd, None, 1, st(s)), "adam")
+                                 _p(fz.step_counter), fz._hyper, None, 1, st(s)), "adam")
 
 
 def phase1(T, streams):

@@ -86,8 +86,8 @@ def _worker(rank, world, port, q):
         P_ = ops._p
         assert d.lib.pcg_dense_step(g.desc_ref(), P_(theta0), E, P_(gb_ids), P_(gb_lab), world * B, P_(agg_g), F, 2.0,
                                     1.0 / (world * B), P_(lg), P_(ce), None, P_(rl), P_(slabs), None, st) == 0
-        assert d.lib.pcg_adam_step(None, None, None, P_(slabs), n_tiles, d.n_params, None, 0.01, 0.9, 0.999, 1e-8, 0.001,
-                                   P_(grad), 0, st) == 0
+        assert d.lib.pcg_adam_step(None, None, None, P_(slabs), n_tiles, d.n_params, None,
+                                   d._libmod.AdamHyper(0.01, 0.9, 0.999, 1e-8, 0.001), P_(grad), 0, st) == 0
         torch.cuda.synchronize()
         np.testing.assert_allclose(d.grad.cpu().numpy(), grad.cpu().numpy(), rtol=0, atol=2e-6)
         # logits of this rank's rows agree with the same rows in the global batch

@@ -641,7 +641,7 @@ def test_adam_step_matches_torch_adam(P):
                 slabs[:, ::7] = 0.0                     # exact zeros: the update is then pure weight decay / momentum
             counter += 1
             _lib.check(lib.pcg_adam_step(ops._p(theta), ops._p(m), ops._p(v), ops._p(slabs), n_slabs, n, ops._p(counter),
-                                         lr, b1, b2, eps, wd, ops._p(grad_out), 1, ops._stream(dev())), "pcg_adam_step")
+                                         _lib.AdamHyper(lr, b1, b2, eps, wd), ops._p(grad_out), 1, ops._stream(dev())), "pcg_adam_step")
             g = slabs.double().sum(0).float()
             np.testing.assert_allclose(grad_out.cpu().numpy(), g.cpu().numpy(), rtol=2e-6, atol=1e-6 * n_slabs)
             ref.grad = grad_out.clone()                 # the same summed gradient, so only the update rule is compared
@@ -1159,8 +1159,9 @@ def test_epoch_plans_and_in_kernel_sort_equal_separate_calls(P, B, n_pos):
         agg_a, cnt_a = ops.choose_aggregate(g, ids_s, lab_s, s0_a, keys_a, thr, rho, True, ws=ws_a)
         # the planned path: scores + unsorted keys, then select (sorting inside) + gather over slot s and the shared data part
         keys_b.zero_()
-        _lib.check(lib.pcg_step_scores_train(g.desc_ref(), _p(theta), _p(m), _p(v), E, _p(s0_b), _p(keys_b), _p(slabs), _p(step), _p(sync),
-                                             0.01, 0.9, 0.999, 1e-8, 0.0, None, st), "pcg_step_scores_train")
+        state = _lib.TrainState(theta=_p(theta), m=_p(m), v=_p(v), step_counter=_p(step), sync_words=_p(sync), slabs=_p(slabs), emb=E,
+                                 hyper=_lib.AdamHyper(0.01, 0.9, 0.999, 1e-8, 0.0))
+        _lib.check(lib.pcg_step_scores_train(g.desc_ref(), state, _p(s0_b), _p(keys_b), None, st), "pcg_step_scores_train")
         agg_b = torch.full((R, Bs, F), float("nan"), device=dev())
         cnt_b = torch.zeros(R, Bs, dtype=torch.int32, device=dev())
         _lib.check(lib.pcg_choose_gather_planned(g.desc_ref(), _p(ids[sl]), _p(lab[sl]), Bs, _p(s0_b), None, _p(keys_b), thr_c, rho_c, 1, 0,
@@ -1282,8 +1283,10 @@ def test_touched_rows_only_scoring(P, monkeypatch):
         got = maps[s_ * stride:(s_ + 1) * stride].cpu().numpy()
         assert np.array_equal(got, want), f"batch {s_}: marks = centres + neighbours + train positives"
         s0 = torch.full((w.n,), -12345.0, device=dev())
-        _lib.check(lib.pcg_step_scores_train(g.desc_ref(), _p(theta), _p(m), _p(v), E, _p(s0), _p(keys), _p(slabs), _p(step), _p(sync),
-                                             0.01, 0.9, 0.999, 1e-8, 0.0, ctypes_ptr(maps, s_ * stride), st), "pcg_step_scores_train")
+        state = _lib.TrainState(theta=_p(theta), m=_p(m), v=_p(v), step_counter=_p(step), sync_words=_p(sync), slabs=_p(slabs), emb=E,
+                                 hyper=_lib.AdamHyper(0.01, 0.9, 0.999, 1e-8, 0.0))
+        _lib.check(lib.pcg_step_scores_train(g.desc_ref(), state, _p(s0), _p(keys), ctypes_ptr(maps, s_ * stride), st),
+                   "pcg_step_scores_train")
         torch.cuda.synchronize()
         mk = torch.from_numpy(want[:w.n].astype(bool)).cuda()
         assert 0 < int(mk.sum()) < w.n
