@@ -138,20 +138,47 @@ SHAPES = {
     (16, 48, 5): ("dense_step_kernel<false, 0, 0, 0>", BATCHES_SHORT, 11),
     (24, 16, 5): ("dense_step_kernel<true, 0, 0, 0>", BATCHES_SHORT, 12),
 }
-REL_DEG = {1: (12,), 3: (4, 12, 3), 5: (4, 12, 3, 6, 2)}
+# Wide feature rows (the attribution tests parametrise over SHAPES: a table of its own keeps them as they are).  What each reaches
+# in the dense kernel's staging prologue (csrc/dense.h: element e = r * 16 * F + t * F + f of a tile's [R][16][F] aggregates;
+# the first 2048 elements are loaded two per thread, the rest by a loop with a summation of its own) and in the gather:
+#   (100, 64, 3)  F > 64 self-row loop; the loop beyond for relation 1 from tile row 4 on and all of relation 2; stride 100
+#   (68, 16, 2)   first width past 64; the loop beyond only for relation 1's tile rows 14 and 15; with the weights' LDS copy
+#   (260, 16, 1)  two accumulators per lane (stride > 256): gather_train_kernel<2>; the loop beyond from tile row 7 / 8 on
+#   (400, 16, 1)  the same without the weights' LDS copy; the loop beyond from tile row 5 / 6 on
+# Every batch of these has the graph's hub rows pinned into it (wide_pins): only a set of more than 128 entries - several gather
+# chunks - makes the staging code add partial sums, and random draws put one there in the largest batches only.
+WIDE_SHAPES = {
+    (100, 64, 3): ("dense_step_kernel<false, 0, 0, 0>", BATCHES_SHORT, 11),
+    (68, 16, 2): ("dense_step_kernel<true, 0, 0, 0>", BATCHES_SHORT, 12),
+    (260, 16, 1): ("dense_step_kernel<true, 0, 0, 0>", BATCHES_SHORT, 11),
+    (400, 16, 1): ("dense_step_kernel<false, 0, 0, 0>", BATCHES_SHORT, 11),
+}
+WIDE_LDS_BYTES = {(100, 64, 3): 98432, (68, 16, 2): 63104, (260, 16, 1): 123392, (400, 16, 1): 101216}
+REL_DEG = {1: (12,), 2: (12, 3), 3: (4, 12, 3), 5: (4, 12, 3, 6, 2)}
 MAX_BATCH = 2049
+TILE_ROWS, STAGED_DIRECT, CHUNK = 16, 2048, 128     # rows of a dense tile | aggregate elements loaded two per thread | a gather chunk
+
+
+def dense_smem_bytes(F, E, R, wlds):
+    """dense_smem_bytes of csrc/dense.h, restated: the dense launch's dynamic LDS with / without the weights' copy"""
+    kpad, tb, waves = 16, 16, 16
+    k1p, k2p = (2 * F + kpad - 1) // kpad * kpad, (F + R * E + kpad - 1) // kpad * kpad
+    ntile_e = E // 16
+    kparts = waves // ntile_e if ntile_e <= waves else 1
+    floats = R * tb * (k1p + 1) + tb * (k2p + 1) + (2 + R) * tb * (E + 1) + 4 * tb + 2 * E + 2 * F + 4 + 4
+    floats += (k2p + R * k1p) * (E + 4) if wlds else kparts * tb * E
+    return 4 * floats
 
 
 def dense_wlds(F, E, R):
     """The dense kernel's rule for staging the weight matrices in LDS (dense_wlds / dense_smem_bytes in csrc/dense.h),
     restated: which of the two run-time-shape kernels a shape gets."""
     kpad, tb, waves = 16, 16, 16
-    k1p, k2p = (2 * F + kpad - 1) // kpad * kpad, (F + R * E + kpad - 1) // kpad * kpad
+    k1p = (2 * F + kpad - 1) // kpad * kpad
     ntile_e = E // 16
     kparts = waves // ntile_e if ntile_e <= waves else 1
-    floats = R * tb * (k1p + 1) + tb * (k2p + 1) + (2 + R) * tb * (E + 1) + 4 * tb + 2 * E + 2 * F + 4 + 4
-    floats += (k2p + R * k1p) * (E + 4)
-    return 4 * floats <= 160 * 1024 and (waves * 64) % (E // 4) == 0 and kparts * tb * E <= R * k1p * (E + 4)
+    return (dense_smem_bytes(F, E, R, True) <= 160 * 1024 and (waves * 64) % (E // 4) == 0
+            and kparts * tb * E <= R * k1p * (E + 4))
 
 
 class GradCase:
@@ -176,16 +203,39 @@ class GradCase:
 
     @classmethod
     def of(cls, shape):
-        return cls(*shape, seed=SHAPES[shape][2])
+        return cls(*shape, seed=(SHAPES[shape] if shape in SHAPES else WIDE_SHAPES[shape])[2])
 
     def params(self):
         return {k: v.clone() for k, v in self._params.items()}
 
-    def batch(self, B, salt=0):
-        """(ids, labels) int64 numpy, drawn with replacement"""
+    def batch(self, B, salt=0, pins=None):
+        """(ids, labels) int64 numpy, drawn with replacement; pins {position: node}: those positions hold those nodes instead
+        of their draws (the other positions are what they are without pins)"""
         rs = np.random.RandomState(self.seed * 100003 + 31 * B + salt)
         ids = rs.randint(0, self.n, size=B)
+        for at, node in (pins or {}).items():
+            ids[at] = node
         return ids, self.labels[ids]
+
+    def hubs(self, k=2):
+        """the k nodes of the highest total degree (synth_graph's hub first: it is the largest row of every relation)"""
+        deg = sum(np.diff(indptr) for indptr, _ in self.csr)
+        return [int(v) for v in np.argsort(-deg, kind="stable")[:k]]
+
+    def wide_pins(self, B):
+        """{position: node} that puts rows of several gather chunks where the staging loops differ: the hub at tile rows 0 and
+        15 of the first tile, the second largest row at 1 and 14, and - a ragged batch - the hub on the last tile's first row;
+        B = 1: the hub itself"""
+        hub, second = self.hubs(2)
+        if B < TILE_ROWS:
+            return {0: hub}
+        pins = {0: hub, 1: second, TILE_ROWS - 2: second, TILE_ROWS - 1: hub}
+        if B % TILE_ROWS:
+            pins[B // TILE_ROWS * TILE_ROWS] = hub
+        return pins
+
+    def wide_batch(self, B, salt=0):
+        return self.batch(B, salt, pins=self.wide_pins(B))
 
     def host_sets(self, ids, labels, params=None):
         """the oracle's training-mode selection for a batch (CPU tests: no device to take the sets from)"""
@@ -201,6 +251,23 @@ class GradCase:
             sets.append(O.choose_sets(s0[torch.as_tensor(ids).long()], labels.tolist(), lists, nsc, self.train_pos, s0[pos],
                                       0.5, self.rho, True))
         return sets
+
+
+def staged_multi_chunk_rows(sets, F, B):
+    """Where the dense kernel's staging prologue meets rows of several gather chunks (sets of more than 128 entries) in a batch:
+    (rows the first 2048 aggregate elements of their tile cover, rows the loop beyond covers) as lists of (relation, batch row),
+    from a row's elements [r * 16 * F + t * F, + F) of its tile; a row across the boundary is in both."""
+    direct, beyond = [], []
+    for r, rel in enumerate(sets):
+        for b in range(B):
+            if len(rel[b]) <= CHUNK:
+                continue
+            e0 = r * TILE_ROWS * F + (b % TILE_ROWS) * F
+            if e0 < STAGED_DIRECT:
+                direct.append((r, b))
+            if e0 + F > STAGED_DIRECT:
+                beyond.append((r, b))
+    return direct, beyond
 
 
 def reference_pair(case, ids, labels, sets, params=None, dev_masks=None):

@@ -29,10 +29,52 @@ def host_refs(cases):
     return out
 
 
+@pytest.fixture(scope="module")
+def wide_refs():
+    """host_refs for the wide shapes, whose batches have the hub rows pinned into them: (shape, B, salt) -> (share of ambiguous
+    activations, the oracle's sets); salt 1: the second batch of the deferred-update test"""
+    out = {}
+    for shape, (_, batches, _) in D.WIDE_SHAPES.items():
+        c = D.GradCase.of(shape)
+        for B, salt in [(B, 0) for B in sorted(set(batches))] + [(1025, 1)]:
+            ids, lab = c.wide_batch(B, salt)
+            sets = c.host_sets(ids, lab)
+            out[shape, B, salt] = (D.reference_pair(c, ids, lab, D.sets_to_index(sets))[2], sets)
+    return out
+
+
 def test_wlds_rule_of_the_shapes():
     """which dense kernel each shape runs (the templated ones by their exact shape, the others by the shared-memory rule)"""
-    for (F, E, R), (kernel, _, _) in D.SHAPES.items():
+    for (F, E, R), (kernel, _, _) in list(D.SHAPES.items()) + list(D.WIDE_SHAPES.items()):
         assert D.dense_wlds(F, E, R) == kernel.startswith("dense_step_kernel<true"), (F, E, R)
+    for (F, E, R), (kernel, _, _) in D.WIDE_SHAPES.items():
+        assert kernel.endswith("<true, 0, 0, 0>") or kernel.endswith("<false, 0, 0, 0>")     # no templated instantiation
+        assert D.dense_smem_bytes(F, E, R, D.dense_wlds(F, E, R)) == D.WIDE_LDS_BYTES[F, E, R] <= 160 * 1024
+        assert F > 64 and (F + 3) // 4 * 4 <= 512
+    assert not set(D.SHAPES) & set(D.WIDE_SHAPES)
+
+
+def test_pins_change_their_positions_only():
+    c = D.GradCase.of((260, 16, 1))
+    for B in (1, 17, 1025, 2049):
+        pins = c.wide_pins(B)
+        (plain, _), (ids, lab) = c.batch(B), c.wide_batch(B)
+        other = np.array([b not in pins for b in range(B)])
+        assert np.array_equal(ids[other], plain[other]) and all(ids[b] == v for b, v in pins.items())
+        assert np.array_equal(lab, c.labels[ids])
+        assert 0 in pins and (B < 16 or 15 in pins) and (B % 16 == 0 or B < 16 or B // 16 * 16 in pins)
+    assert c.hubs(1) == [7]                                     # synth_graph's hub
+
+
+def test_wide_batches_stage_rows_of_several_chunks_in_both_loops(wide_refs):
+    """with the oracle's sets (the device's are asserted again on the GPU): every wide batch of a whole tile has a pinned set of
+    more than 128 entries among the first 2048 staged aggregate elements and one in the loop beyond"""
+    cases = {shape: D.GradCase.of(shape) for shape in D.WIDE_SHAPES}
+    for (shape, B, salt), (_, sets) in wide_refs.items():
+        pins = cases[shape].wide_pins(B)
+        direct, beyond = D.staged_multi_chunk_rows(sets, shape[0], B)
+        assert [x for x in direct if x[1] in pins], (shape, B, salt)
+        assert B < D.TILE_ROWS or [x for x in beyond if x[1] in pins], (shape, B, salt)
 
 
 @pytest.mark.parametrize("shape,B", [((25, 64, 3), 65), ((16, 48, 5), 17), ((32, 128, 3), 1)])
@@ -63,8 +105,9 @@ def test_masked_reference_is_plain_autograd(cases, shape, B):
         assert D.rel_err(r64["grads"][k], p[k].grad) <= 1e-12, k
 
 
-def test_every_case_keeps_the_ambiguous_cap(host_refs):
+def test_every_case_keeps_the_ambiguous_cap(host_refs, wide_refs):
     over = {k: v[2] for k, v in host_refs.items() if v[2] > D.AMBIGUOUS_CAP}
+    over.update({k: v[0] for k, v in wide_refs.items() if v[0] > D.AMBIGUOUS_CAP})
     assert not over, f"ambiguous ReLU pre-activations above {D.AMBIGUOUS_CAP}: {over} - change the seed or the weight scale"
 
 

@@ -29,6 +29,19 @@ ratio), `of bound` = e_kernel / (8 * e_f32 + 2^-20) over all entries:
     (16, 48, 5)      dense_step_kernel<false, 0, 0, 0>       2.28               0.16     | -                 -
     (24, 16, 5)      dense_step_kernel<true, 0, 0, 0>        1.43               0.13     | -                 -
 
+Wide feature rows (dense_ref.WIDE_SHAPES; profiles/r17/wide_f64_ratios.txt): the dense staging's F > 64 self-row loop and its second
+aggregate loop (elements beyond the first 2048 of a tile's [R][16][F] aggregates, with a summation of its own), and stride > 256 -
+two accumulators per lane, gather_train_kernel<2> with the Adam and weight-gradient riders.  Every batch of these shapes has the
+graph's two largest rows pinned at tile rows 0, 1, 14, 15 of the first tile and the hub on a ragged batch's last tile
+(dense_ref.wide_pins), and the test asserts from the device's own sets (more than 128 entries: several gather chunks) that a
+pinned row is staged by the first 2048 elements and - every batch of a whole tile - one by the loop beyond:
+
+    shape (F, E, R)  kernel                                  gradients() ratio  of bound | train step ratio  of bound
+    (100, 64, 3)     dense_step_kernel<false, 0, 0, 0>       2.33               0.14     | 3.08              0.18
+    (68, 16, 2)      dense_step_kernel<true, 0, 0, 0>        1.44               0.12     | -                 -
+    (260, 16, 1)     dense_step_kernel<true, 0, 0, 0>        2.09               0.20     | 4.11              0.19
+    (400, 16, 1)     dense_step_kernel<false, 0, 0, 0>       2.80               0.24     | -                 -
+
 Every kernel error is a few 1e-7 of the tensor's largest element - the size of the float32 CPU run's own - so the bound is
 mostly its floor; nothing came near the margin of 8.  ((10, 16, 1) runs the run-time-shape kernel WITHOUT the weights' LDS copy:
 its K-split partial tiles do not fit where the W_intra copy would be; (24, 16, 5) is here for the run-time-shape kernel with it.)
@@ -44,6 +57,11 @@ from tests.util import PARAM_KEYS, build_model
 pytestmark = pytest.mark.gpu
 
 TRAIN_SHAPES = [(32, 64, 3), (25, 128, 3)]
+WIDE_TRAIN_SHAPES = [(100, 64, 3), (260, 16, 1)]      # gather_train_kernel<1> at stride 100 / <2> at stride 260, with their riders
+# (shape, B) of the first-moment test: the four boundary sizes for the project's shapes, a short and a long batch for the wide ones
+TRAIN_CASES = ([pytest.param(s, B, id=f"shape{i}-{B}") for i, s in enumerate(TRAIN_SHAPES) for B in (17, 1024, 1025, 2049)]
+               + [pytest.param(s, B, id=f"shape{len(TRAIN_SHAPES) + i}-{B}") for i, s in enumerate(WIDE_TRAIN_SHAPES)
+                  for B in (17, 1025)])
 
 
 @pytest.fixture(scope="module")
@@ -67,6 +85,31 @@ def on_dev(ids, lab):
     return torch.from_numpy(ids.astype(np.int32)).to(dev()), torch.from_numpy(lab.astype(np.int32)).to(dev())
 
 
+def table_of(shape):
+    return D.SHAPES if shape in D.SHAPES else D.WIDE_SHAPES
+
+
+def draw(c, shape, B, salt=0):
+    """the case's batch; a wide shape's with the hub rows pinned into it (dense_ref.wide_pins)"""
+    return c.wide_batch(B, salt) if shape in D.WIDE_SHAPES else c.batch(B, salt)
+
+
+def staged_pins(c, shape, sets, B):
+    """Wide shapes: the PINNED rows of several gather chunks (the device's own sets: more than 128 entries) the dense kernel's
+    staging prologue covers with its first 2048 aggregate elements / with the loop beyond, as (relation, batch row) lists;
+    asserted non-empty where the batch has a whole first tile.  None for the project's shapes."""
+    if shape not in D.WIDE_SHAPES:
+        return None
+    pins = c.wide_pins(B)
+    direct, beyond = D.staged_multi_chunk_rows(sets, c.f, B)
+    direct, beyond = [x for x in direct if x[1] in pins], [x for x in beyond if x[1] in pins]
+    print(f"{shape} B={B}: multi-chunk pinned rows (relation, row): first 2048 elements {direct}, loop beyond {beyond}")
+    assert direct, f"{shape} B={B}: no row of several chunks among the first 2048 staged elements"
+    if B >= D.TILE_ROWS:
+        assert beyond, f"{shape} B={B}: no row of several chunks in the staging loop beyond 2048 elements"
+    return direct, beyond
+
+
 def reference(c, fz, ids, lab, sets, B, params=None):
     """reference_pair with the engine's ReLU masks of its last acts-mode dense launch; the cap and the mask rule asserted"""
     masks = D.device_masks(fz.acts, c.f, c.emb, c.R, B)
@@ -77,16 +120,18 @@ def reference(c, fz, ids, lab, sets, B, params=None):
     return r64, r32
 
 
-@pytest.mark.parametrize("shape", list(D.SHAPES))
+@pytest.mark.parametrize("shape", list(D.SHAPES) + list(D.WIDE_SHAPES))
 def test_gradients_against_float64(P, shape):
-    kernel, batches, _ = D.SHAPES[shape]          # (which dense kernel runs: asserted by the shared-memory rule on the host)
+    kernel, batches, _ = table_of(shape)[shape]   # (which dense kernel runs: asserted by the shared-memory rule on the host)
     c = D.GradCase.of(shape)
     m, fz = engine(P, c)
     tally = Tally(f"{shape} gradients()")
+    staged = []
     for B in batches:
-        ids, lab = c.batch(B)
+        ids, lab = draw(c, shape, B)
         ids_d, lab_d = on_dev(ids, lab)
         sets = m.inter1.chosen_sets(ids_d, lab_d, True)
+        staged.append(staged_pins(c, shape, sets, B))
         got = {}
         for via in ("acts", "slabs"):
             grads = fz.gradients(ids_d, lab_d, via=via)
@@ -100,21 +145,23 @@ def test_gradients_against_float64(P, shape):
             tally.check(f"B={B} via={via} logits", logits, r64["logits"], r32["logits"])
             tally.check(f"B={B} via={via} label-aware logits", center, r64["center"], r32["center"])
     assert int(fz.step_counter.item()) == 0
+    if shape in D.WIDE_SHAPES:      # both staging loops met a row of several chunks (every batch of a whole tile: staged_pins)
+        assert any(d for d, _ in staged) and any(b for _, b in staged)
     tally.done()
 
 
-@pytest.mark.parametrize("B", [17, 1024, 1025, 2049])
-@pytest.mark.parametrize("shape", TRAIN_SHAPES)
+@pytest.mark.parametrize("shape,B", TRAIN_CASES)
 def test_train_step_gradient_through_first_moment(P, shape, B):
     """One deferred train_step, then flush(), on an engine of max_batch 2049: from m = v = 0 the step leaves
     m1 = (1 - beta1) (g + wd theta0), so g = m1 / (1 - beta1) - wd theta0.  (B = 17: the flush launch's block count is the
     engine's 129, the device's pending word says 2.)"""
     c = D.GradCase.of(shape)
     m, fz = engine(P, c)
-    ids, lab = c.batch(B)
+    ids, lab = draw(c, shape, B)
     ids_d, lab_d = on_dev(ids, lab)
     theta0 = fz.theta.clone()
     sets = m.inter1.chosen_sets(ids_d, lab_d, True)
+    staged_pins(c, shape, sets, B)
     fz.train_step(ids_d, lab_d, defer=True)
     fz.flush()
     loss = float(fz.last_loss())
@@ -127,7 +174,7 @@ def test_train_step_gradient_through_first_moment(P, shape, B):
     tally.done()
 
 
-@pytest.mark.parametrize("shape", TRAIN_SHAPES)
+@pytest.mark.parametrize("shape", TRAIN_SHAPES + [(260, 16, 1)])
 def test_deferred_update_riding_in_the_next_step(P, shape):
     """train_step(defer=True) at B = 2049, again at B = 1025, flush(): the first update rides in the second step's gather launch
     (three workgroups per weight-gradient tile, sized for the engine's 129 blocks).  A second engine flushes in between: both
@@ -135,7 +182,7 @@ def test_deferred_update_riding_in_the_next_step(P, shape):
     (m2 - beta1 m1) / (1 - beta1) - wd theta1, compared with the reference at theta1 with the device's sets at theta1."""
     c = D.GradCase.of(shape)
     (ma, fa), (mb, fb) = engine(P, c), engine(P, c)
-    (ids1, lab1), (ids2, lab2) = c.batch(2049), c.batch(1025, salt=1)
+    (ids1, lab1), (ids2, lab2) = draw(c, shape, 2049), draw(c, shape, 1025, salt=1)
     d1, d2 = on_dev(ids1, lab1), on_dev(ids2, lab2)
     fa.train_step(*d1, defer=True)
     fa.train_step(*d2, defer=True)
@@ -146,6 +193,7 @@ def test_deferred_update_riding_in_the_next_step(P, shape):
     theta1, m1, v1 = fb.theta.clone(), fb.m.clone(), fb.v.clone()
     params1 = {k: v.detach().cpu().clone() for k, v in fb.views.items()}
     sets2 = mb.inter1.chosen_sets(*d2, True)
+    staged_pins(c, shape, sets2, 1025)
     fb.train_step(*d2, defer=True)
     fb.flush()
     torch.cuda.synchronize()
