@@ -76,7 +76,8 @@ typedef struct pcg_graph_desc {
 
 /* library / build identification: "pcgnn_hip gfx950 <abi>" (host pointer, static) */
 const char *pcg_version(void);
-int pcg_abi_version(void);   /* 12 (the training entry points take parameter structs; added: pcg_abi_layout) */
+int pcg_abi_version(void);   /* 13 (added: pcg_explain_out, pcg_explain_new, pcg_explain_new_workspace_bytes; 12: the training entry
+                                points take parameter structs, pcg_abi_layout) */
 
 /* ---- parameter structs of the training entry points ------------------------------------------
  * What a training engine owns is handed over as structs, by const pointer: an entry point reads them during the call and keeps
@@ -138,7 +139,25 @@ typedef struct pcg_dense_out {
     float *logits, *center, *combined, *row_loss;
 } pcg_dense_out;
 
-/* Layout of struct `which` (0 pcg_adam_hyper, 1 pcg_train_state, 2 pcg_select_ws, 3 pcg_batch, 4 pcg_dense_out) as this library
+/* What pcg_explain_new writes for its n query rows, in three groups; a group is requested by setting ALL of its pointers and left
+ * out by setting none of them (some set, others NULL: PCG_E_ARG).  At least one group must be requested. */
+typedef struct pcg_explain_out {
+    /* the attribution group (pcg_attr_set's outputs) */
+    float *logits;               /* [n][2] */
+    float *d_self;               /* [n][feat_dim] */
+    float *d_agg;                /* [n_rel][n][feat_dim] */
+    float *self_contrib;         /* [n] */
+    float *rel_contrib;          /* [n_rel][n] */
+    /* the chosen group (pcg_chosen_set's outputs) */
+    const int64_t *out_begin;    /* int64 [n_rel * n + 1]: an INPUT, formed on the host as for pcg_chosen_set */
+    int32_t *out_ids;            /* [out_begin[n_rel * n]] */
+    float *out_dist;             /* [out_begin[n_rel * n]] */
+    /* every chosen neighbour's share (pcg_attr_neighbours' output): only with both groups above */
+    float *neigh_contrib;        /* [out_begin[n_rel * n]] */
+} pcg_explain_out;
+
+/* Layout of struct `which` (0 pcg_adam_hyper, 1 pcg_train_state, 2 pcg_select_ws, 3 pcg_batch, 4 pcg_dense_out, 5 pcg_explain_out)
+ * as this library
  * was compiled: out[0] = sizeof, out[1 ..] = offsetof of every member in declaration order (padding members included).
  * Returns the number of values written, or PCG_E_ARG (unknown struct, out NULL, cap too small).  Host only: no device call. */
 int32_t pcg_abi_layout(int32_t which, int64_t *out, int32_t cap);
@@ -703,6 +722,35 @@ int pcg_attr_set(const pcg_graph_desc *g, const float *theta, int32_t emb, const
                  void *stream);
 int pcg_attr_neighbours(const pcg_graph_desc *g, const int64_t *flat_offsets, const int32_t *ids, int32_t n_rel, int32_t n,
                         const float *d_agg, float *out, uint32_t *status, void *stream);
+/* Explaining nodes that are NOT in the graph (FusedPCGNN.chosen_new / attribute_new): for the rows ids [n] of a query batch q
+ * (pcg_infer_new's descriptor, ids, s0 / score_base, thresholds, workspace and list_capacity contracts, word for word) the chosen
+ * neighbours, ranked, with their distances, and / or the exact input attributions of the gnn logits, from ONE selection per chunk.
+ * out: the groups of pcg_explain_out - attribution (logits, d_self, d_agg, self_contrib, rel_contrib: pcg_attr_set's outputs for
+ * s = w0 * logit0 + w1 * logit1; w0, w1 finite, else PCG_E_ARG), chosen (out_begin - an input: row (r, i) keeps exactly
+ * pcg_sel_capacity_row(deg_q, threshold, 0, 0, 0, 0) entries -, out_ids, out_dist: pcg_chosen_set's outputs; the ids are GLOBAL,
+ * in [0, N + nq)) and neigh_contrib (pcg_attr_neighbours' output for those lists and d_agg; only beside both other groups).  A
+ * NULL struct, no group, a half-filled group or neigh_contrib without both groups is PCG_E_ARG before anything is enqueued.
+ * Checks: pcg_infer_new's, and pcg_attr_set's bound on the backward's LDS (PCG_E_UNSUPPORTED).
+ * Launches: pcg_infer_new's front (the base table's scores only when score_base != 0, the query rows' scores -> s0[N, N + nq), the
+ * look-back words zeroed); per chunk of chunk_rows ids plan (test mode, over q's rows) -> select ONCE (centre b's score
+ * s0[ids[b] + N]) -> [chosen] the two rank launches of pcg_rank_lists directly behind it (they only read the lists and the plan)
+ * -> [attribution] pcg_infer_new's two-table gather -> pcg_attr_set's dense launch with the self rows from q->X; after the last
+ * chunk -> [neigh_contrib] one gather-dot over all R * n ranked rows (entry id < N reads row id of g->X, id >= N row id - N of
+ * q->X; its tail slices sized by q->max_degree).  Never synchronises, never allocates.  n == 0 or nq == 0: nothing is enqueued.
+ * workspace: pcg_explain_new_workspace_bytes (== pcg_infer_new_workspace_bytes for the same arguments; negative = rejected).
+ * Status bits: PCG_ST_SEL_OVERFLOW (list_capacity too small: that chunk selects nothing; its ranked rows are then not written -
+ * PCG_ST_RANK_MISMATCH - and what the gather-dot reads in their place is clamped), PCG_ST_LIST_ID_RANGE (a list entry outside
+ * [0, N + nq): skipped by the gather like a hole, clamped for the rank's score read and for the gather-dot's row read - a report,
+ * not a guard: the caller's contract on q->indices is pcg_infer_new's), PCG_ST_RANK_MISMATCH (a row whose kept count on the device
+ * is not its extent in out_begin, or whose extent leaves the arrays, is not written; nothing is written outside a row's extent).
+ * Parity: every value is bit for bit what pcg_chosen_set, pcg_attr_set and pcg_attr_neighbours write for node N + j on a graph
+ * built with the query rows appended to the base table and CSR, with the same theta - whichever groups are requested, whatever
+ * the chunk or the row's position: the table a row is read from changes an address, not a value or an order. */
+int64_t pcg_explain_new_workspace_bytes(const pcg_graph_desc *g, const pcg_graph_desc *q, int32_t emb, int32_t chunk_rows,
+                                        int64_t list_capacity);
+int pcg_explain_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float *theta, int32_t emb, const int32_t *ids, int32_t n,
+                    int32_t chunk_rows, float *s0, int32_t score_base, const double *thresholds, void *workspace,
+                    int64_t list_capacity, float w0, float w1, const pcg_explain_out *out, uint32_t *status, void *stream);
 int pcg_step_front_train(const pcg_graph_desc *g, const pcg_train_state *st, float *s0, uint64_t *pos_keys, const pcg_batch *batch,
                          const pcg_select_ws *sel, void *stream);
 /* The optimizer of a data-parallel / partitioned step, whose gradient passes through an all-reduce: pcg_grad_reduce sums the

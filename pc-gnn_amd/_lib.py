@@ -18,7 +18,7 @@ PCG_ST_SORT_OVERFLOW = 8
 PCG_ST_EVAL_INPUT = 16
 PCG_ST_RANK_MISMATCH = 32
 PCG_NORM_COUNT, PCG_NORM_SQRT_COUNT = 0, 1
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class GraphDesc(C.Structure):
@@ -67,8 +67,13 @@ class DenseOut(C.Structure):
     _fields_ = [("logits", _P), ("center", _P), ("combined", _P), ("row_loss", _P)]
 
 
-ABI_STRUCTS = (AdamHyper, TrainState, SelectWs, Batch, DenseOut)     # pcg_abi_layout's `which`, in order
-_H, _ST, _SEL, _B, _OUT = (C.POINTER(t) for t in ABI_STRUCTS)
+class ExplainOut(C.Structure):
+    _fields_ = [("logits", _P), ("d_self", _P), ("d_agg", _P), ("self_contrib", _P), ("rel_contrib", _P), ("out_begin", _P),
+                ("out_ids", _P), ("out_dist", _P), ("neigh_contrib", _P)]
+
+
+ABI_STRUCTS = (AdamHyper, TrainState, SelectWs, Batch, DenseOut, ExplainOut)     # pcg_abi_layout's `which`, in order
+_H, _ST, _SEL, _B, _OUT, _XOUT = (C.POINTER(t) for t in ABI_STRUCTS)
 
 # name -> (restype, argtypes); must list every symbol include/pcgnn.h declares
 PROTOTYPES = {
@@ -134,6 +139,9 @@ PROTOTYPES = {
                                        C.POINTER(_F64), _P, _I32, _I64, _P, _P, _P, _P]),
     "pcg_infer_new_workspace_bytes": (_I64, [_G, _G, _I32, _I32, _I64]),
     "pcg_infer_new": (C.c_int, [_G, _G, _P, _I32, _P, _I32, _I32, _P, _I32, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P]),
+    "pcg_explain_new_workspace_bytes": (_I64, [_G, _G, _I32, _I32, _I64]),
+    "pcg_explain_new": (C.c_int, [_G, _G, _P, _I32, _P, _I32, _I32, _P, _I32, C.POINTER(_F64), _P, _I64, C.c_float, C.c_float, _XOUT,
+                                  _P, _P]),
     "pcg_rank_lists": (C.c_int, [_G, _P, _I32, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "pcg_rank_minority": (C.c_int, [_G, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pcg_chosen_workspace_bytes": (_I64, [_G, _I32, _I64]),

@@ -15,9 +15,11 @@
 //                         then d_self = dx0 + sum_r dcat_r[:, :F] (r = 0 .. R-1), d_agg_r = dcat_r[:, F:], and the two inner
 //                         products per row, 16 lanes each, a fixed order.  Every GEMM is v_mfma_f32_16x16x4_f32.
 //   pcg_attr_neighbours : out[e] = <X[ids[e]], d_agg[r, i]> / len for every entry e of row (r, i) of ranked lists.
+// Both launches are exported (attr.h) to pcg_explain_new (explain_new.hip): the dense launch with the self rows of a query
+// table, the gather-dot in its two-table form (entry id >= N reads row id - N of the query table: an address, not a value).
 //
 // A row's results depend on the row alone: no atomics on floats, no workgroup waits for another, every sum in a fixed order.
-#include "infer.h"
+#include "attr.h"
 
 namespace pcg {
 
@@ -212,6 +214,8 @@ __global__ void __launch_bounds__(DENSE_THREADS) attr_dense_kernel(const DenseAr
     }
 }
 
+bool attr_shape_ok(int F, int E, int R) { return attr_smem_bytes(F, E, R, infer_wlds(F, E, R)) <= 160 * 1024; }
+
 static int launch_attr_dense(const DenseArgs &a, const AttrArgs &x, int B, hipStream_t st) {
     const int F = a.feat_dim, E = a.emb, R = a.n_rel;
     const bool wlds = infer_wlds(F, E, R);            // (the forward's own choice: the logits are pcg_infer_set's)
@@ -260,7 +264,9 @@ constexpr int NEIGH_SHORT = 128, NEIGH_SLICE = 256, NEIGH_MAX_TAIL = 15, NEIGH_T
 struct NeighArgs {
     const float *X;
     int32_t F, stride;
-    int64_t n_nodes;
+    int64_t n_nodes;            // rows an id may name (TWO: base + query rows)
+    const float *Xq;            // TWO: the query table, row id - n_base for id >= n_base
+    int64_t n_base;
     const int64_t *off;         // [rows + 1]
     const int32_t *ids;         // [off[rows]]
     int64_t rows;               // R * n
@@ -270,7 +276,10 @@ struct NeighArgs {
     int32_t n_tail;
 };
 
-// entries first, first + step, .. < last of a row that begins at `lo` and has `len` entries (all uniform over the lane group)
+// entries first, first + step, .. < last of a row that begins at `lo` and has `len` entries (all uniform over the lane group).
+// TWO: ids of the base table and of the query table behind it (gather_chunks_two's form: the clamped id in a register,
+// id - n_base >= 0 picks between two addresses formed from it, the row loads unconditional either way)
+template <bool TWO>
 __device__ __forceinline__ void neigh_span(const NeighArgs &a, const float (&d)[2][4], const bool (&has)[2], const int (&chc)[2],
                                            int64_t lo, int64_t len, int64_t first, int64_t last, int step, int sub, int lpr) {
     typedef float f4 __attribute__((ext_vector_type(4)));
@@ -291,6 +300,10 @@ __device__ __forceinline__ void neigh_span(const NeighArgs &a, const float (&d)[
             bad = bad || (oob && e0 + (int64_t)u * step < last);
             const int64_t idc = id[u] < 0 ? 0 : ((int64_t)id[u] >= a.n_nodes ? a.n_nodes - 1 : (int64_t)id[u]);
             const float *xr = a.X + (size_t)idc * a.stride;
+            if constexpr (TWO) {
+                const int64_t qr = idc - a.n_base;
+                xr = qr >= 0 ? a.Xq + (size_t)qr * a.stride : xr;
+            }
 #pragma unroll
             for (int k = 0; k < 2; ++k) xv[u][k] = *reinterpret_cast<const f4 *>(xr + 4 * chc[k]);
         }
@@ -327,6 +340,7 @@ __device__ __forceinline__ void neigh_load_d(const NeighArgs &a, int64_t row, fl
         }
 }
 
+template <bool TWO>
 __global__ void __launch_bounds__(NEIGH_THREADS) attr_neigh_kernel(const NeighArgs a) {
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int lpr = lanes_per_row(a.stride), rpw = PCG_WAVE / lpr;
@@ -354,7 +368,7 @@ __global__ void __launch_bounds__(NEIGH_THREADS) attr_neigh_kernel(const NeighAr
         const int64_t n_e = (a.n_tail > 0 && len > NEIGH_SHORT) ? NEIGH_SHORT : len;
         if (n_e <= 0) return;
         neigh_load_d(a, rc, d, has, chc);
-        neigh_span(a, d, has, chc, lo, len, 0, n_e, 1, sub, lpr);
+        neigh_span<TWO>(a, d, has, chc, lo, len, 0, n_e, 1, sub, lpr);
         return;
     }
     if (__ballot(len > NEIGH_SHORT) == 0ull) return;
@@ -367,8 +381,66 @@ __global__ void __launch_bounds__(NEIGH_THREADS) attr_neigh_kernel(const NeighAr
         const int64_t last = first + per < len_q ? first + per : len_q;
         // (a group beyond the slice runs an empty span: no lane leaves the loop body's common path)
         neigh_load_d(a, wave_global * rpw + q, d, has, chc);
-        neigh_span(a, d, has, chc, lo_q, len_q, first + grp, last > first ? last : first, rpw, sub, lpr);
+        neigh_span<TWO>(a, d, has, chc, lo_q, len_q, first + grp, last > first ? last : first, rpw, sub, lpr);
     }
+}
+
+// (attr.h) the attribution dense launch of a chunk
+int attr_chunk(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *cid, int32_t B, const Workspace &w, float *agg,
+               const int32_t *cnt, int64_t off, int32_t n, float w0, float w1, float *out_logits, float *center_scratch,
+               float *out_d_self, float *out_d_agg, float *out_self_contrib, float *out_rel_contrib, hipStream_t st) {
+    const int F = g->feat_dim;
+    DenseExtra ex;
+    ex.chunk_begin = w.chunk_begin;
+    ex.partial = w.partial;
+    ex.cnt = cnt;
+    ex.partial_stride = g->feat_stride;
+    DenseArgs a;
+    int n_sort_blocks = 0;
+    const int rc = dense_args(a, n_sort_blocks, g, theta, emb, cid, nullptr, B, agg, F, 0.f, 1.f, out_logits + 2 * off, center_scratch,
+                              nullptr, nullptr, nullptr, nullptr, ex);
+    if (rc != PCG_OK) return rc;
+    a.stamps = nullptr;
+    AttrArgs x;
+    x.w0 = w0;
+    x.w1 = w1;
+    x.d_self = out_d_self + (size_t)off * F;
+    x.d_agg = out_d_agg + (size_t)off * F;
+    x.agg_rstride = (int64_t)n * F;
+    x.self_contrib = out_self_contrib + off;
+    x.rel_contrib = out_rel_contrib + off;
+    x.n_total = n;
+    return launch_attr_dense(a, x, B, st);
+}
+
+// (attr.h) the gather-dot launch
+int launch_attr_neigh(const float *X, int64_t base_rows, const float *query_X, int64_t query_rows, int32_t feat_dim,
+                      int32_t feat_stride, int32_t max_degree, const int64_t *flat_offsets, const int32_t *ids, int64_t rows,
+                      const float *d_agg, float *out, uint32_t *status, hipStream_t st) {
+    NeighArgs a;
+    a.X = X;
+    a.F = feat_dim;
+    a.stride = feat_stride;
+    a.n_nodes = base_rows + query_rows;
+    a.Xq = query_X;
+    a.n_base = base_rows;
+    a.off = flat_offsets;
+    a.ids = ids;
+    a.rows = rows;
+    a.d_agg = d_agg;
+    a.out = out;
+    a.status = status;
+    const int64_t over = (int64_t)max_degree - NEIGH_SHORT;
+    const int64_t tail = over > 0 ? (over + NEIGH_SLICE - 1) / NEIGH_SLICE : 0;
+    a.n_tail = (int32_t)(tail < NEIGH_MAX_TAIL ? tail : NEIGH_MAX_TAIL);
+    const int rows_per_block = (NEIGH_THREADS / PCG_WAVE) * (PCG_WAVE / lanes_per_row(a.stride));
+    const int64_t blocks = (a.rows + rows_per_block - 1) / rows_per_block;
+    if (blocks >= (1ll << 31)) return PCG_E_ARG;
+    const dim3 grid((unsigned)blocks, (unsigned)(1 + a.n_tail));
+    if (query_X) hipLaunchKernelGGL(attr_neigh_kernel<true>, grid, dim3(NEIGH_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(attr_neigh_kernel<false>, grid, dim3(NEIGH_THREADS), 0, st, a);
+    PCG_LAUNCH_CHECK();
+    return PCG_OK;
 }
 
 }  // namespace pcg
@@ -388,7 +460,7 @@ int pcg_attr_set(const pcg_graph_desc *g, const float *theta, int32_t emb, const
     int rc = pcg::infer_carve(g, 2, true, emb, chunk_rows, list_capacity, c);
     if (rc != PCG_OK) return rc;
     const int F = g->feat_dim, E = emb, R = g->n_rel;
-    if (pcg::attr_smem_bytes(F, E, R, pcg::infer_wlds(F, E, R)) > 160 * 1024) return PCG_E_UNSUPPORTED;
+    if (!pcg::attr_shape_ok(F, E, R)) return PCG_E_UNSUPPORTED;
     if (n == 0) return PCG_OK;
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     float *agg = reinterpret_cast<float *>(ws + c.agg), *center_scratch = reinterpret_cast<float *>(ws + c.center);
@@ -402,27 +474,8 @@ int pcg_attr_set(const pcg_graph_desc *g, const float *theta, int32_t emb, const
         int rc = pcg_gather_lists_planned(g->X, F, g->feat_stride, g->n_nodes, R * B, d.cnt, g, B, d.data, w.counters, list_capacity,
                                           agg, F, status, stream);
         if (rc != PCG_OK) return rc;
-        pcg::DenseExtra ex;
-        ex.chunk_begin = w.chunk_begin;
-        ex.partial = w.partial;
-        ex.cnt = d.cnt;
-        ex.partial_stride = g->feat_stride;
-        pcg::DenseArgs a;
-        int n_sort_blocks = 0;
-        rc = pcg::dense_args(a, n_sort_blocks, g, theta, emb, cid, nullptr, B, agg, F, 0.f, 1.f, out_logits + 2 * off, center_scratch,
-                             nullptr, nullptr, nullptr, nullptr, ex);
-        if (rc != PCG_OK) return rc;
-        a.stamps = nullptr;
-        pcg::AttrArgs x;
-        x.w0 = w0;
-        x.w1 = w1;
-        x.d_self = out_d_self + (size_t)off * F;
-        x.d_agg = out_d_agg + (size_t)off * F;
-        x.agg_rstride = (int64_t)n * F;
-        x.self_contrib = out_self_contrib + off;
-        x.rel_contrib = out_rel_contrib + off;
-        x.n_total = n;
-        return pcg::launch_attr_dense(a, x, B, d.st);
+        return pcg::attr_chunk(g, theta, emb, cid, B, w, agg, d.cnt, off, n, w0, w1, out_logits, center_scratch, out_d_self, out_d_agg,
+                               out_self_contrib, out_rel_contrib, d.st);
     });
 }
 
@@ -433,27 +486,8 @@ int pcg_attr_neighbours(const pcg_graph_desc *g, const int64_t *flat_offsets, co
     if ((reinterpret_cast<uintptr_t>(g->X) & 15u) != 0) return PCG_E_ARG;
     if (n == 0) return PCG_OK;
     if (!ids || !d_agg || !out) return PCG_E_ARG;
-    pcg::NeighArgs a;
-    a.X = g->X;
-    a.F = g->feat_dim;
-    a.stride = g->feat_stride;
-    a.n_nodes = g->n_nodes;
-    a.off = flat_offsets;
-    a.ids = ids;
-    a.rows = (int64_t)n_rel * n;
-    a.d_agg = d_agg;
-    a.out = out;
-    a.status = status;
-    const int64_t over = (int64_t)g->max_degree - pcg::NEIGH_SHORT;
-    const int64_t tail = over > 0 ? (over + pcg::NEIGH_SLICE - 1) / pcg::NEIGH_SLICE : 0;
-    a.n_tail = (int32_t)(tail < pcg::NEIGH_MAX_TAIL ? tail : pcg::NEIGH_MAX_TAIL);
-    const int rows_per_block = (pcg::NEIGH_THREADS / PCG_WAVE) * (PCG_WAVE / pcg::lanes_per_row(a.stride));
-    const int64_t blocks = (a.rows + rows_per_block - 1) / rows_per_block;
-    if (blocks >= (1ll << 31)) return PCG_E_ARG;
-    hipLaunchKernelGGL(pcg::attr_neigh_kernel, dim3((unsigned)blocks, (unsigned)(1 + a.n_tail)), dim3(pcg::NEIGH_THREADS), 0,
-                       static_cast<hipStream_t>(stream), a);
-    PCG_LAUNCH_CHECK();
-    return PCG_OK;
+    return pcg::launch_attr_neigh(g->X, g->n_nodes, nullptr, 0, g->feat_dim, g->feat_stride, g->max_degree, flat_offsets, ids,
+                                  (int64_t)n_rel * n, d_agg, out, status, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// Shared between the whole-set entry points (infer.hip, infer_new.hip, rank.hip): the zeroing workgroups of a front kernel, the
+// Shared between the whole-set entry points (infer.hip, infer_new.hip, rank.hip, attr.hip, explain_new.hip): the zeroing workgroups of a front kernel, the
 // call's workspace layout, the per-chunk plan -> select -> stage loop and the forward-only dense launch.
 #pragma once
 #include "dense.h"
@@ -105,5 +105,25 @@ void infer_zero_regions(ZeroRegions &z, const ChunkDriver &d);
 ChunkDriver infer_driver(const pcg_graph_desc *g, const int32_t *ids, int32_t n, int32_t chunk_rows, int64_t list_capacity,
                          const double *thresholds, const float *s0, int64_t center_off, int n_slots, void *workspace,
                          const InferCarve &c, uint32_t *status, void *stream);
+
+
+// ---- query batches (pcg_infer_new, pcg_explain_new): rows of a query table q behind the base table g ---------------------------
+// infer_new.hip: the two descriptors describe tables of one shape (else PCG_E_ARG)
+int infer_new_descs(const pcg_graph_desc *g, const pcg_graph_desc *q);
+// infer_new.hip: the front launch of a query call whose driver (over q, center_off = g->n_nodes, two slots) is d: [the base
+// table's scores -> s0[0, N), only when score_base] || the query rows' scores -> s0[N, N + nq) || d's look-back words zeroed
+int launch_infer_new_front(const pcg_graph_desc *g, const pcg_graph_desc *q, const float *theta, int32_t emb, float *s0,
+                           int32_t score_base, const ChunkDriver &d);
+// gather.hip: lists of ids in [0, base_rows + query_rows): id < base_rows -> row id of X, else row id - base_rows of query_X
+int launch_gather_two(const float *X, int64_t base_rows, const float *query_X, int64_t query_rows, int32_t feat_dim,
+                      int32_t feat_stride, int32_t n_rows, const int32_t *cnt, const Workspace &w, float *agg, int32_t agg_stride,
+                      uint32_t *status, hipStream_t st);
+
+// rank.hip: the two rank launches over the lists (and the plan) in `w` - rows (r, b), b < B, of a chunk that is ids
+// [b_off, b_off + B) of the call's n_total, written at out_begin[r * n_total + b_off + b].  g: the graph whose rows were planned
+// and selected; s0 [n_scores] by list id; centre b's score center_s0 ? center_s0[b] : s0[nodes[b] + center_off]
+int launch_rank_lists(const pcg_graph_desc *g, const int32_t *nodes, int32_t B, int64_t n_total, int64_t b_off, const float *s0,
+                      const float *center_s0, const Workspace &w, const int64_t *out_begin, int32_t *out_ids, float *out_dist,
+                      uint32_t *status, int64_t center_off, int64_t n_scores, hipStream_t st);
 
 }  // namespace pcg

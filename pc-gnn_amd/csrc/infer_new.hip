@@ -18,11 +18,6 @@
 
 namespace pcg {
 
-// gather.hip
-int launch_gather_two(const float *X, int64_t base_rows, const float *query_X, int64_t query_rows, int32_t feat_dim,
-                      int32_t feat_stride, int32_t n_rows, const int32_t *cnt, const Workspace &w, float *agg, int32_t agg_stride,
-                      uint32_t *status, hipStream_t st);
-
 // workgroups [0, n_base) score the base table (n_base == 0: the caller's scores are current), [n_base, n_base + n_query) the
 // query rows into s0 + n_base_rows, the rest zero.  n_base = score_table_blocks(n_base_rows): pcg_score_table's grid.
 __global__ void __launch_bounds__(256) infer_new_front_kernel(const float *__restrict__ X, int64_t n_base_rows,
@@ -43,11 +38,27 @@ __global__ void __launch_bounds__(256) infer_new_front_kernel(const float *__res
     infer_zero_body(z, b - n_query);
 }
 
-// what both entry points check before anything else: the two descriptors describe tables of one shape
-static int infer_new_descs(const pcg_graph_desc *g, const pcg_graph_desc *q) {
+// what the query entry points check before anything else: the two descriptors describe tables of one shape (infer.h)
+int infer_new_descs(const pcg_graph_desc *g, const pcg_graph_desc *q) {
     if (!g || !q) return PCG_E_ARG;
     if (q->feat_dim != g->feat_dim || q->feat_stride != g->feat_stride || q->n_rel != g->n_rel) return PCG_E_ARG;
     if (g->n_nodes < 1 || q->n_nodes < 0 || q->n_pos != 0 || g->n_nodes + q->n_nodes >= (1ll << 31)) return PCG_E_ARG;
+    return PCG_OK;
+}
+
+// the front launch of a query call (infer.h): d is the call's driver over q
+int launch_infer_new_front(const pcg_graph_desc *g, const pcg_graph_desc *q, const float *theta, int32_t emb, float *s0,
+                           int32_t score_base, const ChunkDriver &d) {
+    const int F = g->feat_dim, E = emb, R = g->n_rel;
+    const int64_t N = g->n_nodes, nq = q->n_nodes;
+    ZeroRegions z = {};
+    infer_zero_regions(z, d);
+    const int n_zero = infer_zero_blocks(z);
+    const int n_base = score_base ? (int)score_table_blocks(N, g->feat_stride) : 0;
+    const int n_query = (int)score_table_blocks(nq, g->feat_stride);
+    hipLaunchKernelGGL(infer_new_front_kernel, dim3(n_base + n_query + n_zero), dim3(256), 0, d.st, g->X, N, q->X, nq, F,
+                       g->feat_stride, theta + off_clf(F, E, R), theta + off_bias(F, E, R), s0, n_base, n_query, z);
+    PCG_LAUNCH_CHECK();
     return PCG_OK;
 }
 
@@ -87,14 +98,8 @@ int pcg_infer_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float 
     const pcg::ChunkDriver d = pcg::infer_driver(q, ids, n, chunk_rows, list_capacity, thresholds, s0, N, 2, workspace, c, status, stream);
 
     // the front: [base scores] || query scores || the look-back words of both plan slots (as pcg_infer_set zeroes them)
-    pcg::ZeroRegions z = {};
-    pcg::infer_zero_regions(z, d);
-    const int n_zero = pcg::infer_zero_blocks(z);
-    const int n_base = score_base ? (int)pcg::score_table_blocks(N, g->feat_stride) : 0;
-    const int n_query = (int)pcg::score_table_blocks(nq, g->feat_stride);
-    hipLaunchKernelGGL(pcg::infer_new_front_kernel, dim3(n_base + n_query + n_zero), dim3(256), 0, d.st, g->X, N, q->X, nq, F,
-                       g->feat_stride, theta + pcg::off_clf(F, E, R), theta + pcg::off_bias(F, E, R), s0, n_base, n_query, z);
-    PCG_LAUNCH_CHECK();
+    rc = pcg::launch_infer_new_front(g, q, theta, emb, s0, score_base, d);
+    if (rc != PCG_OK) return rc;
 
     return d.run([&](int64_t off, int32_t B, const int32_t *cid, const pcg::Workspace &w) {
         const int rc = pcg::launch_gather_two(g->X, N, q->X, nq, F, g->feat_stride, R * B, d.cnt, w, agg, F, status, d.st);

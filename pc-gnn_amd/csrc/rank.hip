@@ -38,7 +38,9 @@ struct RankArgs {
     Workspace w;                // the plan (recs, queues, counters: read only) and the lists (len, list) of the batch
     const int32_t *nodes;       // [B] the batch's centres
     int32_t B, n_rel;
-    int64_t n_nodes, n_total, b_off;   // row (r, b) of the batch is row (r, b_off + b) of the caller's n_total ids
+    int64_t n_nodes, n_total, b_off;   // row (r, b) of the batch is row (r, b_off + b) of the caller's n_total ids; n_nodes: the
+                                       // entries of s0 (the table's rows; a query batch: base + query rows)
+    int64_t center_off;         // centre b's score is s0[nodes[b] + center_off] (a query batch's rows lie behind the base table's)
     const float *s0, *center_s0;
     const int64_t *out_begin;   // [n_rel * n_total + 1]
     int32_t *out_ids;
@@ -69,7 +71,7 @@ __device__ __forceinline__ RankRow rank_row(const RankArgs &a, int row) {
                     (int64_t)p.lbeg + n <= a.w.list_capacity;
     q.n = ok ? (n > 0 ? n : -1) : -1;
     if (!ok && a.status && (threadIdx.x & (PCG_WAVE - 1)) == 0) atomicOr(a.status, (uint32_t)PCG_ST_RANK_MISMATCH);
-    int64_t node = a.nodes[b];
+    int64_t node = a.nodes[b] + a.center_off;
     node = node < 0 ? 0 : (node >= a.n_nodes ? a.n_nodes - 1 : node);
     q.c = a.center_s0 ? a.center_s0[b] : a.s0[node];
     return q;
@@ -109,7 +111,7 @@ __device__ __forceinline__ void rank_four_short_rows(const RankArgs &a, int q_fi
     if (active && !ok && pos == 0 && a.status) atomicOr(a.status, (uint32_t)PCG_ST_RANK_MISMATCH);
     const bool have = active && ok && pos < n;
     const int32_t id = a.w.list[have ? p.lbeg + pos : 0];                  // unconditional load (clamped)
-    int64_t node = a.nodes[b];
+    int64_t node = a.nodes[b] + a.center_off;
     node = node < 0 ? 0 : (node >= a.n_nodes ? a.n_nodes - 1 : node);
     const float c = a.center_s0 ? a.center_s0[b] : a.s0[node];
     const float dist = fabsf(c - rank_score(a, id, have));
@@ -290,15 +292,17 @@ __global__ void __launch_bounds__(RANK_THREADS) rank_wg_rows(const RankArgs a) {
 }
 
 // the two launches over the lists (and the plan) in `w`: rows (r, b), b < B, of a batch that is ids [b_off, b_off + B) of n_total
-static int launch_rank_lists(const pcg_graph_desc *g, const int32_t *nodes, int32_t B, int64_t n_total, int64_t b_off,
-                             const float *s0, const float *center_s0, const Workspace &w, const int64_t *out_begin,
-                             int32_t *out_ids, float *out_dist, uint32_t *status, hipStream_t st) {
+// (declared in infer.h; g: the graph whose rows were planned and selected, s0 [n_scores], centre b's score s0[nodes[b] + center_off])
+int launch_rank_lists(const pcg_graph_desc *g, const int32_t *nodes, int32_t B, int64_t n_total, int64_t b_off, const float *s0,
+                      const float *center_s0, const Workspace &w, const int64_t *out_begin, int32_t *out_ids, float *out_dist,
+                      uint32_t *status, int64_t center_off, int64_t n_scores, hipStream_t st) {
     RankArgs a;
     a.w = w;
     a.nodes = nodes;
     a.B = B;
     a.n_rel = g->n_rel;
-    a.n_nodes = g->n_nodes;
+    a.n_nodes = n_scores;
+    a.center_off = center_off;
     a.n_total = n_total;
     a.b_off = b_off;
     a.s0 = s0;
@@ -572,7 +576,7 @@ int pcg_rank_lists(const pcg_graph_desc *g, const int32_t *nodes, int32_t B, con
     if (B == 0) return PCG_OK;
     pcg::Workspace w;
     pcg::carve1(g, B, list_capacity, static_cast<unsigned char *>(const_cast<void *>(workspace)), &w);
-    return pcg::launch_rank_lists(g, nodes, B, B, 0, s0, center_s0, w, out_begin, out_ids, out_dist, status,
+    return pcg::launch_rank_lists(g, nodes, B, B, 0, s0, center_s0, w, out_begin, out_ids, out_dist, status, 0, g->n_nodes,
                                   static_cast<hipStream_t>(stream));
 }
 
@@ -604,7 +608,7 @@ int pcg_chosen_set(const pcg_graph_desc *g, const float *theta, int32_t emb, con
     rc = pcg::launch_infer_front(g, theta + pcg::off_clf(F, E, R), theta + pcg::off_bias(F, E, R), s0, z, d.st);
     if (rc != PCG_OK) return rc;
     return d.run([&](int64_t off, int32_t B, const int32_t *cid, const pcg::Workspace &w) {
-        return pcg::launch_rank_lists(g, cid, B, n, off, s0, nullptr, w, out_begin, out_ids, out_dist, status, d.st);
+        return pcg::launch_rank_lists(g, cid, B, n, off, s0, nullptr, w, out_begin, out_ids, out_dist, status, 0, g->n_nodes, d.st);
     });
 }
 

@@ -288,8 +288,8 @@ int pcg_gather_rows(const pcg_graph_desc *g, const int32_t *ids, int32_t n_ids, 
     return PCG_OK;
 }
 
-const char *pcg_version(void) { return "pcgnn_hip gfx950 abi12"; }
-int pcg_abi_version(void) { return 12; }
+const char *pcg_version(void) { return "pcgnn_hip gfx950 abi13"; }
+int pcg_abi_version(void) { return 13; }
 
 /* sizeof, then offsetof of every member in declaration order, of the ABI's parameter structs: what a binding checks its mirror
  * of the header against.  Host only. */
@@ -310,9 +310,15 @@ int32_t pcg_abi_layout(int32_t which, int64_t *out, int32_t cap) {
                                     PCG_OFF(pcg_batch, plan), PCG_OFF(pcg_batch, B), PCG_OFF(pcg_batch, inv_count)};
     static const int64_t dense_out[] = {sizeof(pcg_dense_out), PCG_OFF(pcg_dense_out, logits), PCG_OFF(pcg_dense_out, center),
                                         PCG_OFF(pcg_dense_out, combined), PCG_OFF(pcg_dense_out, row_loss)};
+    static const int64_t explain_out[] = {sizeof(pcg_explain_out), PCG_OFF(pcg_explain_out, logits), PCG_OFF(pcg_explain_out, d_self),
+                                          PCG_OFF(pcg_explain_out, d_agg), PCG_OFF(pcg_explain_out, self_contrib),
+                                          PCG_OFF(pcg_explain_out, rel_contrib), PCG_OFF(pcg_explain_out, out_begin),
+                                          PCG_OFF(pcg_explain_out, out_ids), PCG_OFF(pcg_explain_out, out_dist),
+                                          PCG_OFF(pcg_explain_out, neigh_contrib)};
 #undef PCG_OFF
 #define PCG_ROW(a) {a, (int32_t)(sizeof(a) / sizeof(a[0]))}
-    static const struct { const int64_t *v; int32_t n; } all[] = {PCG_ROW(hyper), PCG_ROW(state), PCG_ROW(sel), PCG_ROW(batch), PCG_ROW(dense_out)};
+    static const struct { const int64_t *v; int32_t n; } all[] = {PCG_ROW(hyper), PCG_ROW(state), PCG_ROW(sel), PCG_ROW(batch), PCG_ROW(dense_out),
+                                                                  PCG_ROW(explain_out)};
 #undef PCG_ROW
     if (which < 0 || which >= (int32_t)(sizeof(all) / sizeof(all[0])) || !out || cap < all[which].n) return PCG_E_ARG;
     for (int32_t i = 0; i < all[which].n; ++i) out[i] = all[which].v[i];

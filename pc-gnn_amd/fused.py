@@ -1195,7 +1195,8 @@ class FusedPCGNN:
         the minority part beside it (``minor_row``, ``has_minority``): per row of a positive centre the m = min(int(k * rho),
         n_pos) training positives nearest to its score, ranked, with their distances (pcg_rank_minority, one more pass over all
         n ids after the chunks; the train-positive keys of the call's own scores are sorted into a buffer of the call's own -
-        the training engine's keys are neither read nor written)."""
+        the training engine's keys are neither read nor written).
+        Nodes that are not in the graph (``infer_new``'s query batches): ``chosen_new`` (test mode only)."""
         g, lib, inf = self.g, self.lib, self._inf
         if train_flag and labels is None:
             raise ValueError("chosen: train_flag=True needs labels (one per id)")
@@ -1254,8 +1255,8 @@ class FusedPCGNN:
         neighbours=True calls ``chosen(ids)`` and adds its lists and ``neigh_contrib`` beside them.  The training engine is left
         alone exactly as by ``infer`` (a deferred update is applied first).  Synchronises once (the status word; once more per
         ``chosen`` call).  target: two finite floats, else ValueError.
-        Out of scope: ``DistributedPCGNN``, ``infer_new`` queries, the train-mode selection and its minority picks, the
-        GraphSAGE / GCN baselines."""
+        Nodes that are not in the graph (``infer_new``'s query batches): ``attribute_new``.
+        Out of scope: ``DistributedPCGNN``, the train-mode selection and its minority picks, the GraphSAGE / GCN baselines."""
         g, lib, inf = self.g, self.lib, self._inf
         try:
             w0, w1 = (float(t) for t in target)
@@ -1314,15 +1315,8 @@ class FusedPCGNN:
         pass.  The training engine is left alone exactly as by ``infer`` (a deferred update is applied first).  Synchronises
         once (the status word).  (_list_capacity: not part of the interface - the tests' way to make a selection list
         overflow; the call sizes its list exactly.)"""
-        g, lib = self.g, self.lib
-        self.flush()
-        if query.n_base != g.n_nodes or query.feat_dim != g.feat_dim or query.R != g.R:
-            raise ValueError(f"infer_new: the query batch was built for a base graph of {query.n_base} nodes / {query.feat_dim} "
-                             f"features / {query.R} relations, this engine's has {g.n_nodes} / {g.feat_dim} / {g.R}")
-        if query.X is None or query.device != self.dev or query.feat_stride != g.feat_stride:
-            query.to(self.dev, g)
-        nq, inf = query.nq, self._inf
-        ids_host, ids_dev, n = whole_set_ids(ids, nq, self.dev, "infer_new: ids", " (query-local rows)")
+        g, lib, inf = self.g, self.lib, self._inf
+        ids_host, ids_dev, n = self._new_query(query, ids, "infer_new")
         logits = torch.empty(n, 2, dtype=torch.float32, device=self.dev)
         center = torch.empty(n, 2, dtype=torch.float32, device=self.dev) if want_center else None
         if n == 0:
@@ -1331,11 +1325,7 @@ class FusedPCGNN:
         chunk, cap, ws = whole_set_chunk(inf, "new_ws", self.dev, ws_bytes, "pcg_infer_new_workspace_bytes",
                                          infer_row_caps(query.deg_host, self.thresholds, ids_host), chunk,
                                          self.infer_workspace_bytes, _list_capacity)
-        # a grown buffer holds no scores: capacity in powers of two, so a stream of batches grows it a few times at most
-        if whole_set_buffers(inf, self.dev, "new_s0", g.n_nodes + nq, g.n_nodes + (1 << max(nq - 1, 255).bit_length())):
-            inf["new_s0_version"] = None
-        score_base = not (reuse_scores and inf["new_s0_version"] == self._param_version)
-        self._new_scored_base = score_base          # (whether the last infer_new ran the table pass: tests, scripts)
+        score_base = self._new_scores(query, reuse_scores)
         _lib.check(lib.pcg_infer_new(g.desc_ref(), query.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk, _p(inf["new_s0"]),
                                      1 if score_base else 0, self._thr, _p(ws), cap, _p(logits), _p(center),
                                      _p(inf["status"]), self._stream()), "pcg_infer_new")
@@ -1343,6 +1333,107 @@ class FusedPCGNN:
         inf["new_s0_version"] = self._param_version
         self._infer_status()
         return (logits, center) if want_center else logits
+
+    def _new_query(self, query: QueryBatch, ids, what: str):
+        """What every query call does first: a deferred update applied, the batch checked against this engine's graph and
+        uploaded for it if it is not; -> whole_set_ids of the query-local ``ids`` (None = all nq)."""
+        g = self.g
+        self.flush()
+        if query.n_base != g.n_nodes or query.feat_dim != g.feat_dim or query.R != g.R:
+            raise ValueError(f"{what}: the query batch was built for a base graph of {query.n_base} nodes / {query.feat_dim} "
+                             f"features / {query.R} relations, this engine's has {g.n_nodes} / {g.feat_dim} / {g.R}")
+        if query.X is None or query.device != self.dev or query.feat_stride != g.feat_stride:
+            query.to(self.dev, g)
+        return whole_set_ids(ids, query.nq, self.dev, f"{what}: ids", " (query-local rows)")
+
+    def _new_scores(self, query: QueryBatch, reuse_scores: bool) -> bool:
+        """The score buffer of the query calls (inf["new_s0"], N + capacity floats) for this batch; -> whether the call has to
+        run the base table's score pass (the buffer is new, the parameters were written since it was filled, or the caller
+        says so)."""
+        g, inf, nq = self.g, self._inf, query.nq
+        # a grown buffer holds no scores: capacity in powers of two, so a stream of batches grows it a few times at most
+        if whole_set_buffers(inf, self.dev, "new_s0", g.n_nodes + nq, g.n_nodes + (1 << max(nq - 1, 255).bit_length())):
+            inf["new_s0_version"] = None
+        score_base = not (reuse_scores and inf["new_s0_version"] == self._param_version)
+        self._new_scored_base = score_base          # (whether the last query call ran the table pass: tests, scripts)
+        return score_base
+
+    def _explain_new(self, what: str, query: QueryBatch, ids, chunk, target, want_attr: bool, want_chosen: bool, reuse_scores: bool,
+                     list_capacity: Optional[int]):
+        """chosen_new / attribute_new: ONE pcg_explain_new call - one selection per chunk feeds the ranking and the attribution.
+        -> (Attribution or None, ChosenLists or None)."""
+        g, lib, inf = self.g, self.lib, self._inf
+        try:
+            w0, w1 = (float(t) for t in target)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: target must be two finite floats, got {target!r}") from None
+        if not (np.isfinite(w0) and np.isfinite(w1)):
+            raise ValueError(f"{what}: target must be two finite floats, got {target!r}")
+        ids_host, ids_dev, n = self._new_query(query, ids, what)
+        if ids_host is None:
+            ids_host = np.arange(n, dtype=np.int64)
+        F, R, f32 = g.feat_dim, g.R, dict(dtype=torch.float32, device=self.dev)
+        out = _lib.ExplainOut()
+        attr = chosen = None
+        caps2 = ops.sel_capacity(query, ids_host, None, self.thresholds, 0.0, False)     # [R, n]: exact in test mode
+        if want_chosen:
+            off = ops.rank_offsets(caps2)
+            total = int(off[-1])
+            out_begin = torch.from_numpy(off).to(self.dev)
+            # (at least one entry behind every pointer: an empty tensor has none, and a NULL member means "group not requested")
+            ids_buf, dist_buf = torch.empty(max(total, 1), dtype=torch.int32, device=self.dev), torch.empty(max(total, 1), **f32)
+            chosen = ChosenLists(out_begin, ids_buf[:total], dist_buf[:total], R, n, host_offsets=off)
+            out.out_begin, out.out_ids, out.out_dist = _p(out_begin), _p(ids_buf), _p(dist_buf)
+        if want_attr:
+            attr = Attribution(ids_dev, query.X, F, torch.empty(n, 2, **f32), torch.empty(n, F, **f32), torch.empty(R, n, F, **f32),
+                               torch.empty(n, **f32), torch.empty(R, n, **f32), (w0, w1))
+            out.logits, out.d_self, out.d_agg = _p(attr.logits), _p(attr.d_self), _p(attr.d_agg)
+            out.self_contrib, out.rel_contrib = _p(attr.self_contrib), _p(attr.rel_contrib)
+            if want_chosen:
+                nc_buf = torch.empty(max(total, 1), **f32)
+                attr.chosen, attr.neigh_contrib = chosen, nc_buf[:total]
+                out.neigh_contrib = _p(nc_buf)
+        if n == 0:
+            return attr, chosen
+        ws_bytes = lambda c, cap: int(lib.pcg_explain_new_workspace_bytes(g.desc_ref(), query.desc_ref(), self.E, c, cap))
+        chunk, cap, ws = whole_set_chunk(inf, "new_ws", self.dev, ws_bytes, "pcg_explain_new_workspace_bytes", caps2.sum(0), chunk,
+                                         self.infer_workspace_bytes, list_capacity)           # (the sum == infer_row_caps)
+        score_base = self._new_scores(query, reuse_scores)
+        _lib.check(lib.pcg_explain_new(g.desc_ref(), query.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk,
+                                       _p(inf["new_s0"]), 1 if score_base else 0, self._thr, _p(ws), cap, w0, w1, C.byref(out),
+                                       _p(inf["status"]), self._stream()), "pcg_explain_new")
+        # (the table pass is enqueued before anything that could overflow: the scores are valid whatever the status says)
+        inf["new_s0_version"] = self._param_version
+        self._infer_status()
+        return attr, chosen
+
+    def chosen_new(self, query: QueryBatch, ids=None, chunk: Optional[int] = None, reuse_scores: bool = True,
+                   _list_capacity: Optional[int] = None) -> ChosenLists:
+        """``chosen`` for nodes that are NOT in the graph: for every requested row of ``query`` (graph.QueryBatch, as
+        ``infer_new``'s) and every relation, the neighbours the test-mode selection kept - the selection ``infer_new`` scores
+        the row with - in the reference's order, with their distances (pcg_explain_new, its chosen group alone: per chunk plan
+        -> select -> rank; no gather, no dense launch).  ids: query-local rows in [0, nq) (None = all; any order, duplicates
+        allowed); the ids IN the returned lists are global, in [0, N + nq): base nodes, other nodes of the batch (N + j), the
+        node itself.  The offsets are host arithmetic on the query's degrees (a row keeps deg > k + 1 ? k : deg entries).
+        Bit for bit what ``chosen(N + ids)`` returns on a graph built with the query rows appended.  chunk, reuse_scores and
+        the cached base scores: ``infer_new``'s - a call after ``infer_new`` (or another query call) scores the nq query rows
+        only.  The base graph is not modified; the training engine is left alone as by ``infer``.  Synchronises once (the
+        status word).  Out of scope: train-mode / minority lists (a query's logits are test-mode by definition)."""
+        return self._explain_new("chosen_new", query, ids, chunk, (0.0, 1.0), False, True, reuse_scores, _list_capacity)[1]
+
+    def attribute_new(self, query: QueryBatch, ids=None, chunk: Optional[int] = None, target=(0.0, 1.0), neighbours: bool = False,
+                      reuse_scores: bool = True, _list_capacity: Optional[int] = None) -> Attribution:
+        """``attribute`` for nodes that are NOT in the graph: the exact split of ``target[0] * logit0 + target[1] * logit1`` of
+        every requested row of ``query`` into the shares of the row's own features, of every relation and - neighbours=True -
+        of every chosen neighbour (pcg_explain_new).  The result's logits are ``infer_new(query, ids)`` bit for bit; it is
+        built over the query's feature table and the query-local ids, so ``feature_contrib`` and ``completeness_residual``
+        work as for resident nodes.  neighbours=True adds ``chosen`` (what ``chosen_new`` returns: global ids) and
+        ``neigh_contrib`` from the SAME call and the same single selection per chunk - no second plan / select, no second
+        score pass.  Every value is bit for bit what ``attribute(N + ids, neighbours=True)`` returns on a graph built with
+        the query rows appended.  ids, chunk, reuse_scores and the cached base scores: ``infer_new``'s; target: two finite
+        floats, else ValueError.  The base graph is not modified; the training engine is left alone as by ``infer``.
+        Synchronises once (the status word).  Out of scope: ``DistributedPCGNN``, the train-mode selection, GraphSAGE / GCN."""
+        return self._explain_new("attribute_new", query, ids, chunk, target, True, bool(neighbours), reuse_scores, _list_capacity)[0]
 
     def evaluate(self, ids, labels, thresholds=None, chunk: Optional[int] = None) -> dict:
         """The evaluation metrics of a node set without its probabilities leaving the device: ``infer`` -> sigmoid (torch, so

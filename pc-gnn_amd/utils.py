@@ -169,6 +169,21 @@ def explain_nodes(engine, ids, labels=None, attribute: bool = False):
         return ch, prob, engine.attribute(ids, neighbours=True)
 
 
+def explain_new(engine, query, ids=None, attribute: bool = False):
+    """``explain_nodes`` for nodes that are NOT in the graph - the rows ``ids`` (query-local; None = all) of a
+    ``graph.QueryBatch``: (``engine.chosen_new(query, ids)`` - the neighbours the model listened to, ranked, with their
+    distances; global ids -, the test-mode class probabilities [n, 2] - sigmoid of ``infer_new``'s logits), on the device.
+    attribute=True: a third value, the ``Attribution`` - and then everything comes from ONE
+    ``engine.attribute_new(query, ids, neighbours=True)`` call (its ``chosen``, sigmoid of its ``logits``): one selection per
+    chunk, one read of the status word."""
+    with torch.no_grad():
+        if attribute:
+            at = engine.attribute_new(query, ids=ids, neighbours=True)
+            return at.chosen, torch.sigmoid(at.logits).float(), at
+        ch = engine.chosen_new(query, ids=ids)
+        return ch, torch.sigmoid(engine.infer_new(query, ids=ids)).float()
+
+
 def predict_proba(test_nodes, model, batch_size: int, labels=None) -> np.ndarray:
     """Test-mode class probabilities [n, 2] of ``test_nodes`` (sigmoid of the gnn logits, utils.py:305), on the host.
     A FusedPCGNN runs its whole-set pass (``infer``: one call, one score pass) - test-mode results do not depend on how the
