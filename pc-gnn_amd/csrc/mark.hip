@@ -189,7 +189,7 @@ __global__ void __launch_bounds__(256) mark_short_kernel(const MarkPlanArgs a) {
             const int32_t *nbr = nullptr;
             for (int rr = 0; rr < PCG_MAX_REL; ++rr)
                 if (rr == r) nbr = a.indices[rr];
-            nbr += p.start;
+            nbr += p.d > 0 ? p.start : 0;                                 // (a row without neighbours may start AT the array's end)
             const int d = qi < qn ? p.d : 0;
             int32_t idv[4];
 #pragma unroll
