@@ -801,6 +801,24 @@ int64_t pcg_wgrad_act_rows(int32_t feat_dim, int32_t emb, int32_t n_rel);
 int64_t pcg_wgrad_scratch_bytes(int32_t feat_dim, int32_t emb, int32_t n_rel, int32_t B);
 int pcg_wgrad(const pcg_train_state *st, int32_t B, int32_t feat_dim, int32_t n_rel, float *grad_out, int32_t apply,
               int32_t with_clf, uint32_t *flag_set, void *stream);
+/* Custom losses on the fused path: the dense launch of pcg_train_dense(adam_clf = 4) with its backward started from the CALLER's
+ * loss gradients instead of the built-in CE(gnn) + lambda_1 * CE(label) (additive since ABI 13; no new struct).  The launch runs
+ * the forward for the batch (bit for bit pcg_train_dense's logits), takes row b's seeds d_logits[2b], d_logits[2b + 1] = d loss /
+ * d gnn logits and d_center[2b], d_center[2b + 1] = d loss / d label-aware logits (device float [B, 2] each) AS GIVEN - no
+ * 1 / count, no lambda_1, no label read, non-finite values propagate - and leaves the transposed activations / activation
+ * gradients in st->acts; pcg_wgrad(with_clf = 1) over the same acts then gives every parameter's gradient (apply = 0) or steps
+ * every parameter (apply = 1).  Nothing else of the backward depends on the loss, and the selection is not differentiated.
+ *   st:    theta, emb, acts, act_ld (what pcg_train_dense(adam_clf = 4) reads); no slabs, no sync words, no Adam state, and
+ *          step_counter is not touched
+ *   batch: ids, B, cnt, plan; labels and inv_count are ignored
+ *   agg, agg_stride, sel: as given to pcg_choose_gather_planned for this batch (sel->workspace != NULL: rows the gather left
+ *          as partial sums are added up here, as in pcg_train_dense)
+ *   out:   may be NULL; logits / center / combined that are not NULL are written by the launch's own forward; row_loss is ignored
+ * PCG_E_ARG before any launch: a NULL g / st / batch / sel / d_logits / d_center, NULL theta or acts, B < 0, NULL ids with
+ * B >= 1, and whatever pcg_train_dense(adam_clf = 4) rejects; PCG_E_UNSUPPORTED exactly where that call returns it.  B == 0:
+ * PCG_OK, nothing is enqueued.  One 1024-thread workgroup per 16 batch rows, the shape dispatch of the training launch. */
+int pcg_dense_vjp(const pcg_graph_desc *g, const pcg_train_state *st, const pcg_batch *batch, const float *agg, int32_t agg_stride,
+                  const pcg_select_ws *sel, const float *d_logits, const float *d_center, const pcg_dense_out *out, void *stream);
 
 /* ---- multi-GPU halo exchange helpers (no counterpart in the reference) ----------
  * A rank of a partitioned run holds the table [ owned rows | train-pos rows | halo ]; CSR rows and selection lists hold

@@ -158,6 +158,7 @@ PROTOTYPES = {
     "pcg_wgrad_act_rows": (_I64, [_I32, _I32, _I32]),
     "pcg_wgrad_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "pcg_wgrad": (C.c_int, [_ST, _I32, _I32, _I32, _P, _I32, _I32, _P, _P]),
+    "pcg_dense_vjp": (C.c_int, [_G, _ST, _B, _P, _I32, _SEL, _P, _P, _OUT, _P]),
     "pcg_step_scores_dist": (C.c_int, [_G, _ST, _P, _P, _I64, _I64, _P, _P, _P, _I64, _P]),
     "pcg_gather_lists_dist": (C.c_int, [_P, _I32, _I32, _I64, _I32, _P, _G, _I32, _P, _P, _I64, _P, _I32, _P, _I32, _I32, _I32, _P, _P,
                                         _I32, _P, _I64, _P, _I32, _I32, _P, _P, _P, _I64, _I32, _P, _P]),

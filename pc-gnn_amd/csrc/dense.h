@@ -196,8 +196,13 @@ __device__ __forceinline__ float row16_sum(float p) {
 // partial tiles of `combined` go where the backward's dcomb / dh_r arrays are (the W_intra copy stays live for the next tile),
 // and STAGE_W = false skips the weights' LDS copy (the workgroup's first tile made it).  The training launches set neither:
 // their code is what it was before these flags existed.
-template <bool WLDS, int F_, int E_, int R_, bool INFER = false, bool STAGE_W = true>
-__device__ __forceinline__ void dense_tile_body(const DenseArgs &a, int bid, float *sm) {
+// EXT: the backward starts from the CALLER's loss gradients instead of the built-in loss's (dense_vjp_kernel, vjp.hip; acts mode
+// only): row b's seeds are d_logits[2b], d_logits[2b + 1] (d loss / d gnn logits) and d_center[2b], d_center[2b + 1] (d loss / d
+// label-aware logits), used as given - no 1 / count, no lambda_1, no label read, no row loss; rows beyond the batch get zeros.
+// Everything behind the loss phase reads only s_dlog / s_dcl and the forward's LDS state, so nothing else differs.
+template <bool WLDS, int F_, int E_, int R_, bool INFER = false, bool STAGE_W = true, bool EXT = false>
+__device__ __forceinline__ void dense_tile_body(const DenseArgs &a, int bid, float *sm, const float *__restrict__ d_logits = nullptr,
+                                                const float *__restrict__ d_center = nullptr) {
     // bid: this workgroup's index among the tiles' workgroups (a.n_tile_blocks of them); sm: the launch's dynamic LDS
     const int F = F_ > 0 ? F_ : a.feat_dim, E = E_ > 0 ? E_ : a.emb, R = R_ > 0 ? R_ : a.n_rel;
     const int K1 = 2 * F, K1p = (K1 + KPAD - 1) / KPAD * KPAD, K2 = F + R * E, K2p = (K2 + KPAD - 1) / KPAD * KPAD;
@@ -233,7 +238,17 @@ __device__ __forceinline__ void dense_tile_body(const DenseArgs &a, int bid, flo
     }
     // wave t's row of the loss phase: its label is requested now, not when the logits are ready
     const int my_b = row0 + wave;
-    const int my_label = (a.labels && my_b < a.B) ? a.labels[my_b] : 0;
+    const int my_label = (!EXT && a.labels && my_b < a.B) ? a.labels[my_b] : 0;
+    // (EXT: its four seeds instead - unconditional loads at a clamped row, the values of rows beyond the batch discarded)
+    float seed_g0 = 0.f, seed_g1 = 0.f, seed_c0 = 0.f, seed_c1 = 0.f;
+    if constexpr (EXT) {
+        const int sb = my_b < a.B ? my_b : a.B - 1;
+        seed_g0 = d_logits[2 * sb];
+        seed_g1 = d_logits[2 * sb + 1];
+        seed_c0 = d_center[2 * sb];
+        seed_c1 = d_center[2 * sb + 1];
+        if (my_b >= a.B) seed_g0 = seed_g1 = seed_c0 = seed_c1 = 0.f;
+    }
     DENSE_STAMP(0);
     if (a.stamps && threadIdx.x == 0 && sp == 0) a.stamps[(size_t)tile_id * 16 + 12] = clock64();     // shader cycles (diagnostic)
 
@@ -443,13 +458,25 @@ __device__ __forceinline__ void dense_tile_body(const DenseArgs &a, int bid, flo
         if (lane == 0) {
             float dg0 = 0.f, dg1 = 0.f, dc0 = 0.f, dc1 = 0.f;
             if (b < a.B) {
-                if (sp == 0) {
+                if constexpr (EXT) {
+                    if (a.logits) {
+                        a.logits[2 * b] = g0;
+                        a.logits[2 * b + 1] = g1;
+                    }
+                    if (a.center) {
+                        a.center[2 * b] = c0;
+                        a.center[2 * b + 1] = c1;
+                    }
+                } else if (sp == 0) {
                     a.logits[2 * b] = g0;
                     a.logits[2 * b + 1] = g1;
                     a.center[2 * b] = c0;
                     a.center[2 * b + 1] = c1;
                 }
-                if (a.labels) {
+                if constexpr (EXT) {
+                    dg0 = seed_g0; dg1 = seed_g1;
+                    dc0 = seed_c0; dc1 = seed_c1;
+                } else if (a.labels) {
                     const int y = my_label;
                     float lg, lc;
                     xent2(g0, g1, y, lg, dg0, dg1);

@@ -26,6 +26,10 @@ The model's parameters are re-pointed into ONE flat f32 buffer (order: see
 ``pcg_dense_step`` in include/pcgnn.h); the ``nn.Parameter`` objects, their names
 and ``state_dict()`` stay exactly the reference's.
 
+Another objective or optimizer than the reference's stays on this path too: ``forward`` returns the two logit tensors under
+autograd (the backward is ``pcg_dense_vjp`` - the dense kernel's backward from the caller's loss gradients - and ``pcg_wgrad``),
+``optimizer_step`` lets any ``torch.optim`` optimizer write the flat buffer, ``train_step_custom`` keeps the engine's Adam.
+
 Reference loop replaced: src/model_handler.py:147-153 (and :305 of utils.py for
 ``predict``).
 """
@@ -145,6 +149,24 @@ def whole_set_buffers(inf: dict, dev, s0_key: str, need: int, alloc: Optional[in
     return True
 
 
+class _SeededDense(torch.autograd.Function):
+    """FusedPCGNN.forward under autograd: the engine's train-mode forward as a function of the model's parameters.  The backward
+    hands the loss gradients of the two logit tensors to pcg_dense_vjp + pcg_wgrad (FusedPCGNN._enqueue_vjp); the ids, labels and
+    the selection get no gradient (the selection is index-only: the reference does not differentiate it either)."""
+
+    @staticmethod
+    def forward(ctx, fz, ids, labels, train_flag, *params):
+        gnn, center = fz._forward_live(ids, labels, train_flag)
+        ctx.fz, ctx.serial = fz, fz._live["serial"]
+        return gnn, center
+
+    @staticmethod
+    def backward(ctx, d_gnn, d_center):
+        fz = ctx.fz
+        flat = fz._enqueue_vjp(fz._live_of(ctx.serial), d_gnn, d_center)
+        return (None, None, None, None) + tuple(fz._by_name(flat).values())
+
+
 class FusedPCGNN:
     def __init__(self, model: PCALayer, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8,
                  max_batch: int = 1024, global_batch_scale: int = 1, list_capacity: Optional[int] = None,
@@ -178,6 +200,9 @@ class FusedPCGNN:
             view.copy_(p.data.to(self.dev))
             p.data = view                      # the Parameter now lives inside the flat buffer
             self.views[name] = view
+        self._params = [named[name] for name, _, _ in spec]     # the Parameters behind self.views, in its order (forward()'s inputs)
+        self._live = None          # forward(): the one forward whose plan, lists, aggregates and counts are still in the workspace
+        self._live_serial = 0
         self.w_clf = self.views["inter1.label_clf.weight"]
         self.b_clf = self.views["inter1.label_clf.bias"]
         self.m = torch.zeros_like(self.theta)
@@ -255,6 +280,7 @@ class FusedPCGNN:
         if torch.cuda.is_current_stream_capturing():
             raise _lib.PcgnnLibraryError("batch larger than max_batch inside a graph capture: allocate before capturing")
         self._drop_prepared()                        # (an epoch prepared ahead goes with its buffers)
+        self._live = None
         # every captured graph holds raw pointers into the buffers replaced below
         self._graphs.clear()
         self._ep_graphs.clear()
@@ -353,6 +379,7 @@ class FusedPCGNN:
     def _enqueue_plan_one(self, ids, labels, B, train_flag) -> int:
         """plan of ONE batch into this batch size's own slot (+ its touched-row map); returns the slot's address"""
         slot = self._plan_slot(B)
+        self._live = None                            # (the slot of a forward() still waiting for its backward is overwritten)
         self._enqueue_plan(ids, labels, B, B, slot, slot.numel(), train_flag)
         if self.touched_on and train_flag:
             if self._touch_one is None:
@@ -389,12 +416,14 @@ class FusedPCGNN:
         """a call that enqueues a write of theta (now, or deferred to the next flush): infer_new's cached base scores are stale"""
         self._param_version += 1
         self._theta_dirty = True
+        self._live = None
 
     def params_changed(self):
         """Tell the engine that the parameters were written from outside (a state dict loaded into the flat buffer's views):
         the stepped copy of the label classifier and the score table are taken from theta again."""
         self.flush()
         self._param_version += 1
+        self._live = None
         self.clf_next.copy_(self.theta[self.n_rest:])
         self._fresh = False
 
@@ -419,6 +448,7 @@ class FusedPCGNN:
         """select (+ the label classifier's step for this batch) and gather (+ the deferred update of the other parameters,
         + the next step's scores if score_next) of a training step: pcg_choose_gather_train."""
         g = self.g
+        self._live = None                            # (lists, aggregates and counts are overwritten)
         agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
         cnt = self.cnt.view(-1)[:g.R * B].view(g.R, B)
         timed = self._prof is not None and not torch.cuda.is_current_stream_capturing()
@@ -443,6 +473,7 @@ class FusedPCGNN:
         select kernel sorts them itself unless there are too many: then they are sorted already) and the launch clears the
         "deferred update pending" word."""
         g = self.g
+        self._live = None                            # (lists, aggregates and counts are overwritten)
         agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
         cnt = self.cnt.view(-1)[:g.R * B].view(g.R, B)
         timed = self._prof is not None and not torch.cuda.is_current_stream_capturing()
@@ -489,6 +520,7 @@ class FusedPCGNN:
         (clf_out: the classifier slot it fills), 2 = the gather launch.
         bufs: the (s0, keys) pair the launch reads (select) or writes (the gather launch's score pass), default the engine's own"""
         g = self.g
+        self._live = None                            # (lists, aggregates and counts are overwritten)
         agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
         s0, keys = (self.s0, self.keys) if bufs is None else bufs
         _lib.check(self.lib.pcg_choose_train_part(
@@ -1154,6 +1186,120 @@ class FusedPCGNN:
         self._enqueue_tail(ids, None, B, agg, plan, False, combined=comb)
         res = (self.logits[:B].clone(), self.center[:B].clone())
         return res + (comb,) if want_combined else res
+
+    # -- custom losses and optimizers on the fused path ----------------------------------------------
+    # The whole backward of the dense kernel is a function of two small arrays - d loss / d gnn logits and d loss / d label-aware
+    # logits - and of the forward's state; the selection is not differentiated.  So: a forward that returns the two logit tensors
+    # under autograd, and a backward that hands whatever gradients autograd brings for them to pcg_dense_vjp + pcg_wgrad.
+    # Out of scope (they keep the built-in loss and Adam): DistributedPCGNN, the GraphSAGE / GCN models, the graph, pipelined and
+    # whole-epoch engines (train_step_graph, epoch_*), and hipGraph capture of the custom step.
+    def _forward_live(self, ids, labels, train_flag):
+        """predict, remembered as THE forward whose plan, lists, aggregates and counts are in the workspace"""
+        if train_flag and labels is None:
+            raise ValueError("forward(train_flag=True) needs the batch's labels (the training-mode selection reads them)")
+        res = self.predict(ids, labels, train_flag)
+        B = ids.numel()
+        self._live_serial += 1
+        self._live = dict(serial=self._live_serial, ids=ids, B=B, plan=self._plan_slot(B).data_ptr())
+        return res
+
+    def _live_of(self, serial: int) -> dict:
+        live = self._live
+        if live is None or live["serial"] != serial:
+            raise RuntimeError("stale forward: the engine's workspace or parameters have been overwritten since this forward() "
+                               "(another forward / predict / gradients / train_step* / epoch_* call, or params_changed / "
+                               "optimizer_step) - one forward is outstanding per engine; run forward() again")
+        return live
+
+    def _by_name(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        return {k: flat[v.storage_offset():v.storage_offset() + v.numel()].view(v.shape) for k, v in self.views.items()}
+
+    def _enqueue_vjp(self, live: dict, d_logits, d_center, apply: bool = False, out=None) -> Optional[torch.Tensor]:
+        """pcg_dense_vjp over what the live forward left in the workspace, then the weight-gradient GEMMs: the flat gradient in a
+        buffer of its own (apply=False), or the engine's Adam on every parameter (apply=True; the caller has moved the step
+        counter on).  out: (logits, center) tensors the launch's own forward writes.  Nothing synchronises."""
+        g, B = self.g, live["B"]
+        if B == 0:
+            return None if apply else torch.zeros(self.n_params, dtype=torch.float32, device=self.dev)
+        seeds = []
+        for what, d in (("d_logits", d_logits), ("d_center", d_center)):
+            if d is None:
+                d = torch.zeros(B, 2, dtype=torch.float32, device=self.dev)
+            if tuple(d.shape) != (B, 2) or d.device != self.dev:
+                raise ValueError(f"{what}: a [{B}, 2] tensor on {self.dev} expected, got {tuple(d.shape)} on {d.device}")
+            seeds.append(d.detach().to(torch.float32).contiguous())
+        agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
+        cnt = self.cnt.view(-1)[:g.R * B]
+        dense_out = None if out is None else _lib.DenseOut(_p(out[0]), _p(out[1]), None, None)
+        _lib.check(self.lib.pcg_dense_vjp(
+            g.desc_ref(), self._st, self._batch(live["ids"], None, B, live["plan"], cnt), _p(agg), agg.stride(1), self._sel,
+            _p(seeds[0]), _p(seeds[1]), dense_out, self._stream()), "pcg_dense_vjp")
+        if apply:
+            _lib.check(self.lib.pcg_wgrad(self._st, B, self.F, self.R, None, 1, 1, None, self._stream()), "pcg_wgrad")
+            return None
+        grad = torch.empty(self.n_params, dtype=torch.float32, device=self.dev)
+        _lib.check(self.lib.pcg_wgrad(self._st_grad, B, self.F, self.R, _p(grad), 0, 1, None, self._stream()), "pcg_wgrad")
+        return grad
+
+    def forward(self, ids: torch.Tensor, labels: Optional[torch.Tensor] = None, train_flag: bool = True):
+        """The forward of a training step as a differentiable function of the model's parameters -> (gnn logits [B, 2],
+        label-aware logits [B, 2]); the values are bit for bit ``predict(ids, labels, train_flag)``.  Under ``torch.no_grad()`` it IS
+        predict.  Otherwise the two tensors come from an autograd function whose inputs are the model's parameters, so any loss of
+        them - ``loss.backward()`` - leaves the gradients in ``p.grad`` of ``model.parameters()``, accumulated as autograd
+        accumulates.  The backward runs on the device: pcg_dense_vjp (the dense kernel's backward, started from the loss
+        gradients of the two logit tensors) over the plan, lists, aggregates and counts this forward left in the workspace, then
+        the weight-gradient GEMMs of pcg_wgrad.  Nothing synchronises.  The selection is not differentiated.
+        ONE forward is outstanding per engine: any call that overwrites the workspace or enqueues a write of theta (another
+        forward / predict / gradients / train_step* / epoch_*, params_changed, optimizer_step) makes it stale, and its backward
+        then raises a RuntimeError instead of computing from overwritten buffers.  A second backward of a live forward
+        (retain_graph=True) gives the same gradients again.  ``ids`` is kept by reference until then: do not write it.
+        train_flag=True needs labels, as predict does.  Not captured into hipGraphs."""
+        if not torch.is_grad_enabled():
+            return self.predict(ids, labels, train_flag)
+        return _SeededDense.apply(self, ids, labels, train_flag, *self._params)
+
+    def vjp(self, d_logits: torch.Tensor, d_center: torch.Tensor, want_logits: bool = False):
+        """The low-level form of forward()'s backward: the per-parameter gradients (the format ``gradients()`` returns) of the live
+        forward for the given d loss / d gnn logits and d loss / d label-aware logits ([B, 2] each, used as given).
+        want_logits: also the (gnn, label-aware) logits the launch's own forward wrote -> (grads, logits, center)."""
+        if self._live is None:
+            self._live_of(-1)
+        live = self._live
+        out = None
+        if want_logits:
+            out = tuple(torch.empty(live["B"], 2, dtype=torch.float32, device=self.dev) for _ in range(2))
+        grads = self._by_name(self._enqueue_vjp(live, d_logits, d_center, out=out))
+        return (grads,) + out if want_logits else grads
+
+    def optimizer_step(self, opt):
+        """``opt.step()`` for any ``torch.optim`` optimizer over ``model.parameters()``: the parameters are views into the flat
+        buffer, so the optimizer writes theta directly; ``params_changed()`` then tells the engine (the stepped copy of the label
+        classifier and the score table are taken from theta again; an outstanding forward becomes stale)."""
+        opt.step()
+        self.params_changed()
+
+    def train_step_custom(self, ids: torch.Tensor, labels: torch.Tensor, loss_fn):
+        """One training step with the caller's loss and the ENGINE's Adam (its lr, betas, eps, weight decay): forward ->
+        ``loss_fn(gnn_logits, center_logits, labels)`` (a scalar) -> its autograd down to the two logit tensors -> pcg_dense_vjp ->
+        pcg_wgrad(apply = 1, with_clf = 1).  Every parameter, the label classifier included, is stepped together from this batch's
+        gradient: there is no one-step-ahead classifier on this path.  Returns the loss tensor (detached); nothing synchronises.
+        Eager launches only - the graph, pipelined and whole-epoch engines keep the built-in loss."""
+        if ids.numel() == 0:
+            return None
+        with torch.no_grad():
+            gnn, center = self._forward_live(ids, labels, True)
+        live = self._live
+        gnn.requires_grad_(True)
+        center.requires_grad_(True)
+        with torch.enable_grad():
+            loss = loss_fn(gnn, center, labels)
+        d_gnn, d_center = torch.autograd.grad(loss, (gnn, center), allow_unused=True)
+        self._theta_written()                        # (the forward is spent: theta is about to change)
+        self.step_counter += 1                       # Adam's t, on the device, ahead of the launch that reads it
+        self._enqueue_vjp(live, d_gnn, d_center, apply=True)
+        self.clf_next.copy_(self.theta[self.n_rest:])      # (the label classifier is stepped with everything else here)
+        self._fresh = False
+        return loss.detach()
 
     def infer(self, ids=None, chunk: Optional[int] = None, want_center: bool = False):
         """Test-mode logits of a whole node set in one call (pcg_infer_set): ONE score pass, then per chunk of ids plan ->

@@ -25,7 +25,13 @@ DEFAULTS = dict(model="PCGNN", emb_size=64, rho=0.5, alpha=2.0, lr=0.01, weight_
 
 
 class PCGNNTrainer:
-    def __init__(self, workload, config: Optional[Dict] = None, device=None):
+    def __init__(self, workload, config: Optional[Dict] = None, device=None, loss_fn=None, optimizer=None):
+        """loss_fn / optimizer (keyword arguments, not config keys; engine="fused" only): a custom objective on the fused path.
+        ``loss_fn(gnn_logits, center_logits, labels)`` (labels: the batch's int32 device tensor) returns a scalar; with it alone
+        ``step()`` runs ``FusedPCGNN.train_step_custom`` (the engine's own Adam).  ``optimizer``, a factory
+        ``params -> torch.optim.Optimizer``, replaces that Adam too: ``step()`` then runs zero_grad -> ``FusedPCGNN.forward`` ->
+        loss_fn -> backward -> ``FusedPCGNN.optimizer_step``.  Without them every engine does what it did before.  The graph /
+        whole-epoch paths (engine="graph", ``run_epoch_graph``, ``run_epoch_one_graph``) keep the built-in loss and Adam."""
         cfg = dict(DEFAULTS)
         cfg.update(config or {})
         self.cfg = cfg
@@ -43,6 +49,12 @@ class PCGNNTrainer:
         self.engine = cfg["engine"]
         self.fused = None
         self.opt = None
+        self.loss_fn = loss_fn
+        if (loss_fn is not None or optimizer is not None) and self.engine != "fused":
+            raise ValueError(f"loss_fn / optimizer need engine='fused' (got {self.engine!r}): the graph engine keeps the built-in "
+                             f"loss, and the torch engine is plain autograd - write its loop directly")
+        if optimizer is not None and loss_fn is None:
+            raise ValueError("optimizer needs a loss_fn: the built-in step has its own Adam")
         if self.engine == "torch":      # dense tail + Adam through torch autograd (generic, slower)
             self.opt = torch.optim.Adam([p for p in self.model.parameters() if p.requires_grad], lr=cfg["lr"],
                                         weight_decay=cfg["weight_decay"])             # :124
@@ -50,6 +62,8 @@ class PCGNNTrainer:
             from .fused import FusedPCGNN
             self.fused = FusedPCGNN(self.model, cfg["lr"], cfg["weight_decay"], max_batch=cfg["batch_size"],
                                     global_batch_scale=cfg.get("world_size", 1), list_capacity=cfg.get("list_capacity"))
+            if optimizer is not None:
+                self.opt = optimizer([p for p in self.model.parameters() if p.requires_grad])
         self.labels_dev = torch.from_numpy(w.labels).to(self.device)
         self.labels_i32 = self.labels_dev.to(torch.int32)
         self.sampler = PickSampler(w.idx_train, w.labels[w.idx_train], w.homo_deg[w.idx_train], self.device,
@@ -108,6 +122,14 @@ class PCGNNTrainer:
             labels = self.labels_i32[batch_ids.long()]
             if self.engine == "graph":
                 self.fused.train_step_graph(batch_ids, labels, timed)
+            elif self.opt is not None:               # custom loss, external optimizer
+                self.opt.zero_grad(set_to_none=True)
+                loss = self.loss_fn(*self.fused.forward(batch_ids, labels), labels)
+                loss.backward()
+                self.fused.optimizer_step(self.opt)
+                return loss.detach()
+            elif self.loss_fn is not None:           # custom loss, the engine's Adam
+                return self.fused.train_step_custom(batch_ids, labels, self.loss_fn)
             else:
                 self.fused.train_step(batch_ids, labels)
             return None
