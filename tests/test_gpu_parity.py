@@ -1093,7 +1093,9 @@ def test_step_front_equals_separate_calls(P, B, train):
     assert torch.equal(s0_a, s0_c)
 
 
-@pytest.mark.parametrize("B,n_pos", [(300, 1500), (700, 5000), (64, 40)])
+# (8192 / 8193: the last size whose LDS search index takes every 16th key and the first that takes every 32nd; 16384: the last size
+#  sorted inside the select kernel)
+@pytest.mark.parametrize("B,n_pos", [(300, 1500), (700, 5000), (64, 40), (64, 8192), (64, 8193), (64, 16384)])
 def test_epoch_plans_and_in_kernel_sort_equal_separate_calls(P, B, n_pos):
     """pcg_plan_batches (every batch of an "epoch" planned in one launch, one plan slot each, ONE shared data part) +
     pcg_step_scores_train (scores and UNSORTED train-pos keys in one launch) + pcg_choose_gather_planned(sync_words) (the
@@ -1113,6 +1115,10 @@ def test_epoch_plans_and_in_kernel_sort_equal_separate_calls(P, B, n_pos):
     train_pos = np.flatnonzero(labels == 1)[:n_pos].tolist()
     if len(train_pos) < n_pos:                      # (more positives than the labels hold: any distinct nodes will do)
         train_pos = sorted(set(train_pos) | set(range(100, 100 + n_pos - len(train_pos))))
+    if len(train_pos) < n_pos:                      # (some of those were positives already: top up to exactly n_pos)
+        have = set(train_pos)
+        train_pos = sorted(have | set([v for v in range(n) if v not in have][:n_pos - len(have)]))
+    assert len(train_pos) == n_pos
     g = P.DeviceGraph(X, csrs, train_pos, dev())
     F, E, R = 32, 16, 2
     gen = torch.Generator().manual_seed(8)
