@@ -1,4 +1,4 @@
-"""What the GPU gradient tests share (tests/test_gpu_grad_f64.py, tests/test_gpu_dist_train_f64.py): the tally that prints every
+"""What the GPU gradient tests share (tests/test_gpu_grad_f64.py, tests/test_gpu_dist_train_f64.py, tests/train_adam_ref.py): the tally that prints every
 figure before anything is asserted, the flat-buffer -> per-parameter views, and the first-moment check (the gradient a training
 step took, recovered from Adam's first moment, with float32 torch.optim.Adam on the float32 reference as its yardstick)."""
 import types
@@ -64,14 +64,19 @@ def adam_first_moment_f32(theta_old, grad32, c, state=None):
     return opt.state[p]["exp_avg"]
 
 
+def recovered_pair(c, m_new, theta_old, grad32, state=None):
+    """One parameter: (the gradient the step took, recovered from its first moment m_new; the yardstick - the float32
+    reference's gradient sent through float32 torch.optim.Adam and the same recovery).  state: the parameter's (m, v) before."""
+    mo = None if state is None else state[0]
+    m32 = adam_first_moment_f32(theta_old, grad32, c, state)
+    return D.recover_grad(m_new, theta_old, c.betas[0], c.wd, mo), D.recover_grad(m32, theta_old, c.betas[0], c.wd, mo)
+
+
 def check_first_moment(tally, c, fz, what, m_new, theta_old, r64, r32, state=None):
     """the gradient the step took, recovered from Adam's first moment, per parameter; the yardstick goes the same way"""
     th, mn = by_name(fz, theta_old), by_name(fz, m_new)
     m_old = None if state is None else by_name(fz, state[0])
     v_old = None if state is None else by_name(fz, state[1])
     for k in PARAM_KEYS(c.R):
-        mo = None if state is None else m_old[k]
-        g_dev = D.recover_grad(mn[k], th[k], c.betas[0], c.wd, mo)
-        m32 = adam_first_moment_f32(th[k], r32["grads"][k], c, None if state is None else (m_old[k], v_old[k]))
-        g_32 = D.recover_grad(m32, th[k], c.betas[0], c.wd, mo)
+        g_dev, g_32 = recovered_pair(c, mn[k], th[k], r32["grads"][k], None if state is None else (m_old[k], v_old[k]))
         tally.check(f"{what} grad {k}", g_dev, r64["grads"][k], g_32)
