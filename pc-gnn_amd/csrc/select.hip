@@ -125,9 +125,29 @@ constexpr int SORT_SPIN_MAX = 1 << 21;       // x >= 0.2 us per poll
 // sorted key.  Every row's window search starts in it (LDS) instead of in the keys themselves: a thousand rows are released at
 // the same moment, and the first round of a search over the whole buffer probes the same 64 positions for every one of them -
 // the few L2 lines behind those positions took ~4 us to serve them all.
+//
+// PRE (a compile-time flag of the row paths, picked by the host from n_sort == 0): the keys were sorted by an EARLIER launch.
+// No device memory is polled: the workgroup's last wave builds the index at entry (select_rows_body) while the others start on
+// their rows, and sets [0]; a wave that needs the index before that waits on the LDS word alone (nothing it waits for waits for
+// anything but its own loads).
 constexpr int KIDX_MAX = 512;
+constexpr int WIN_WORDS = 8;                 // behind the index: the six words of a workgroup row's early window (select_wg_row)
+template <bool PRE = false>
 __device__ __forceinline__ uint64_t pk_ld(const uint64_t *pk, int i);
+__device__ __forceinline__ int key_index_stride(int P) {
+    int stride = 16;
+    while ((P + stride - 1) / stride > KIDX_MAX) stride <<= 1;
+    return stride;
+}
+template <bool PRE>
 __device__ __forceinline__ void wait_sorted_keys(const ChooseArgs &a, int &keys_ok, int lane, int *sortw) {
+    if constexpr (PRE) {
+        if (keys_ok) return;
+        while (__hip_atomic_load(&sortw[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(1);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        keys_ok = 1;
+        return;
+    }
     if (a.n_sort == 0 || keys_ok) return;                                  // (wave-uniform)
     if (__hip_atomic_load(&sortw[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
         int elected = 0;
@@ -146,8 +166,7 @@ __device__ __forceinline__ void wait_sorted_keys(const ChooseArgs &a, int &keys_
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");         // (compiler + wave ordering: the key loads come after the wait)
             const int P = a.g.n_pos;
-            int stride = 16;
-            while ((P + stride - 1) / stride > KIDX_MAX) stride <<= 1;
+            const int stride = key_index_stride(P);
             const int n_idx = (P + stride - 1) / stride;
             for (int t = lane; t < n_idx; t += PCG_WAVE) sortw[4 + t] = (int)(uint32_t)(pk_ld(a.pos_keys, t * stride) >> 32);
             if (lane == 0) {
@@ -178,10 +197,19 @@ __device__ __forceinline__ void wait_sorted_keys(const ChooseArgs &a, int &keys_
 //   PCG_PK_NT = 1: non-temporal loads (L1 bypassed, no sc1).
 // An agent-scope acquire fence instead (buffer_inv sc1 per workgroup, three workgroups per CU) cost ~5 us per positive row: it
 // empties the L1 under the other workgroups' score gathers.
+//
+// PRE (the keys were written by an earlier launch): none of the above is needed - a launch starts with clean caches, so plain
+// cached loads see the keys, and the few hot lines of the buffer (21 KB at YelpChi scale) stay in the L1 (PCG_PRE_PLAIN = 1, the
+// default; 0: the sc1 form in presorted launches too - the A/B reference).
 #ifndef PCG_PK_NT
 #define PCG_PK_NT 2
 #endif
+#ifndef PCG_PRE_PLAIN
+#define PCG_PRE_PLAIN 1
+#endif
+template <bool PRE>
 __device__ __forceinline__ uint64_t pk_ld(const uint64_t *pk, int i) {
+    if constexpr (PRE && PCG_PRE_PLAIN) return pk[i];
 #if PCG_PK_NT == 2
     // (the descriptor is wave-uniform - four scalar registers formed from the kernel argument; 0x00020000: raw 32-bit format;
     //  the range is not bounded here: every index is clamped by its caller)
@@ -196,8 +224,25 @@ __device__ __forceinline__ uint64_t pk_ld(const uint64_t *pk, int i) {
 #endif
 }
 
-__device__ __forceinline__ float pos_score(const uint64_t *pk, int i) { return from_orderable((uint32_t)(pk_ld(pk, i) >> 32)); }
-__device__ __forceinline__ uint32_t pos_dkey(const uint64_t *pk, int i, float c) { return dist_key(c, pos_score(pk, i)); }
+// the score half of a key alone (the window search's probes need nothing else)
+template <bool PRE>
+__device__ __forceinline__ uint32_t pk_score_bits(const uint64_t *pk, int i) {
+    if constexpr (PRE && PCG_PRE_PLAIN) return reinterpret_cast<const uint32_t *>(pk)[2 * (size_t)i + 1];
+    return (uint32_t)(pk_ld<PRE>(pk, i) >> 32);
+}
+// the same for the staged window search (WinStage): a load that stays where it is written.  The compiler sinks an ordinary load
+// to its first use - behind the row's score gathers and the k-th value, which is the round trip the stages are there to hide; a
+// relaxed atomic load of wavefront scope is the same instruction (no cache bits, no wait of its own) and is not moved.
+template <bool PRE>
+__device__ __forceinline__ uint32_t pk_score_bits_here(const uint64_t *pk, int i) {
+    if constexpr (PRE && PCG_PRE_PLAIN)
+        return __hip_atomic_load(reinterpret_cast<const uint32_t *>(pk) + 2 * (size_t)i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    return (uint32_t)(pk_ld<PRE>(pk, i) >> 32);
+}
+template <bool PRE = false>
+__device__ __forceinline__ float pos_score(const uint64_t *pk, int i) { return from_orderable(pk_score_bits<PRE>(pk, i)); }
+template <bool PRE = false>
+__device__ __forceinline__ uint32_t pos_dkey(const uint64_t *pk, int i, float c) { return dist_key(c, pos_score<PRE>(pk, i)); }
 
 // First x in [lo, hi] with pred(x) false, pred being true on a prefix of [lo, hi).
 // 64 probes per step (one memory latency each) instead of one.
@@ -227,10 +272,11 @@ __device__ __forceinline__ int wave_partition_point(int lo, int hi, int lane, Pr
 }
 
 // first index in [i0, end) whose distance key != kstar (or end); all lanes take part
+template <bool PRE>
 __device__ __forceinline__ int run_end_fwd(const uint64_t *pk, float c, uint32_t kstar, int i0, int end, int lane) {
     for (int i = i0; i < end; i += PCG_WAVE) {
         const int j = i + lane;
-        const bool same = j < end && pos_dkey(pk, j, c) == kstar;
+        const bool same = j < end && pos_dkey<PRE>(pk, j, c) == kstar;
         const uint64_t bad = ~__ballot(same);
         if (bad) {
             const int f = i + (__ffsll((unsigned long long)bad) - 1);
@@ -240,10 +286,11 @@ __device__ __forceinline__ int run_end_fwd(const uint64_t *pk, float c, uint32_t
     return end;
 }
 // smallest x in [low, i0+1] such that every index in [x, i0] has key == kstar (i0+1 if none)
+template <bool PRE>
 __device__ __forceinline__ int run_begin_bwd(const uint64_t *pk, float c, uint32_t kstar, int i0, int low, int lane) {
     for (int i = i0; i >= low; i -= PCG_WAVE) {
         const int j = i - lane;
-        const bool same = j >= low && pos_dkey(pk, j, c) == kstar;
+        const bool same = j >= low && pos_dkey<PRE>(pk, j, c) == kstar;
         const uint64_t bad = ~__ballot(same);
         if (bad) {
             const int f = i - (__ffsll((unsigned long long)bad) - 1);  // first non-matching going down
@@ -276,38 +323,69 @@ __device__ __forceinline__ void wave_kth(uint32_t ck, bool have, int n, int want
 struct MinorWindow {
     int L, R, L2, R2, tau, need_t;
 };
+constexpr uint32_t WIN_NOKEY = 0xFFFFFFFEu;    // never equals a distance key (keys have bit 31 clear)
+// Where the window [lo, lo + m) of the m nearest (m < P) can start: with pc = the number of keys whose score is below c, the
+// search predicate (minority_window) is false for every x >= pc (the left end is not below c) and true for every x < pc - m
+// (the element right of the window is still below c), so lo is in [pc - m, pc]; the workgroup's search index (every stride-th
+// key's score, in LDS) brackets pc to one stride.  Without an index: [0, P - m].
+template <bool PRE>
+__device__ __forceinline__ void window_bracket(const ChooseArgs &a, int m, float c, int lane, const int *sortw, int &lo_min, int &lo_max) {
+    const int P = a.g.n_pos;
+    lo_min = 0;
+    lo_max = P - m;
+    if ((PRE || a.n_sort > 0) && sortw) {
+        // (PRE: the index's shape from P itself - scalar arithmetic - instead of the two LDS words: what follows stays wave-uniform
+        //  to the compiler)
+        const int stride = PRE ? key_index_stride(P) : sortw[3], n_idx = PRE ? (P + stride - 1) / stride : sortw[2];
+        const uint32_t *ix = reinterpret_cast<const uint32_t *>(sortw + 4);
+        const int t = wave_partition_point(0, n_idx, lane, [&](int x) { return from_orderable(ix[x]) < c; });
+        const int pc_lo = t > 0 ? (t - 1) * stride + 1 : 0, pc_hi = t * stride < P ? t * stride : P;
+        lo_min = pc_lo - m > 0 ? pc_lo - m : 0;
+        lo_max = pc_hi < P - m ? pc_hi : P - m;
+        lo_max = lo_max < lo_min ? lo_min : lo_max;
+    }
+}
+
+template <bool PRE>
+__device__ __forceinline__ MinorWindow window_resolve(const ChooseArgs &a, int m, float c, int lane, int lo, uint32_t ka, uint32_t kb,
+                                                      uint32_t ka1, uint32_t kb1, uint32_t kl, uint32_t kr);
+
+template <bool PRE>
 __device__ __forceinline__ MinorWindow minority_window(const ChooseArgs &a, int m, float c, int lane, const int *sortw) {
     const uint64_t *__restrict__ pk = a.pos_keys;
     const int P = a.g.n_pos;
-    int L, R, L2, R2, tau = INT_MAX, need_t = 0;
     if (m >= P) {
-        L = L2 = 0;
-        R = R2 = P;
-    } else {
-        // window [lo, lo+m) of the m nearest: first lo whose left end is not farther than the element right of the window.
-        // With pc = the number of keys whose score is below c: the predicate is false for every x >= pc (the left end is not
-        // below c) and true for every x < pc - m (the element right of the window is still below c), so lo is in
-        // [pc - m, pc]; the workgroup's search index (every stride-th key's score, in LDS) brackets pc to one stride.
-        int lo_min = 0, lo_max = P - m;
-        if (a.n_sort > 0 && sortw) {
-            const int n_idx = sortw[2], stride = sortw[3];
-            const uint32_t *ix = reinterpret_cast<const uint32_t *>(sortw + 4);
-            const int t = wave_partition_point(0, n_idx, lane, [&](int x) { return from_orderable(ix[x]) < c; });
-            const int pc_lo = t > 0 ? (t - 1) * stride + 1 : 0, pc_hi = t * stride < P ? t * stride : P;
-            lo_min = pc_lo - m > 0 ? pc_lo - m : 0;
-            lo_max = pc_hi < P - m ? pc_hi : P - m;
-            lo_max = lo_max < lo_min ? lo_min : lo_max;
-        }
-        const int lo = wave_partition_point(lo_min, lo_max, lane, [&](int x) {
-            return (c - pos_score(pk, x)) > (pos_score(pk, x + m) - c);
-        });
-        // one batch of six independent loads decides the usual tie-free case
-        const uint32_t NOKEY = 0xFFFFFFFEu;    // never equals a distance key (keys have bit 31 clear)
-        const uint32_t ka = pos_dkey(pk, lo, c), kb = pos_dkey(pk, lo + m - 1, c);
-        const uint32_t ka1 = m > 1 ? pos_dkey(pk, lo + 1, c) : NOKEY;
-        const uint32_t kb1 = m > 1 ? pos_dkey(pk, lo + m - 2, c) : NOKEY;
-        const uint32_t kl = lo > 0 ? pos_dkey(pk, lo - 1, c) : NOKEY;
-        const uint32_t kr = lo + m < P ? pos_dkey(pk, lo + m, c) : NOKEY;
+        MinorWindow w;
+        w.L = w.L2 = 0;
+        w.R = w.R2 = P;
+        w.tau = INT_MAX;
+        w.need_t = 0;
+        return w;
+    }
+    // window [lo, lo+m) of the m nearest: first lo whose left end is not farther than the element right of the window.
+    int lo_min, lo_max;
+    window_bracket<PRE>(a, m, c, lane, sortw, lo_min, lo_max);
+    const int lo = wave_partition_point(lo_min, lo_max, lane, [&](int x) {
+        return (c - pos_score<PRE>(pk, x)) > (pos_score<PRE>(pk, x + m) - c);
+    });
+    // one batch of six independent loads decides the usual tie-free case
+    const uint32_t ka = pos_dkey<PRE>(pk, lo, c), kb = pos_dkey<PRE>(pk, lo + m - 1, c);
+    const uint32_t ka1 = m > 1 ? pos_dkey<PRE>(pk, lo + 1, c) : WIN_NOKEY;
+    const uint32_t kb1 = m > 1 ? pos_dkey<PRE>(pk, lo + m - 2, c) : WIN_NOKEY;
+    const uint32_t kl = lo > 0 ? pos_dkey<PRE>(pk, lo - 1, c) : WIN_NOKEY;
+    const uint32_t kr = lo + m < P ? pos_dkey<PRE>(pk, lo + m, c) : WIN_NOKEY;
+    return window_resolve<PRE>(a, m, c, lane, lo, ka, kb, ka1, kb1, kl, kr);
+}
+
+// The window from its start lo (m < P) and the distance keys at its edges: lo, lo + m - 1, lo + 1, lo + m - 2, lo - 1, lo + m
+// (WIN_NOKEY where there is no such element) - the usual tie-free case needs no further load.
+template <bool PRE>
+__device__ __forceinline__ MinorWindow window_resolve(const ChooseArgs &a, int m, float c, int lane, int lo, uint32_t ka, uint32_t kb,
+                                                      uint32_t ka1, uint32_t kb1, uint32_t kl, uint32_t kr) {
+    const uint64_t *__restrict__ pk = a.pos_keys;
+    const int P = a.g.n_pos;
+    int L, R, L2, R2, tau = INT_MAX, need_t = 0;
+    {
         const uint32_t ks = ka > kb ? ka : kb;  // m-th smallest distance
         const bool tie_l = ka == ks, tie_r = kb == ks;
         const bool none_outside = kl != ks && kr != ks;
@@ -320,10 +398,10 @@ __device__ __forceinline__ MinorWindow minority_window(const ChooseArgs &a, int 
             R = R2 = tie_l ? lo + m : lo + m - 1;
             if (tie_l) L2 = lo; else R2 = lo + m;      // that one element is the (single) tie, and it is taken
         } else {
-            L = run_end_fwd(pk, c, ks, lo, lo + m, lane);
-            R = (L == lo + m) ? L : run_begin_bwd(pk, c, ks, lo + m - 1, L, lane);
-            L2 = run_begin_bwd(pk, c, ks, lo - 1, 0, lane);
-            R2 = run_end_fwd(pk, c, ks, lo + m, P, lane);
+            L = run_end_fwd<PRE>(pk, c, ks, lo, lo + m, lane);
+            R = (L == lo + m) ? L : run_begin_bwd<PRE>(pk, c, ks, lo + m - 1, L, lane);
+            L2 = run_begin_bwd<PRE>(pk, c, ks, lo - 1, 0, lane);
+            R2 = run_end_fwd<PRE>(pk, c, ks, lo + m, P, lane);
         }
         // ties are [L2, L) and [R, R2); strictly nearer ones are [L, R)
         need_t = m - (R - L);
@@ -339,11 +417,11 @@ __device__ __forceinline__ MinorWindow minority_window(const ChooseArgs &a, int 
                 int cn = 0;
                 for (int i0 = L2; i0 < L; i0 += PCG_WAVE) {
                     const int i = i0 + lane;
-                    cn += wave_count(i < L && (int)(uint32_t)pk_ld(pk, i) <= mid);
+                    cn += wave_count(i < L && (int)(uint32_t)pk_ld<PRE>(pk, i) <= mid);
                 }
                 for (int i0 = R; i0 < R2; i0 += PCG_WAVE) {
                     const int i = i0 + lane;
-                    cn += wave_count(i < R2 && (int)(uint32_t)pk_ld(pk, i) <= mid);
+                    cn += wave_count(i < R2 && (int)(uint32_t)pk_ld<PRE>(pk, i) <= mid);
                 }
                 if (cn >= need_t) phi = mid;
                 else plo = mid + 1;
@@ -353,7 +431,7 @@ __device__ __forceinline__ MinorWindow minority_window(const ChooseArgs &a, int 
             const int nl = L - L2;
             const int ti = lane < nl ? L2 + lane : R + (lane - nl);
             const bool tv = lane < T;
-            const int tp = tv ? (int)(uint32_t)pk_ld(pk, ti) : INT_MAX;
+            const int tp = tv ? (int)(uint32_t)pk_ld<PRE>(pk, ti) : INT_MAX;
             int rank = 0;
             for (int j = 0; j < T; ++j) rank += __builtin_amdgcn_readlane(tp, j) < tp;
             // tau = the need_t-th smallest position among the ties (positions are distinct)
@@ -367,16 +445,126 @@ __device__ __forceinline__ MinorWindow minority_window(const ChooseArgs &a, int 
     return w;
 }
 
+// One round of wave_partition_point split at its memory round trip: the position a lane probes in [lo, hi) (hi > lo) ...
+__device__ __forceinline__ int pp_probe(int lo, int hi, int lane, bool &valid) {
+    const int n = hi - lo;
+    if (n <= PCG_WAVE) {
+        valid = lo + lane < hi;
+        return valid ? lo + lane : hi - 1;
+    }
+    const int step = (n + PCG_WAVE - 1) >> 6;
+    const int q = lo + (lane + 1) * step - 1;
+    valid = true;
+    return q > hi - 1 ? hi - 1 : q;
+}
+// ... and what cnt probes that answered true make of [lo, hi]: true when lo is the partition point
+__device__ __forceinline__ bool pp_advance(int &lo, int &hi, int cnt) {
+    const int n = hi - lo;
+    if (n <= PCG_WAVE) {
+        lo += cnt;
+        return true;
+    }
+    if (cnt == PCG_WAVE) {
+        lo = hi;
+        return true;
+    }
+    const int step = (n + PCG_WAVE - 1) >> 6;
+    int qc = lo + (cnt + 1) * step - 1;   // first probe that answered false
+    if (qc > hi - 1) qc = hi - 1;
+    if (cnt > 0) {
+        int ql = lo + cnt * step - 1;
+        if (ql > hi - 1) ql = hi - 1;
+        lo = ql + 1;
+    }
+    hi = qc;
+    return hi <= lo;
+}
+
+// minority_window in stages, for a single-wave row of a presorted launch: the window's loads are issued BESIDE the row's own
+// (begin: behind the neighbour ids' loads, as soon as the centre's score is there - the first probe round travels with the
+// score gathers; step: the next round, or the edge keys, which stay in flight over the k-th value) instead of behind them,
+// and win_stage_end hands finish_row the same six numbers minority_window would (same bracket, same predicate - it is true on
+// a prefix, so the partition point does not depend on the probes -, same window_resolve).  Everything but v0 / v1 is
+// wave-uniform.  live: 1 = a probe round is in flight, 2 = the edge keys are.  Rows that cannot be staged (m >= P, or a
+// bracket that may take more than two probe rounds: win_stageable) take the plain row path: their tail calls minority_window.
+struct WinStage {
+    int live, lo, hi;
+    uint32_t v0, v1;
+};
+template <bool PRE>
+__device__ __forceinline__ WinStage win_stage_issue(const ChooseArgs &a, int m, int lane, int lo, int hi) {
+    const uint64_t *__restrict__ pk = a.pos_keys;
+    const int P = a.g.n_pos;
+    const bool probe = hi > lo;              // (wave-uniform)
+    // a probe round: the scores at x and x + m (x <= hi - 1 <= P - m - 1); or, lo known, the six edge keys, one per lane
+    // (minority_window's order), clamped.  One pair of loads serves both: no load sits inside a branch.
+    bool valid;
+    const int x = pp_probe(lo, probe ? hi : lo + 1, lane, valid);
+    int e = lane == 0 ? lo : lane == 1 ? lo + m - 1 : lane == 2 ? lo + 1 : lane == 3 ? lo + m - 2 : lane == 4 ? lo - 1 : lo + m;
+    e = e < 0 ? 0 : (e > P - 1 ? P - 1 : e);
+    WinStage s;
+    s.lo = lo;
+    s.hi = hi;
+    s.live = probe ? 1 : 2;
+    s.v0 = pk_score_bits_here<PRE>(pk, probe ? x : e);
+    s.v1 = pk_score_bits_here<PRE>(pk, probe ? x + m : e);
+    return s;
+}
+// (the caller has checked win_stageable: begin and step hold no branch around a load - the compiler waits for EVERY load in
+//  flight where two paths meet that issued different numbers of them, the row's own gathers included)
+__device__ __forceinline__ bool win_stageable(const ChooseArgs &a, int m) {
+    const int P = a.g.n_pos;
+    return m > 0 && m < P && key_index_stride(P) - 1 + m <= PCG_WAVE * PCG_WAVE;     // (a bracket is at most stride - 1 + m wide)
+}
+template <bool PRE>
+__device__ __forceinline__ WinStage win_stage_begin(const ChooseArgs &a, int m, float c, int lane, const int *sortw) {
+    int lo, hi;
+    window_bracket<PRE>(a, m, c, lane, sortw, lo, hi);
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    hi = __builtin_amdgcn_readfirstlane(hi);
+    return win_stage_issue<PRE>(a, m, lane, lo, hi);
+}
+// consumes a probe round - if one is in flight - and issues what comes next (the edge keys once more if they were under way
+// already: the same lines, the same values)
+template <bool PRE>
+__device__ __forceinline__ WinStage win_stage_step(const ChooseArgs &a, int m, float c, int lane, const WinStage &s) {
+    bool valid;
+    (void)pp_probe(s.lo, s.hi > s.lo ? s.hi : s.lo + 1, lane, valid);
+    const bool farther = (c - from_orderable(s.v0)) > (from_orderable(s.v1) - c);
+    const int cnt = wave_count(valid & farther);
+    int lo = s.lo, hi = s.hi > s.lo ? s.hi : s.lo + 1;
+    const bool done = pp_advance(lo, hi, cnt);
+    const bool probed = s.live == 1;
+    lo = probed ? lo : s.lo;
+    hi = probed ? (done ? lo : hi) : s.lo;
+    return win_stage_issue<PRE>(a, m, lane, lo, hi);
+}
+template <bool PRE>
+__device__ __forceinline__ MinorWindow win_stage_end(const ChooseArgs &a, int m, float c, int lane, WinStage s) {
+    while (s.live == 1) s = win_stage_step<PRE>(a, m, c, lane, s);
+    const int P = a.g.n_pos, lo = s.lo;
+    const int dk = (int)dist_key(c, from_orderable(s.v0));
+    const uint32_t ka = (uint32_t)__builtin_amdgcn_readlane(dk, 0), kb = (uint32_t)__builtin_amdgcn_readlane(dk, 1);
+    const uint32_t ka1 = m > 1 ? (uint32_t)__builtin_amdgcn_readlane(dk, 2) : WIN_NOKEY;
+    const uint32_t kb1 = m > 1 ? (uint32_t)__builtin_amdgcn_readlane(dk, 3) : WIN_NOKEY;
+    const uint32_t kl = lo > 0 ? (uint32_t)__builtin_amdgcn_readlane(dk, 4) : WIN_NOKEY;
+    const uint32_t kr = lo + m < P ? (uint32_t)__builtin_amdgcn_readlane(dk, 5) : WIN_NOKEY;
+    return window_resolve<PRE>(a, m, c, lane, lo, ka, kb, ka1, kb1, kl, kr);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Shared tail of every row (layers.py:675-694): minority over-sampling for positive centres, GCN-style self union,
 // the kept ids to the list (unless the caller has stored them already), |set|, length and the chunk fill counts.
 // sel[0 .. ns): the kept neighbour ids, ascending - LDS, or (over-long rows) the row's own region of the global list.
 // NW waves work on the row (tid / NT: thread index and count inside the group); red: 2 * NW + 2 ints of LDS (NW > 1).
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NW>
+// has_window: pre_window is the window, worked out beside the row's key pass (select_wg_row: by a wave of the workgroup; the
+// single-wave rows of a presorted launch: in stages, WinStage); otherwise it is worked out here.  (A flag and a reference, not a
+// pointer that may be null: the callers' structs stay in registers.)
+template <int NW, bool PRE>
 __device__ __forceinline__ void finish_row(const ChooseArgs &a, int row, const RowRec &p, float c, const uint32_t *sel, int ns,
                                            bool sel_stored, int wave, int lane, int *red, int &keys_ok, int *sortw,
-                                           const int *pre_window = nullptr) {
+                                           bool has_window, const MinorWindow &pre_window) {
     constexpr int NT = NW * PCG_WAVE;
     const int tid = wave * PCG_WAVE + lane;
     const int m = p.m, node = p.node;
@@ -386,12 +574,12 @@ __device__ __forceinline__ void finish_row(const ChooseArgs &a, int row, const R
     if (m > 0) {
         const uint64_t *__restrict__ pk = a.pos_keys;
         int L, R, L2, R2, tau, need_t;
-        if (pre_window) {                        // worked out by a wave of this workgroup beside the row's key pass (select_wg_row)
-            L = pre_window[0]; R = pre_window[1]; L2 = pre_window[2]; R2 = pre_window[3]; tau = pre_window[4]; need_t = pre_window[5];
+        if (has_window) {
+            L = pre_window.L; R = pre_window.R; L2 = pre_window.L2; R2 = pre_window.R2; tau = pre_window.tau; need_t = pre_window.need_t;
         } else {
-            wait_sorted_keys(a, keys_ok, lane, sortw);
+            wait_sorted_keys<PRE>(a, keys_ok, lane, sortw);
             PCG_STAMP(7);
-            const MinorWindow mw = minority_window(a, m, c, lane, sortw);
+            const MinorWindow mw = minority_window<PRE>(a, m, c, lane, sortw);
             L = mw.L; R = mw.R; L2 = mw.L2; R2 = mw.R2; tau = mw.tau; need_t = mw.need_t;
         }
         PCG_STAMP(4);
@@ -402,7 +590,7 @@ __device__ __forceinline__ void finish_row(const ChooseArgs &a, int row, const R
 #pragma unroll
             for (int x = 0; x < KEY_UNROLL; ++x) {
                 const int j = base + x * NT;
-                pos[x] = (uint32_t)pk_ld(pk, L + (j < n_strict ? j : n_strict - 1));
+                pos[x] = (uint32_t)pk_ld<PRE>(pk, L + (j < n_strict ? j : n_strict - 1));
             }
 #pragma unroll
             for (int x = 0; x < KEY_UNROLL; ++x) u[x] = (uint32_t)a.g.train_pos[pos[x]];
@@ -427,7 +615,7 @@ __device__ __forceinline__ void finish_row(const ChooseArgs &a, int row, const R
                     bool take = false;
                     uint32_t u = 0;
                     if (i < e0i) {
-                        const uint32_t pos = (uint32_t)pk_ld(pk, i);
+                        const uint32_t pos = (uint32_t)pk_ld<PRE>(pk, i);
                         take = (int)pos <= tau;
                         if (take) u = (uint32_t)a.g.train_pos[pos];
                     }
@@ -525,10 +713,12 @@ __device__ __forceinline__ void select_four_short_rows(const ChooseArgs &a, int 
 
 // One row of 17 .. 64 neighbours on one wave: one key per lane, ranked lane against lane in the stable (key, position)
 // order - no k-th value is formed.  area: WAVE_AREA words of LDS (the kept ids go behind the histogram's place).
-__device__ __forceinline__ void select_lane_row(const ChooseArgs &a, int row, uint32_t *area, int lane, int &keys_ok, int *sortw) {
+// STG (presorted launches): a positive centre's window search runs in stages beside the row's own loads (WinStage).
+template <bool PRE, bool STG>
+__device__ __forceinline__ void select_lane_row_body(const ChooseArgs &a, int row, const RowRec &p, uint32_t *area, int lane, int &keys_ok,
+                                                     int *sortw) {
     const int tid = lane;
     if (a.stamps && tid == 0) a.stamps[(size_t)row * 8] = wall_clock64() | ((unsigned long long)blockIdx.x << 54);   // + who ran it
-    const RowRec p = a.w.recs[row];
     const int d = p.d, k = p.k;
     const bool keep_all = rec_keep_all(p);
     const int r = row / a.B;
@@ -538,7 +728,16 @@ __device__ __forceinline__ void select_lane_row(const ChooseArgs &a, int row, ui
     const bool tail = p.m > 0 || a.add_self;
     const bool have = lane < d;
     const uint32_t id = (uint32_t)nbr[have ? lane : (d > 0 ? d - 1 : 0)];   // unconditional load (clamped)
+    // (the window's first probes leave while the id is under way - they need c, issued in front of it -, the next round or the
+    //  edge keys while the score is; the ranking below runs over the last of them)
+    WinStage ws = {};
+    const int wm = STG ? __builtin_amdgcn_readfirstlane(p.m) : 0;      // (the row record is wave-uniform)
+    if constexpr (STG) {
+            wait_sorted_keys<PRE>(a, keys_ok, lane, sortw);
+            ws = win_stage_begin<PRE>(a, wm, c, lane, sortw);
+        }
     const float sc = s0_ld<2>(a.s0, id);
+    if constexpr (STG) ws = win_stage_step<PRE>(a, wm, c, lane, ws);
     const uint32_t mine = have ? dist_key(c, sc) : 0xFFFFFFFFu;
     PCG_STAMP(1);
     int rank = 0;
@@ -568,8 +767,15 @@ __device__ __forceinline__ void select_lane_row(const ChooseArgs &a, int row, ui
         else a.w.list[p.lbeg + at] = (int32_t)id;
     }
     PCG_STAMP(3);
-    if (tail) finish_row<1>(a, row, p, c, sel_lds, ns, false, 0, lane, nullptr, keys_ok, sortw);
-    else {
+    if (tail) {
+        MinorWindow mw = {};
+        constexpr bool staged = STG;
+        if constexpr (STG) {
+            PCG_STAMP(7);
+            mw = win_stage_end<PRE>(a, wm, c, lane, ws);
+        }
+        finish_row<1, PRE>(a, row, p, c, sel_lds, ns, false, 0, lane, nullptr, keys_ok, sortw, staged, mw);
+    } else {
         if (lane == 0) report_plain_row(a, row, p, ns);
         PCG_STAMP(6);
     }
@@ -577,10 +783,11 @@ __device__ __forceinline__ void select_lane_row(const ChooseArgs &a, int row, ui
 
 // One row of 65 .. 512 neighbours on one wave: keys in registers.  area: WAVE_AREA words of LDS
 // (histogram HIST_W | kept ids T1_CAP | candidates 64).
-__device__ __forceinline__ void select_wave_row(const ChooseArgs &a, int row, uint32_t *area, int lane, int &keys_ok, int *sortw) {
+template <bool PRE, bool STG>
+__device__ __forceinline__ void select_wave_row_body(const ChooseArgs &a, int row, const RowRec &p, uint32_t *area, int lane, int &keys_ok,
+                                                     int *sortw) {
     const int tid = lane;
     if (a.stamps && tid == 0) a.stamps[(size_t)row * 8] = wall_clock64() | ((unsigned long long)blockIdx.x << 54);   // + who ran it
-    const RowRec p = a.w.recs[row];
     const int d = p.d, k = p.k;
     const bool keep_all = rec_keep_all(p);
     const int r = row / a.B;
@@ -592,6 +799,8 @@ __device__ __forceinline__ void select_wave_row(const ChooseArgs &a, int row, ui
 
     // ---- 1. neighbour ids and distance keys -> registers (position u * 64 + lane) ----
     uint32_t id[KPT], key[KPT];
+    WinStage ws = {};
+    const int wm = STG ? __builtin_amdgcn_readfirstlane(p.m) : 0;      // (the row record is wave-uniform)
     {
         float sc[KPT];
 #pragma unroll
@@ -599,8 +808,15 @@ __device__ __forceinline__ void select_wave_row(const ChooseArgs &a, int row, ui
             const int i = u * PCG_WAVE + lane;
             id[u] = (uint32_t)nbr[i < d ? i : d - 1];                    // unconditional loads (clamped): all in flight together
         }
+        // (the window's first probes leave while the ids are under way - they need c, issued in front of them -, the next round or
+        //  the edge keys while the scores are; the k-th value below runs over the last of them)
+        if constexpr (STG) {
+            wait_sorted_keys<PRE>(a, keys_ok, lane, sortw);
+            ws = win_stage_begin<PRE>(a, wm, c, lane, sortw);
+        }
 #pragma unroll
         for (int u = 0; u < KPT; ++u) sc[u] = s0_ld<2>(a.s0, id[u]);
+        if constexpr (STG) ws = win_stage_step<PRE>(a, wm, c, lane, ws);
 #pragma unroll
         for (int u = 0; u < KPT; ++u) key[u] = (u * PCG_WAVE + lane < d) ? dist_key(c, sc[u]) : 0xFFFFFFFFu;
     }
@@ -692,11 +908,43 @@ __device__ __forceinline__ void select_wave_row(const ChooseArgs &a, int row, ui
         ns += __popcll(sm);
     }
     PCG_STAMP(3);
-    if (tail) finish_row<1>(a, row, p, c, sel_lds, ns, false, 0, lane, nullptr, keys_ok, sortw);
-    else {
+    if (tail) {
+        MinorWindow mw = {};
+        constexpr bool staged = STG;
+        if constexpr (STG) {
+            PCG_STAMP(7);
+            mw = win_stage_end<PRE>(a, wm, c, lane, ws);
+        }
+        finish_row<1, PRE>(a, row, p, c, sel_lds, ns, false, 0, lane, nullptr, keys_ok, sortw, staged, mw);
+    } else {
         if (lane == 0) report_plain_row(a, row, p, ns);
         PCG_STAMP(6);
     }
+}
+
+// STG: the rows whose window search can run in stages (win_stageable) take a copy of the row path of their own - staged or not
+// is decided once, at the row record, and no two paths with different loads in flight meet before the row's end.
+template <bool PRE, bool STG>
+__device__ __forceinline__ void select_lane_row(const ChooseArgs &a, int row, uint32_t *area, int lane, int &keys_ok, int *sortw) {
+    const RowRec p = a.w.recs[row];
+    if constexpr (STG) {
+        if (win_stageable(a, __builtin_amdgcn_readfirstlane(p.m))) {
+            select_lane_row_body<PRE, true>(a, row, p, area, lane, keys_ok, sortw);
+            return;
+        }
+    }
+    select_lane_row_body<PRE, false>(a, row, p, area, lane, keys_ok, sortw);
+}
+template <bool PRE, bool STG>
+__device__ __forceinline__ void select_wave_row(const ChooseArgs &a, int row, uint32_t *area, int lane, int &keys_ok, int *sortw) {
+    const RowRec p = a.w.recs[row];
+    if constexpr (STG) {
+        if (win_stageable(a, __builtin_amdgcn_readfirstlane(p.m))) {
+            select_wave_row_body<PRE, true>(a, row, p, area, lane, keys_ok, sortw);
+            return;
+        }
+    }
+    select_wave_row_body<PRE, false>(a, row, p, area, lane, keys_ok, sortw);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -726,7 +974,7 @@ __device__ __forceinline__ void for_keys(const uint32_t *keys, const uint32_t *_
 }
 
 // lds: WG_KEYCAP words (keys, later the kept ids) | hist HIST_WG | cand 64 | red
-template <bool LDSK, int NW = SEL_NW>
+template <bool LDSK, int NW = SEL_NW, bool PRE = false>
 __device__ __forceinline__ void select_wg_row(const ChooseArgs &a, int row, uint32_t *keys, uint32_t *hist, uint32_t *cand,
                                               int *red, int tid, int &keys_ok, int *sortw, uint32_t *gk = nullptr,
                                               int key_cap = WG_KEYCAP /* words of `keys` */) {
@@ -749,11 +997,11 @@ __device__ __forceinline__ void select_wg_row(const ChooseArgs &a, int row, uint
     uint32_t kstar = 0xFFFFFFFFu;
     int need = 0, n_equal = 0;
     // A positive centre's minority window needs the centre's score and the sorted train-pos keys - nothing of the row.  When the
-    // keys were sorted BEFORE this launch (a.n_sort == 0: the previous step's dense launch did it on CUs it leaves idle) the
-    // group's last wave works the window out (three dependent rounds of key loads, ~2.3 us) while the others form the row's
-    // distance keys, and leaves it in LDS for the row's tail: the search is off the row's chain.
-    int *win = sortw ? sortw + 4 : nullptr;                       // (the search index's place: unused when nothing is sorted in here)
-    const bool early = !keep_all && p.m > 0 && a.n_sort == 0 && win != nullptr && NW > 1;
+    // keys were sorted BEFORE this launch (PRE: the previous step's dense launch did it on CUs it leaves idle) the
+    // group's last wave works the window out (from the workgroup's search index: two dependent rounds of key loads) while the
+    // others form the row's distance keys, and leaves it in LDS for the row's tail: the search is off the row's chain.
+    int *win = sortw ? sortw + 4 + KIDX_MAX : nullptr;            // (behind the search index)
+    const bool early = PRE && !keep_all && p.m > 0 && win != nullptr && NW > 1;
     // (a row too long for the LDS keeps its keys in global scratch, gk: written by pass 1, read back coalesced by the later passes)
     if (!keep_all) {
         // ---- 1. distance keys (-> LDS), their range ----
@@ -761,7 +1009,8 @@ __device__ __forceinline__ void select_wg_row(const ChooseArgs &a, int row, uint
         constexpr int KU1 = 16;     // pass 1 of a workgroup row: sixteen gathers in flight per lane (a 6 000-neighbour row: one round)
         const int nt1 = early ? NT - PCG_WAVE : NT;                // threads that share the key pass
         if (early && wave == NW - 1) {
-            const MinorWindow mw = minority_window(a, p.m, c, lane, nullptr);
+            wait_sorted_keys<PRE>(a, keys_ok, lane, sortw);
+            const MinorWindow mw = minority_window<PRE>(a, p.m, c, lane, sortw);
             if (lane == 0) {
                 win[0] = mw.L; win[1] = mw.R; win[2] = mw.L2; win[3] = mw.R2; win[4] = mw.tau; win[5] = mw.need_t;
             }
@@ -1009,8 +1258,12 @@ __device__ __forceinline__ void select_wg_row(const ChooseArgs &a, int row, uint
         return;
     }
     // (early: the window is in LDS since before the first barrier of the k-th selection)
-    if constexpr (LDSK) finish_row<NW>(a, row, p, c, keys, ns, false, wave, lane, red, keys_ok, sortw, early ? win : nullptr);
-    else finish_row<NW>(a, row, p, c, selbuf, ns, !sel_in_lds, wave, lane, red, keys_ok, sortw, early ? win : nullptr);
+    MinorWindow mw = {};
+    if (early) {
+        mw.L = win[0]; mw.R = win[1]; mw.L2 = win[2]; mw.R2 = win[3]; mw.tau = win[4]; mw.need_t = win[5];
+    }
+    if constexpr (LDSK) finish_row<NW, PRE>(a, row, p, c, keys, ns, false, wave, lane, red, keys_ok, sortw, early, mw);
+    else finish_row<NW, PRE>(a, row, p, c, selbuf, ns, !sel_in_lds, wave, lane, red, keys_ok, sortw, early, mw);
 }
 
 // One persistent launch selects every row of the batch, longest rows first.  The work is one queue of workgroup-sized units,
@@ -1321,9 +1574,18 @@ __device__ __forceinline__ void clf_step_body(const ClfStep c, const float *__re
 // The body of one select workgroup of NW waves (8: select_rows; 16: dense_select_kernel): blk of nblk workgroups that share
 // the selection, smem = its dynamic LDS (select_smem_bytes(key_cap, NW); key_cap >= NW * WAVE_AREA).  The label classifier's
 // step runs on SEL_NW waves whatever NW is (its sums keep their order); the other paths use all of them.
-template <int CLF, int NW = SEL_NW>
+// PRE: the train-pos keys were sorted by an earlier launch (the host: n_sort == 0) - no wait, the search index at entry, cached key
+// loads, a positive single-wave row's window search beside its own loads (STG).
+#ifndef PCG_STAGE_NW8
+#define PCG_STAGE_NW8 1
+#endif
+#ifndef PCG_STAGE_ROWS
+#define PCG_STAGE_ROWS 1
+#endif
+template <int CLF, int NW = SEL_NW, bool PRE = false>
 __device__ __forceinline__ void select_rows_body(const ChooseArgs &a, int blk, int nblk, unsigned char *smem) {
     static_assert(NW == SEL_NW || NW == 2 * SEL_NW, "8 or 16 waves");
+    constexpr bool STG = PRE && PCG_STAGE_ROWS && (NW > SEL_NW || PCG_STAGE_NW8);
     uint32_t *lds = reinterpret_cast<uint32_t *>(smem);
     uint32_t *hist = lds + a.key_cap;
     uint32_t *cand = hist + 4 * NW * PCG_WAVE;
@@ -1332,10 +1594,15 @@ __device__ __forceinline__ void select_rows_body(const ChooseArgs &a, int blk, i
     // per-relation neighbour arrays in LDS: a per-lane relation index (four short rows per wave) then costs one ds_read
     // instead of a waterfall over the kernel arguments
     const int32_t **t_indices = reinterpret_cast<const int32_t **>(red + 2 * NW + 8);
-    int *sortw = reinterpret_cast<int *>(t_indices + PCG_MAX_REL);         // 4 + KIDX_MAX words: wait_sorted_keys
+    int *sortw = reinterpret_cast<int *>(t_indices + PCG_MAX_REL);         // 4 + KIDX_MAX + WIN_WORDS words: wait_sorted_keys
     if (threadIdx.x < PCG_MAX_REL) t_indices[threadIdx.x] = a.g.indices[threadIdx.x < (unsigned)a.g.n_rel ? threadIdx.x : 0];
     const bool leader = threadIdx.x == 0;
     if (leader) sortw[0] = sortw[1] = 0;
+    // PRE: the search index, by the last wave (a short batch leaves it without a row more often than the others), behind the
+    // barrier below: nobody else waits for its loads there.  (Issuing them in front of the barrier, behind the counters' loads,
+    // measured the same.)  Rows with minority picks exist only in training, and then the host has checked the keys.
+    const bool idx_wave = PRE && (int)threadIdx.x >= (NW - 1) * PCG_WAVE;
+    const bool idx_keys = PRE && a.train_flag && a.pos_keys && a.g.n_pos > 0;
     const int n16 = (int)a.w.counters[C_N16], n4 = (int)a.w.counters[C_N4];
     const int n1 = (int)a.w.counters[C_N1], n0 = (int)a.w.counters[C_N0], na = (int)a.w.counters[C_NA];
     const int n_wg = n16 + n4, n_items = n1 + n0 + (na + 3) / 4;
@@ -1353,6 +1620,28 @@ __device__ __forceinline__ void select_rows_body(const ChooseArgs &a, int blk, i
     uint32_t *head = a.w.heads + 16 * shard;                               // (64 bytes apart)
     if (a.pending_clear && bid == 0 && leader) a.pending_clear[0] = 0u;   // the launch before has applied the deferred update
     __syncthreads();
+    if (idx_wave) {
+        if (idx_keys) {
+            const int P = a.g.n_pos, stride = key_index_stride(P), n_idx = (P + stride - 1) / stride;
+            constexpr int KIDX_PER_LANE = KIDX_MAX / PCG_WAVE;
+            uint32_t kix[KIDX_PER_LANE];
+#pragma unroll
+            for (int u = 0; u < KIDX_PER_LANE; ++u) {
+                const int t = u * PCG_WAVE + ((int)threadIdx.x & (PCG_WAVE - 1));
+                kix[u] = pk_score_bits<PRE>(a.pos_keys, t * stride < P ? t * stride : P - 1);       // (clamped: all in flight together)
+            }
+#pragma unroll
+            for (int u = 0; u < KIDX_PER_LANE; ++u) {
+                const int t = u * PCG_WAVE + ((int)threadIdx.x & (PCG_WAVE - 1));
+                if (t < n_idx) sortw[4 + t] = (int)kix[u];
+            }
+            if (((int)threadIdx.x & (PCG_WAVE - 1)) == 0) {
+                sortw[2] = n_idx;
+                sortw[3] = stride;
+            }
+        }
+        if (((int)threadIdx.x & (PCG_WAVE - 1)) == 0) __hip_atomic_store(&sortw[0], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
     // the label classifier's step for this batch (training): one workgroup, before its share of the rows
     if (CLF && bid < 0) {
         // (one workgroup, as long as the launch's longest rows, sharing its CU with two workgroups of rows: it goes first)
@@ -1423,14 +1712,14 @@ __device__ __forceinline__ void select_rows_body(const ChooseArgs &a, int blk, i
             // (a workgroup row is the launch's long pole and shares its CU with two workgroups of short rows: it goes first)
             static_assert(true, "");
             if (PCG_WG_ROW_PRIO) __builtin_amdgcn_s_setprio(PCG_WG_ROW_PRIO);
-            if (d <= a.key_cap) select_wg_row<true, NW>(a, row, lds, hist, cand, red, tid, keys_ok, sortw, nullptr, a.key_cap);      // (longer rows: select_long_rows)
+            if (d <= a.key_cap) select_wg_row<true, NW, PRE>(a, row, lds, hist, cand, red, tid, keys_ok, sortw, nullptr, a.key_cap);      // (longer rows: select_long_rows)
             if (PCG_WG_ROW_PRIO) __builtin_amdgcn_s_setprio(0);
         } else {
             const int j = wave < bs ? (u - n_wg) * bs + wave : n_items;
             if (j < n1) {
-                select_wave_row(a, __builtin_amdgcn_readfirstlane(a.w.q1[j]), area, lane, keys_ok, sortw);
+                select_wave_row<PRE, STG>(a, __builtin_amdgcn_readfirstlane(a.w.q1[j]), area, lane, keys_ok, sortw);
             } else if (j < n1 + n0) {
-                select_lane_row(a, __builtin_amdgcn_readfirstlane(a.w.q0[j - n1]), area, lane, keys_ok, sortw);
+                select_lane_row<PRE, STG>(a, __builtin_amdgcn_readfirstlane(a.w.q0[j - n1]), area, lane, keys_ok, sortw);
             } else if (j < n_items) {
                 select_four_short_rows(a, 4 * (j - n1 - n0), na, t_indices, lane);
             }
@@ -1454,10 +1743,10 @@ __device__ __forceinline__ void select_rows_body(const ChooseArgs &a, int blk, i
 // CLF: the launch carries the label classifier's step (training: pcg_choose_gather_train): 1 = feature rows of up to 256 floats
 // (one float4 chunk per lane: the datasets' 128-B rows), 2 = wider rows.  Instantiation 0 holds none of that code - nor the
 // few bytes of scratch it spills under the row paths' register budget -, so every other caller's launch is the row paths' alone.
-template <int CLF>
+template <int CLF, bool PRE>
 __global__ void __launch_bounds__(SEL_NW *PCG_WAVE) __attribute__((amdgpu_waves_per_eu(6, 8))) select_rows(const ChooseArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    select_rows_body<CLF>(a, (int)blockIdx.x, (int)gridDim.x, smem);
+    select_rows_body<CLF, SEL_NW, PRE>(a, (int)blockIdx.x, (int)gridDim.x, smem);
 }
 
 // The label classifier's step as a launch of its own (pcg_clf_step: the start of a sequence whose classifier runs two batches
@@ -1534,7 +1823,7 @@ __global__ void __launch_bounds__(LONG_NW *PCG_WAVE) select_long_rows(const Choo
 
 static size_t select_smem_bytes(int key_cap, int nw = SEL_NW) {
     return sizeof(uint32_t) * (key_cap + 4 * nw * PCG_WAVE + PCG_WAVE) + sizeof(int) * (2 * nw + 8) + sizeof(void *) * PCG_MAX_REL +   // (claim[2] = red[2 nw + 6 ..])
-           sizeof(int) * (4 + KIDX_MAX);                                                                                            // sortw
+           sizeof(int) * (4 + KIDX_MAX + WIN_WORDS);                                                                                // sortw
 }
 
 // how the in-kernel train-pos sort is shared by row_blocks workgroups (a.n_sort key groups): slices per key group, keys per
@@ -1591,8 +1880,9 @@ int launch_select_rows(const ChooseArgs &a, hipStream_t st) {
     if (big) {
         static bool attr_big = false;
         if (!attr_big) {
-            const void *ks[3] = {reinterpret_cast<const void *>(select_rows<0>), reinterpret_cast<const void *>(select_rows<1>),
-                                 reinterpret_cast<const void *>(select_rows<2>)};
+            const void *ks[6] = {reinterpret_cast<const void *>(select_rows<0, false>), reinterpret_cast<const void *>(select_rows<1, false>),
+                                 reinterpret_cast<const void *>(select_rows<2, false>), reinterpret_cast<const void *>(select_rows<0, true>),
+                                 reinterpret_cast<const void *>(select_rows<1, true>), reinterpret_cast<const void *>(select_rows<2, true>)};
             for (const void *k : ks)
                 if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return PCG_E_LAUNCH;
             attr_big = true;
@@ -1601,9 +1891,14 @@ int launch_select_rows(const ChooseArgs &a, hipStream_t st) {
     const int row_blocks = nblk - (a.clf.clf_next ? a.clf.n_wg : 0);      // (training: one of the workgroups steps the label classifier)
     const int rc = select_sort_shape(as, row_blocks);
     if (rc != PCG_OK) return rc;
-    if (a.clf.clf_next && a.g.feat_stride > 256) hipLaunchKernelGGL(select_rows<2>, dim3(nblk), dim3(SEL_NW * PCG_WAVE), smem, st, as);
-    else if (a.clf.clf_next) hipLaunchKernelGGL(select_rows<1>, dim3(nblk), dim3(SEL_NW * PCG_WAVE), smem, st, as);
-    else hipLaunchKernelGGL(select_rows<0>, dim3(nblk), dim3(SEL_NW * PCG_WAVE), smem, st, as);
+    // (the presorted instantiation: the keys were sorted by an earlier launch - nothing to sort, nothing to wait for in here)
+    const bool pre = as.n_sort == 0;
+    const int clf = !a.clf.clf_next ? 0 : a.g.feat_stride > 256 ? 2 : 1;
+    typedef void (*sel_kern_t)(const ChooseArgs);
+    const sel_kern_t kern = clf == 2 ? (pre ? select_rows<2, true> : select_rows<2, false>)
+                          : clf == 1 ? (pre ? select_rows<1, true> : select_rows<1, false>)
+                                     : (pre ? select_rows<0, true> : select_rows<0, false>);
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(SEL_NW * PCG_WAVE), smem, st, as);
     PCG_LAUNCH_CHECK();
     if (a.g.max_degree > as.key_cap) {       // rows too long for the LDS keys: their own launch (hub-heavy graphs only)
         const int64_t per_wg = a.g.max_degree;
@@ -1667,7 +1962,7 @@ int launch_select_rows(const ChooseArgs &a, hipStream_t st) {
 //                count at all, and its tiles count themselves (DenseArgs::step_counter);
 //   riders' sync none: rank_sort_body's workgroups share nothing (each ranks its 64 keys against all raw keys and stores them
 //   words        at ranks < n_pos <= sort_cap); nobody in the launch waits for them.  sync words [3 ..] are unused here.
-template <bool WLDS, int F_, int E_, int R_>
+template <bool WLDS, int F_, int E_, int R_, bool PRE>
 __global__ void __launch_bounds__(DENSE_THREADS) dense_select_kernel(const DenseArgs d, const ChooseArgs s, const int n_sel) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int n_dense = d.n_tile_blocks;
@@ -1684,7 +1979,7 @@ __global__ void __launch_bounds__(DENSE_THREADS) dense_select_kernel(const Dense
                                                             (int)blockIdx.x - n_dense - n_sel, sh, part, d.sort_raw);
         return;
     }
-    select_rows_body<1, DENSE_WAVES>(s, (int)blockIdx.x - n_dense, n_sel, smem);
+    select_rows_body<1, DENSE_WAVES, PRE>(s, (int)blockIdx.x - n_dense, n_sel, smem);
 }
 
 // Select workgroups of the fused launch for a dense batch of B rows, or 0: the step keeps its three launches.  The selection
@@ -1728,12 +2023,15 @@ int launch_dense_select(const DenseArgs &d, const ChooseArgs &a, int n_sel, hipS
     const size_t dsm = dense_smem_bytes(F, E, R, wlds), ssm = select_smem_bytes(DENSE_WAVES * WAVE_AREA, DENSE_WAVES);
     typedef void (*kern_t)(const DenseArgs, const ChooseArgs, const int);
     kern_t kern;
-    if (R == 3 && F == 32 && E == 64 && wlds) kern = dense_select_kernel<true, 32, 64, 3>;
-    else if (R == 3 && F == 25 && E == 64 && wlds) kern = dense_select_kernel<true, 25, 64, 3>;
-    else if (R == 3 && F == 32 && E == 128 && !wlds) kern = dense_select_kernel<false, 32, 128, 3>;
-    else if (R == 3 && F == 25 && E == 128 && !wlds) kern = dense_select_kernel<false, 25, 128, 3>;
-    else kern = wlds ? dense_select_kernel<true, 0, 0, 0> : dense_select_kernel<false, 0, 0, 0>;
-    static kern_t attr_done[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const bool pre = as.n_sort == 0;         // the select half's presorted instantiation (select_rows_body)
+#define PCG_DS_KERN(W, F, E, R) (pre ? dense_select_kernel<W, F, E, R, true> : dense_select_kernel<W, F, E, R, false>)
+    if (R == 3 && F == 32 && E == 64 && wlds) kern = PCG_DS_KERN(true, 32, 64, 3);
+    else if (R == 3 && F == 25 && E == 64 && wlds) kern = PCG_DS_KERN(true, 25, 64, 3);
+    else if (R == 3 && F == 32 && E == 128 && !wlds) kern = PCG_DS_KERN(false, 32, 128, 3);
+    else if (R == 3 && F == 25 && E == 128 && !wlds) kern = PCG_DS_KERN(false, 25, 128, 3);
+    else kern = wlds ? PCG_DS_KERN(true, 0, 0, 0) : PCG_DS_KERN(false, 0, 0, 0);
+#undef PCG_DS_KERN
+    static kern_t attr_done[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool seen = false;
     for (kern_t k : attr_done) seen = seen || k == kern;
     if (!seen) {

@@ -61,6 +61,14 @@ for what, msk in (("positive", pos), ("negative", ~pos)):
         sel = ran & msk & (deg > lo) & (deg <= hi)
         if sel.any():
             print(f"   {what} {tier} rows: {int(sel.sum())}, start max {st[sel, 0].max() - t0:.1f}, end max {st[sel, 6].max() - t0:.1f}, time in the row mean {np.mean(st[sel, 6] - st[sel, 0]):.2f} max {np.max(st[sel, 6] - st[sel, 0]):.2f} us")
+# the positive single-wave rows' phases: stamps 0 start, 1 distance keys, 2 k-th value, 3 kept ids, 7 the tail begins on the window
+# (behind its wait / with the staged search's loads under way), 4 window known, 5 picks written, 6 end
+sel = ran & pos & (deg <= 512) & (st[:, 7] > 0) & (st[:, 4] > 0)
+if sel.any():
+    ph = [("keys 0-1", 0, 1), ("k-th 1-2", 1, 2), ("kept 2-3", 2, 3), ("to tail 3-7", 3, 7), ("window 7-4", 7, 4), ("picks 4-5", 4, 5),
+          ("end 5-6", 5, 6)]
+    print(f"   positive single-wave rows with a tail ({int(sel.sum())}), mean us per phase: " +
+          ", ".join(f"{n} {np.mean(st[sel, b] - st[sel, a]):.2f}" for n, a, b in ph))
 order = np.flatnonzero(ran)[np.argsort(-(st[ran, 6] - t0))][:6]
 print("last rows to finish: row deg positive | start | end")
 for rr in order:
