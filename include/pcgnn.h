@@ -21,7 +21,10 @@
  * Data layout in HBM (built once per graph, resident for the whole run - mirrors
  * the frozen nn.Embedding + adj_lists the reference keeps, model_handler.py:85-87):
  *   X          float  [n_nodes, feat_stride]  row-major, feat_stride % 4 == 0,
- *                     columns feat_dim..feat_stride-1 are zero, 16-byte aligned
+ *                     columns feat_dim..feat_stride-1 are zero, 16-byte aligned.
+ *                     feat_stride <= 512: every entry point that scores the table (pcg_score_table, pcg_step_front*,
+ *                     pcg_step_scores*, the inference and explanation calls), gathers lists from it or takes a segment
+ *                     mean returns PCG_E_UNSUPPORTED for a wider one; only pcg_score_rows and pcg_gather_rows take any width
  *   indptr[r]  int64  [n_nodes + 1]           CSR row offsets of relation r
  *   indices[r] int32  [nnz_r]                 neighbour ids, ASCENDING inside a row,
  *                                             self-loops kept (utils.py:226-239)

@@ -847,11 +847,14 @@ static int front_a(const pcg_graph_desc *g, const float *W, const float *b, int6
                    const double *thresholds, const double *rho, int32_t train_flag, int32_t add_self, void *workspace,
                    int64_t list_capacity, uint32_t *status, const pcg::DeferredAdam *ad, void *stream, bool no_plan = false,
                    uint32_t *zero_word = nullptr, int64_t pos_row_base = -1, const uint8_t *touched = nullptr) {
-    if (touched && (row_ids || row_begin != 0 || g->feat_stride > 512)) return PCG_E_ARG;
     if (!g || !g->X || !W || !b || !s0_out || B < 0) return PCG_E_ARG;
+    if (touched && (row_ids || row_begin != 0)) return PCG_E_ARG;
     if (g->feat_dim < 1 || g->feat_stride < g->feat_dim || g->feat_stride % 4 != 0) return PCG_E_ARG;
     if ((reinterpret_cast<uintptr_t>(g->X) & 15u) != 0) return PCG_E_ARG;
     if (row_begin < 0 || row_end > g->n_nodes || row_begin > row_end) return PCG_E_ARG;
+    // (score_table_body / score_marked_body: a lane holds at most two float4 chunks of a row - wider rows would lose their columns
+    //  from 512 on, while pos_key_body's general loop kept them)
+    if (g->feat_stride > 512) return PCG_E_UNSUPPORTED;
     if (B == 0 && row_ids && !no_plan) return PCG_E_ARG;
     if (B == 0 && !no_plan) return pcg_score_table(g, W, b, row_begin, row_end, s0_out, stream);   // (then _b gathers its keys itself)
     pcg::ChooseArgs a;
@@ -1005,6 +1008,7 @@ int pcg_step_scores_dist(const pcg_graph_desc *g, const pcg_train_state *st, con
     if ((reinterpret_cast<uintptr_t>(g->X) & 15u) != 0) return PCG_E_ARG;
     if (row_begin < 0 || row_end > g->n_nodes || row_begin > row_end) return PCG_E_ARG;
     if (pos_keys && (pos_row_base < 0 || pos_row_base + g->n_pos > g->n_nodes || g->n_pos > pcg::RANK_MAX)) return PCG_E_ARG;
+    if (g->feat_stride > 512) return PCG_E_UNSUPPORTED;      // (score_table_body; feat_dim <= 512 alone lets a stride of 516 in)
     const int64_t n_params = pcg_dense_n_params(g->feat_dim, st->emb, g->n_rel);
     const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 3, 0);
     if (n_params < 0 || o_clf < 0) return PCG_E_ARG;

@@ -209,6 +209,7 @@ int pcg_score_table(const pcg_graph_desc *g, const float *W, const float *b, int
                     float *s0, void *stream) {
     if (pcg::check_graph_features(g) != PCG_OK || !W || !b || !s0) return PCG_E_ARG;
     if (row_begin < 0 || row_end > g->n_nodes || row_begin > row_end) return PCG_E_ARG;
+    if (g->feat_stride > 512) return PCG_E_UNSUPPORTED;      // (score_table_body: a lane holds at most two float4 chunks of a row)
     if (row_begin == row_end) return PCG_OK;
     const int64_t blocks = pcg::score_table_blocks(row_end - row_begin, g->feat_stride);
     hipLaunchKernelGGL(pcg::score_table_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
