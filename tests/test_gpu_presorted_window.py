@@ -5,7 +5,9 @@ the workgroup rows' early window - with many positive rows per launch, at the si
 
 Part 1 (select_rows, eight waves): ops.pos_sort + ops.choose_aggregate(train=True) against O.choose_sets on the same float32
 scores - exact.  Bars: sets, counts, list lengths and -1 holes exact; aggregated rows within 5e-5 (the bar of that path in
-tests/test_gpu_select_keys.py).
+tests/test_gpu_select_keys.py).  The same at the bucket-sorted sizes, 16384 .. 262145 keys (index strides of 32 .. 1024): the
+crafted centre positions, both sides of the staging switch, brackets of three probe rounds, whole-buffer windows, and runs of 100
+equal scores across the window's edge.
 Part 2 (the fused launch, sixteen waves): sequences of 3 and 4 steps with the classifier two batches ahead against the same steps
 as three launches: bit for bit."""
 import numpy as np
@@ -120,6 +122,125 @@ def test_many_positive_rows_per_launch(P, world, n_pos):
                 assert length[b] == k + m, tag                                            # kept + m slots
                 assert int((segs[b] < 0).sum()) == k + m - len(want[i]), tag              # a -1 hole per pick that is kept too
             np.testing.assert_allclose(agg, ref[batch], rtol=0, atol=AGG_TOL, err_msg=f"P {n_pos} m* {m_star} at d {d_star}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Part 1 at the bucket-sorted sizes (16384 .. 262145 keys: index strides of 32 .. 1024) and with long runs of equal scores
+# ---------------------------------------------------------------------------------------------------------------------------
+N_L = POS_BASE + max(R.LARGE_SIZES) + 200
+CENTRE_BASE_L = POS_BASE + max(R.LARGE_SIZES) + 50            # (behind the last training positive of the largest size)
+
+
+@pytest.fixture(scope="module")
+def large_world():
+    """the construction of `world` with room for 262145 training positives"""
+    X = np.random.RandomState(23).randn(N_L, FEAT).astype(np.float32)
+    deg = np.zeros(N_L, dtype=np.int64)
+    for i, (d, _) in enumerate(CENTRES):
+        deg[CENTRE_BASE_L + i] = d
+    indptr = np.zeros(N_L + 1, dtype=np.int64)
+    np.cumsum(deg, out=indptr[1:])
+    indices = np.concatenate([np.arange(d, dtype=np.int32) for d, _ in CENTRES])
+    return X, (indptr, indices), torch.from_numpy(X)
+
+
+def large_score_table(n_pos, tp, keys, centre_of_kind, seed):
+    """score_table's construction: `keys` are the sorted scores of the positives, shuffled over train_pos; centre i of kind
+    POSITIONS[j] gets centre_of_kind[j]"""
+    rng = np.random.default_rng([seed, n_pos])
+    s0 = np.zeros(N_L, dtype=np.float32)
+    s0[:POOL] = rng.uniform(0.0, float(keys[-1]) + 1.0, size=POOL).astype(np.float32)
+    s0[np.asarray(tp)] = keys[rng.permutation(n_pos)]
+    for i, (d, kind) in enumerate(CENTRES):
+        j = POSITIONS.index(kind) if kind in POSITIONS else (i + d) % len(POSITIONS)
+        s0[CENTRE_BASE_L + i] = centre_of_kind[j]
+    return s0
+
+
+def oracle_large(centres, labels, s0_t, tp, pos_s0, rho):
+    """O.choose_sets, one centre at a time; a positive centre's minority picks are looked for among R.nearest_candidates (every
+    positive at most the m-th distance away, in train_pos order) instead of among all P"""
+    pos_np, tp_np = pos_s0.numpy(), np.asarray(tp)
+    out = []
+    for i, lab in zip(centres, labels):
+        d = CENTRES[i][0]
+        c = s0_t[CENTRE_BASE_L + i:CENTRE_BASE_L + i + 1]
+        m = int(R.sample_count(d) * rho)
+        ids, sc = tp, pos_s0
+        if lab and 0 < m < len(tp):
+            cand = R.nearest_candidates(c.numpy()[0], pos_np, m)
+            ids, sc = tp_np[cand].tolist(), pos_s0[torch.from_numpy(cand)]
+        out.append(O.choose_sets(c, [lab], [range(d)], [s0_t[:d]], ids, sc, R.THR, rho, True)[0])
+    return out
+
+
+def select_large(ops, g, nodes, labels, s0, keys, rho):
+    nodes_h, labels_h = np.asarray(nodes, dtype=np.int64), np.asarray(labels, dtype=np.int64)
+    cap = int(ops.sel_capacity(g, nodes_h, labels_h, [R.THR], rho, True, False).sum()) + sum(CENTRES[v - CENTRE_BASE_L][0] for v in nodes)
+    ws = ops.ChooseWorkspace(g, len(nodes), list_capacity=cap)
+    nodes_d = torch.tensor(nodes, dtype=torch.int32, device=dev())
+    labels_d = torch.tensor(labels, dtype=torch.int32, device=dev())
+    agg, cnt = ops.choose_aggregate(g, nodes_d, labels_d, s0, keys, [R.THR], rho, True, add_self=False, ws=ws)
+    sets = ops.read_sets(g, len(nodes), ws)[0]
+    begin = ws.view(0, torch.int64, len(nodes) + 1).cpu().numpy()
+    length = ws.view(1, torch.int32, len(nodes)).cpu().numpy()
+    lst = ws.view(2, torch.int32, max(int(begin[-1]), 1)).cpu().numpy()
+    segs = [lst[begin[b]:begin[b] + length[b]] for b in range(len(nodes))]
+    ws.check()
+    return sets, agg[0].cpu().numpy(), cnt[0].cpu().numpy(), length, segs
+
+
+def run_large(P, large_world, n_pos, key_scores, centre_of_kind, cases, seed):
+    ops = P.ops
+    X, csr, Xt = large_world
+    tp = train_pos_of(n_pos)
+    g = P.DeviceGraph(X, [csr], tp, dev())
+    s0_h = large_score_table(n_pos, tp, key_scores, centre_of_kind, seed)
+    s0_t = torch.from_numpy(s0_h)
+    s0 = s0_t.to(dev())
+    keys = ops.pos_sort(g, s0)
+    pos_s0 = s0_t[tp]
+    label_of = [0 if kind.startswith("neg") else 1 for _, kind in CENTRES]
+    for m_star, d_star, rho, degrees in cases:
+        sel = [i for i, (d, _) in enumerate(CENTRES) if degrees is None or d in degrees]
+        want = oracle_large(sel, [label_of[i] for i in sel], s0_t, tp, pos_s0, rho)
+        kept = oracle_large(sel, [0] * len(sel), s0_t, tp, pos_s0, rho)
+        ref = O.sparse_aggregate(want, Xt).numpy()
+        order = list(range(len(sel)))
+        rev = order[::-1]
+        for batch in (order, rev + rev[::3] + order[:2]):      # (the two row orders of test_many_positive_rows_per_launch)
+            nodes = [CENTRE_BASE_L + sel[j] for j in batch]
+            labels = [label_of[sel[j]] for j in batch]
+            sets, agg, cnt, length, segs = select_large(ops, g, nodes, labels, s0, keys, rho)
+            for b, j in enumerate(batch):
+                d, kind = CENTRES[sel[j]]
+                k = R.sample_count(d)
+                m = R.row_m(d, rho, n_pos) if labels[b] else 0
+                tag = f"P {n_pos} m* {m_star} at d {d_star}: centre d {d} {kind} m {m}"
+                assert len(kept[j]) == k and kept[j] <= want[j] and len(want[j]) <= k + m, tag
+                assert sets[b] == want[j], f"{tag}: {sorted(sets[b] ^ want[j])[:8]}"
+                assert cnt[b] == len(want[j]), tag
+                assert length[b] == k + m, tag                                            # kept + m slots
+                assert int((segs[b] < 0).sum()) == k + m - len(want[j]), tag              # a -1 hole per pick that is kept too
+            np.testing.assert_allclose(agg, ref[batch], rtol=0, atol=AGG_TOL, err_msg=f"P {n_pos} m* {m_star} at d {d_star}")
+
+
+@pytest.mark.parametrize("n_pos", R.LARGE_SIZES)
+def test_many_positive_rows_per_launch_large(P, large_world, n_pos):
+    """the crafted centre positions, both sides of the staging switch stride - 1 + m <= 4096 and a bracket of three probe rounds
+    at every index stride from 32 to 1024 (tests/test_presorted_window_host.py: which boundaries each size reaches)"""
+    cs = R.centre_scores(n_pos)
+    run_large(P, large_world, n_pos, R.key_scores(n_pos), [cs[kind] for kind in POSITIONS], R.large_cases(n_pos), 24)
+
+
+@pytest.mark.parametrize("n_pos,run", [(n, "runs") for n in R.TIE_SIZES] + [(R.TIE_SIZES[0], "all_equal")])
+def test_ties_across_the_window_edge_large(P, large_world, n_pos, run):
+    """runs of 100 equal scores under strides of 64 and 512 (and, at the smaller size - the oracle sorts every key there - one
+    run of all the keys): the m-th distance falls inside a run left of the centre, right of it, or inside one on either side; of
+    more than 64 ties the earliest in train_pos are taken"""
+    length = R.TIE_RUN if run == "runs" else n_pos
+    cs = R.tie_centre_scores(n_pos, length)
+    run_large(P, large_world, n_pos, R.tie_key_scores(n_pos, length), [cs[kind] for kind in R.TIE_KINDS], R.tie_cases(n_pos), 25)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -132,3 +132,111 @@ def test_m_values():
     assert R.m_values(17) == [1, 2, 16, 17, 18]
     assert R.m_values(8193) == [1, 2, 47, 48, 49, 8192, 8193, 8194]
     assert R.index_stride(64) + 48 == 64 and R.index_stride(64) + 49 > 64
+
+
+# ---- the bucket-sorted sizes: strides of 32 .. 1024 ------------------------------------------------------------------------------
+def test_large_index_shape():
+    assert [R.index_stride(P) for P in R.LARGE_SIZES] == R.LARGE_STRIDES
+    for P in R.LARGE_SIZES:
+        stride, n_idx = R.index_shape(P)
+        print(f"P {P}: stride {stride}, {n_idx} index entries")
+        assert 1 <= n_idx <= R.KIDX_MAX and (n_idx - 1) * stride < P <= n_idx * stride
+    assert R.index_shape(16384) == (32, 512) and R.index_shape(16385) == (64, 257) and R.index_shape(262145) == (1024, 257)
+    assert {R.index_stride(P) for P in R.TIE_SIZES} == {64, 512}
+
+
+@pytest.mark.parametrize("P", R.LARGE_SIZES)
+def test_large_centre_positions_are_what_they_say(P):
+    s = R.key_scores(P)
+    assert np.all(np.diff(s.astype(np.float64)) == 4 * R.UNIT)                  # exact in float32 up to 262145 keys
+    stride, n_idx = R.index_shape(P)
+    c = R.centre_scores(P)
+    assert c["below"] < s[0] and c["above"] > s[-1] and c["on_key"] in s and c["first"] == s[0] and c["last"] == s[-1]
+    at = int(np.flatnonzero(s == c["on_index"])[0])
+    assert at % stride == 0 and at > 0
+    lo_i = int((s < c["between"]).sum())
+    assert c["between"] not in s and (lo_i - 1) // stride == lo_i // stride and lo_i % stride != 0
+    assert len(set(np.float32(v) for v in c.values())) == len(c)
+
+
+@pytest.mark.parametrize("P", R.LARGE_SIZES)
+def test_large_cases_reach_both_sides_of_the_staging_switch(P):
+    """every row of the GPU test's launches at a large size: the bracket holds the window's start; the rows of degree d_star
+    get m_star; the longest single-wave row and a lane row sit on both sides of stride - 1 + m <= 4096; a bracket of three
+    probe rounds occurs; at LARGE_WHOLE the whole buffer is a window"""
+    s = R.key_scores(P)
+    stride, n_idx = R.index_shape(P)
+    centres = R.centre_scores(P)
+    seen = set()
+    for m_star, d_star, rho, degrees in R.large_cases(P):
+        assert R.row_m(d_star, rho, P) == min(m_star, P)
+        for d in degrees or R.DEGREES:
+            m = R.row_m(d, rho, P)
+            if m >= P:
+                seen.add(("all", d))
+                continue
+            if m == 0:
+                continue
+            for name, c in centres.items():
+                lo_min, lo_max, t = R.bracket(s, c, m)
+                lo = window_start_fast(s, c, m)
+                assert 0 <= lo_min <= lo <= lo_max <= P - m, (P, m, name, lo_min, lo, lo_max)
+                w = lo_max - lo_min
+                assert w <= stride - 1 + m
+                assert w <= R.STAGE_MAX or not R.stageable(P, m)
+                seen.add((name, "t0" if t == 0 else "tn" if t == n_idx else "mid"))
+                if d <= 512:
+                    seen.add(("staged" if R.stageable(P, m) else "plain", d <= 64, w))
+                seen.add("three_rounds" if w > R.STAGE_MAX else "two_rounds" if w > 64 else "one_round")
+    assert ("below", "t0") in seen and ("above", "tn") in seen and ("on_index", "mid") in seen and ("between", "mid") in seen
+    for lane_row in (False, True):
+        # an interior centre's bracket on either side of the switch: exactly 4096 wide and staged, 4097 wide and not
+        assert ("staged", lane_row, R.STAGE_MAX) in seen and ("plain", lane_row, R.STAGE_MAX + 1) in seen, lane_row
+    assert {"one_round", "two_rounds", "three_rounds"} <= seen
+    assert (("all", 130) in seen) == (P == R.LARGE_WHOLE)
+    print(f"P {P}: stride {stride}, m* {[c[0] for c in R.large_cases(P)]}")
+
+
+@pytest.mark.parametrize("P", R.TIE_SIZES)
+def test_tie_cases_put_more_than_a_wave_of_ties_on_the_window_edge(P):
+    """the runs table: windows whose m-th distance lies inside a run on the left only, on the right only, and on both sides -
+    more than 64 ties, not all of them taken (the bisection over train_pos positions); the brackets hold the start"""
+    for run in (R.TIE_RUN, P):
+        s = R.tie_key_scores(P, run)
+        assert np.all(np.diff(s) >= 0)
+        centres = R.tie_centre_scores(P, run)
+        assert list(centres) == R.TIE_KINDS
+        sides = set()
+        for m_star, d_star, rho, degrees in R.tie_cases(P, min(run, R.TIE_RUN)):
+            for d in degrees or R.DEGREES:
+                m = R.row_m(d, rho, P)
+                if m == 0 or m >= P:
+                    continue
+                for name, c in centres.items():
+                    lo_min, lo_max, _ = R.bracket(s, c, m)
+                    assert lo_min <= window_start_fast(s, c, m) <= lo_max, (P, run, m, name)
+                    n_lt, T, need_t = R.tie_shape(s, c, m)
+                    if T > 64 and need_t < T:
+                        dist = np.abs(np.float32(c) - s)
+                        ks = np.partition(dist, m - 1)[m - 1]
+                        left, right = bool(((dist == ks) & (s < c)).any()), bool(((dist == ks) & (s >= c)).any())
+                        sides.add((left, right, R.stageable(P, m)))
+        if run == P:
+            assert sides                                                        # every key is a tie, on one side of the centre
+        else:
+            assert {(l, r) for l, r, _ in sides} == {(True, False), (False, True), (True, True)}
+            assert any(stg for _, _, stg in sides) and any(not stg for _, _, stg in sides)
+
+
+def test_nearest_candidates_hold_every_pick():
+    """the shortened list the large GPU cases hand the oracle: a stable sort of the candidates' distances picks what a stable
+    sort of all distances picks, ties by position included"""
+    rs = np.random.RandomState(4)
+    s = (rs.randint(0, 300, size=5000) * R.UNIT).astype(np.float32)             # many equal scores
+    for c in (np.float32(0.0), np.float32(150 * R.UNIT), np.float32(150.5 * R.UNIT), np.float32(1.0)):
+        dist = np.abs(c - s)
+        full = np.argsort(dist, kind="stable")
+        for m in (1, 2, 63, 64, 65, 1000, 4999):
+            cand = R.nearest_candidates(c, s, m)
+            assert np.all(np.diff(cand) > 0)
+            assert np.array_equal(cand[np.argsort(dist[cand], kind="stable")[:m]], full[:m]), (float(c), m)
