@@ -67,8 +67,8 @@ static inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 struct CarveSizes {
     int64_t plan_bytes, data_bytes;
 };
-static inline CarveSizes carve(const pcg_graph_desc *g, int32_t B, int64_t list_capacity, unsigned char *plan_base,
-                               unsigned char *data_base, Workspace *w) {
+static inline CarveSizes carve(const pcg_graph_desc *g, int32_t B, int64_t list_capacity, unsigned char *plan_base = nullptr,
+                               unsigned char *data_base = nullptr, Workspace *w = nullptr) {
     const int64_t rows = (int64_t)g->n_rel * B;
     const int64_t chunk_cap = list_capacity / CHUNK + rows + 1;
     // key scratch: only graphs with rows beyond select_long_rows' LDS key capacity need it; max_degree entries for each of its
@@ -121,7 +121,7 @@ static inline CarveSizes carve(const pcg_graph_desc *g, int32_t B, int64_t list_
 // plan == null: the single-buffer layout [plan | data] at `workspace`; else the plan part at `plan`, the data part at `workspace`
 static inline int64_t carve1(const pcg_graph_desc *g, int32_t B, int64_t list_capacity, unsigned char *workspace, Workspace *w,
                              unsigned char *plan = nullptr) {
-    const CarveSizes sz = carve(g, B, list_capacity, nullptr, nullptr, nullptr);
+    const CarveSizes sz = carve(g, B, list_capacity);
     if (plan) carve(g, B, list_capacity, plan, workspace, w);
     else carve(g, B, list_capacity, workspace, workspace ? workspace + sz.plan_bytes : nullptr, w);
     return sz.plan_bytes + sz.data_bytes;
@@ -248,8 +248,62 @@ struct SideJob {
     int32_t n_key_blocks, n_score_blocks;
     uint32_t *zero_word;       // the select kernel's arrival counter, zeroed for its next launch
 };
-int launch_gather_train(const float *X, int32_t feat_dim, int32_t feat_stride, int64_t table_rows, const int32_t *cnt,
-                        const pcg_graph_desc *g, int32_t B, const Workspace &w, float *agg, int32_t agg_stride, uint32_t *status,
+
+// ---- host side only: what the entry points of choose.hip / gather.hip were asked for, said once -----------------------------------
+struct FeatTable {
+    const float *X;
+    int32_t feat_dim, feat_stride;
+    int64_t rows;              // a list entry outside [0, rows) is not gathered
+};
+static inline FeatTable feat_table(const pcg_graph_desc *g) { return {g->X, g->feat_dim, g->feat_stride, g->n_nodes}; }
+struct GatherOut {
+    float *agg;                // [n_rows, agg_stride]
+    int32_t agg_stride, norm;
+    const int32_t *cnt;
+    uint32_t *status;
+};
+// A lane holds at most two float4 chunks of a row (512 floats).  The order of the answers is part of the ABI's behaviour: the
+// gathers judge the width before the alignment and take any feat_dim, the score fronts refuse every argument error first
+enum TableUse { TABLE_GATHER, TABLE_SCORE };
+static inline bool table_too_wide(const FeatTable &t) { return t.feat_stride > 512; }
+static inline int check_table(const FeatTable &t, TableUse use, int32_t agg_stride = INT32_MAX) {
+    const bool misaligned = (reinterpret_cast<uintptr_t>(t.X) & 15u) != 0;
+    if (t.feat_stride % 4 != 0 || t.feat_stride < t.feat_dim || agg_stride < t.feat_dim) return PCG_E_ARG;
+    if (use == TABLE_SCORE && (t.feat_dim < 1 || misaligned)) return PCG_E_ARG;
+    if (table_too_wide(t)) return PCG_E_UNSUPPORTED;
+    return misaligned ? PCG_E_ARG : PCG_OK;
+}
+
+// a selection call: the batch and the settings as the ABI's own structs, the scores it selects by, what a *_planned call may add.
+// s0 / pos_keys are written through ONLY by the fronts (front_a / front_b / train_parts' riders); batch / ws may be null ONLY
+// for a front that plans nothing (FrontOpts::no_plan), which reads neither
+struct SelectCall {
+    const pcg_graph_desc *g;
+    const pcg_batch *batch;    // ids (`nodes`), labels, cnt, plan (null: inside the workspace), B
+    const pcg_select_ws *ws;   // thresholds, rho, workspace, status, list_capacity, add_self
+    int32_t train_flag;
+    float *s0;                 // read by the selection; written by the calls that score into it
+    const float *center_s0;
+    uint64_t *pos_keys;        // [sorted half | raw half]; read by the selection, written by the calls that form or sort the keys
+    uint32_t *sync_words;      // non-null: the raw half holds the UNSORTED keys; the select kernel sorts them ([3]: zero on entry), clears [1]
+    int64_t center_off;
+};
+
+// the unsorted half of a train-pos key buffer, and the workgroups that form the keys from the positives' feature rows
+template <typename K>
+static inline K *raw_half(K *pos_keys, int32_t n_pos) { return pos_keys + pcg_pos_sort_capacity(n_pos) / 2; }
+static inline int key_blocks(int32_t n_pos, int32_t feat_stride) {
+    const int rows_per_block = 4 * (PCG_WAVE / lanes_per_row(feat_stride)), n = (n_pos + rows_per_block - 1) / rows_per_block;
+    return n > 256 ? 256 : n;
+}
+static inline int clf_workgroups(int32_t B) { return (B + 1023) / 1024 > 8 ? 8 : (B + 1023) / 1024; }   // <= 1024 rows each, at most 8
+// the workspace of a call (plan == null: the single-buffer layout [plan | data] at `workspace`)
+static inline Workspace carve_for(const pcg_graph_desc *g, int32_t B, int64_t list_capacity, void *workspace, const void *plan) {
+    Workspace w;
+    carve1(g, B, list_capacity, static_cast<unsigned char *>(workspace), &w, static_cast<unsigned char *>(const_cast<void *>(plan)));
+    return w;
+}
+int launch_gather_train(const FeatTable &t, const GatherOut &out, const pcg_graph_desc *g, int32_t B, const Workspace &w,
                         const SideJob &side, hipStream_t st);
 
 }  // namespace pcg

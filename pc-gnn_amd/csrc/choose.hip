@@ -663,12 +663,12 @@ int64_t pcg_choose_workspace_bytes(const pcg_graph_desc *g, int32_t B, int64_t l
 
 int64_t pcg_choose_plan_bytes(const pcg_graph_desc *g, int32_t B, int64_t list_capacity) {
     if (!g || B < 0 || list_capacity < 0 || list_capacity >= (1ll << 31)) return PCG_E_ARG;
-    return pcg::carve(g, B, list_capacity, nullptr, nullptr, nullptr).plan_bytes;
+    return pcg::carve(g, B, list_capacity).plan_bytes;
 }
 
 int64_t pcg_choose_data_bytes(const pcg_graph_desc *g, int32_t B, int64_t list_capacity) {
     if (!g || B < 0 || list_capacity < 0 || list_capacity >= (1ll << 31)) return PCG_E_ARG;
-    return pcg::carve(g, B, list_capacity, nullptr, nullptr, nullptr).data_bytes;
+    return pcg::carve(g, B, list_capacity).data_bytes;
 }
 
 int64_t pcg_choose_workspace_offset(const pcg_graph_desc *g, int32_t B, int64_t list_capacity, int32_t which) {
@@ -701,82 +701,64 @@ int64_t pcg_sel_capacity_row(int64_t deg, double threshold, double rho, int32_t 
     return cap + (add_self ? 1 : 0);
 }
 
-static int choose_args(pcg::ChooseArgs &a, const pcg_graph_desc *g, const int32_t *nodes, const int32_t *labels, int32_t B,
-                       const float *s0, const float *center_s0, const uint64_t *pos_keys, const double *thresholds,
-                       const double *rho, int32_t train_flag, int32_t add_self, int32_t *cnt, void *workspace,
-                       int64_t list_capacity, uint32_t *status, bool plan_only = false, const void *plan = nullptr) {
-    if (!nodes || !thresholds || !workspace || !status) return PCG_E_ARG;
-    if (!plan_only && !s0) return PCG_E_ARG;      // (the plan reads neither the scores nor the sorted keys)
-    if (list_capacity < 1 || list_capacity >= (1ll << 31)) return PCG_E_ARG;
-    if (train_flag && !rho) return PCG_E_ARG;
+// A plain-argument entry point says its batch {ids, labels, cnt, plan, B} and its settings {thresholds, rho, workspace, status,
+// list_capacity, add_self} as the ABI's structs on its stack.  No batch, no ws: a front that only scores (FrontOpts::no_plan)
+static pcg::SelectCall select_call(const pcg_graph_desc *g, int32_t train_flag, const float *s0, const uint64_t *pos_keys,
+                                   const pcg_batch *batch = nullptr, const pcg_select_ws *ws = nullptr, const float *center_s0 = nullptr) {
+    pcg::SelectCall c = {};
+    c.g = g; c.batch = batch; c.ws = ws; c.train_flag = train_flag;
+    c.s0 = const_cast<float *>(s0); c.pos_keys = const_cast<uint64_t *>(pos_keys); c.center_s0 = center_s0;
+    return c;
+}
+
+// the in-kernel sort of the train positives (ChooseArgs): unsorted keys in pos_keys' raw half, sorted into its first half
+static void wire_in_kernel_sort(pcg::ChooseArgs &a, uint64_t *pos_keys, uint32_t *sync_words, int32_t n_pos) {
+    a.sort_out = pos_keys; a.raw_keys = pcg::raw_half(pos_keys, n_pos);
+    a.sort_cap = (int32_t)(a.raw_keys - pos_keys); a.n_sort = (n_pos + PCG_WAVE - 1) / PCG_WAVE;
+    a.sort_done = sync_words + 3; a.rank_acc = sync_words + 4; a.group_ticket = sync_words + 4 + pcg::RANK_MAX;
+}
+
+// plan_only: the launch plans and does not select: scores, sorted keys and counts are not asked for and not handed on
+// (the caller has checked c.g, c.batch, c.ws)
+static int choose_args(pcg::ChooseArgs &a, const pcg::SelectCall &c, bool plan_only = false) {
+    const pcg_graph_desc *g = c.g;
+    const pcg_batch &b = *c.batch;
+    const pcg_select_ws &ws = *c.ws;
+    if (!b.ids || !ws.thresholds || !ws.workspace || !ws.status) return PCG_E_ARG;
+    if (!plan_only && !c.s0) return PCG_E_ARG;
+    if (ws.list_capacity < 1 || ws.list_capacity >= (1ll << 31)) return PCG_E_ARG;
+    if (c.train_flag && !ws.rho) return PCG_E_ARG;
     if (g->n_rel < 1 || g->n_rel > PCG_MAX_REL) return PCG_E_ARG;
-    if (train_flag && (!labels || (!plan_only && g->n_pos > 0 && (!pos_keys || !g->train_pos)))) return PCG_E_ARG;
+    if (c.train_flag && (!b.labels || (!plan_only && g->n_pos > 0 && (!c.pos_keys || !g->train_pos)))) return PCG_E_ARG;
     for (int r = 0; r < g->n_rel; ++r)
         if (!g->indptr[r] || !g->indices[r]) return PCG_E_ARG;
+    a = pcg::ChooseArgs{};
     a.g = *g;
-    a.nodes = nodes;
-    a.labels = labels;
-    a.B = B;
-    a.s0 = s0;
-    a.center_s0 = center_s0;
-    a.center_off = 0;
-    a.pos_keys = pos_keys;
-    for (int r = 0; r < PCG_MAX_REL; ++r) a.thr[r] = r < g->n_rel ? thresholds[r] : 0.0;
-    for (int r = 0; r < PCG_MAX_REL; ++r) a.rho[r] = (r < g->n_rel && rho) ? rho[r] : 0.0;
-    a.train_flag = train_flag;
-    a.add_self = add_self;
-    a.cnt = cnt;
-    a.status = status;
-    a.stamps = pcg::g_stamps;
-    a.raw_keys = nullptr;
-    a.sort_out = nullptr;
-    a.sort_done = a.rank_acc = a.group_ticket = nullptr;
-    a.n_sort = a.sort_cap = a.sort_slices = a.sort_slice_len = 0;
-    a.pending_clear = nullptr;
-    a.clf.clf_next = nullptr;
-    a.clf.clf_out = nullptr;
-    a.clf.count_step = nullptr;
-    a.clf.nodes = a.clf.labels = nullptr;
-    a.clf.B = a.clf.t_ahead = 0;
-    a.n_wg_units = 0;
-    pcg::carve1(g, B, list_capacity, static_cast<unsigned char *>(workspace), &a.w,
-                static_cast<unsigned char *>(const_cast<void *>(plan)));
+    a.nodes = b.ids; a.labels = b.labels; a.B = b.B;
+    if (!plan_only) {
+        a.s0 = c.s0; a.center_s0 = c.center_s0; a.pos_keys = c.pos_keys;
+        a.cnt = b.cnt;
+    }
+    for (int r = 0; r < g->n_rel; ++r) a.thr[r] = ws.thresholds[r];
+    for (int r = 0; r < g->n_rel && ws.rho; ++r) a.rho[r] = ws.rho[r];
+    a.train_flag = c.train_flag; a.add_self = ws.add_self;
+    a.status = ws.status; a.stamps = pcg::g_stamps;
+    a.w = pcg::carve_for(g, b.B, ws.list_capacity, ws.workspace, b.plan);
     return PCG_OK;
 }
 
-// what a *_planned call may add: where the plan lives (null: inside `workspace`), and the in-kernel train-pos sort
-struct PlannedExtra {
-    const void *plan = nullptr;
-    uint32_t *sync_words = nullptr;     // non-null: pos_keys' scratch half holds the UNSORTED keys (pcg_step_scores_train); the
-                                        // select kernel sorts them itself ([3] = arrival counter, zero on entry) and clears [1]
-    int64_t center_off = 0;
-};
-
-static int choose_select(bool planned, const pcg_graph_desc *g, const int32_t *nodes, const int32_t *labels, int32_t B,
-                         const float *s0, const float *center_s0, const uint64_t *pos_keys, const double *thresholds,
-                         const double *rho, int32_t train_flag, int32_t add_self, int32_t *cnt, void *workspace,
-                         int64_t list_capacity, uint32_t *status, void *stream, const PlannedExtra &x = PlannedExtra()) {
-    if (!g || B < 0) return PCG_E_ARG;
-    if (B == 0) return PCG_OK;  // empty trailing batch (model_handler.py:134 produces one): nothing to do
-    if (!cnt) return PCG_E_ARG;
-    if (x.plan && !planned) return PCG_E_ARG;
+static int choose_select(bool planned, const pcg::SelectCall &c, void *stream) {
+    if (!c.g || c.batch->B < 0) return PCG_E_ARG;
+    if (c.batch->B == 0) return PCG_OK;  // empty trailing batch (model_handler.py:134 produces one): nothing to do
+    if (!c.batch->cnt) return PCG_E_ARG;
+    if (c.batch->plan && !planned) return PCG_E_ARG;
     pcg::ChooseArgs a;
-    const int rc = choose_args(a, g, nodes, labels, B, s0, center_s0, pos_keys, thresholds, rho, train_flag, add_self, cnt,
-                               workspace, list_capacity, status, false, x.plan);
+    const int rc = choose_args(a, c);
     if (rc != PCG_OK) return rc;
-    a.center_off = x.center_off;
-    if (x.sync_words) {
-        a.pending_clear = x.sync_words + 1;
-        if (train_flag && g->n_pos > 0 && g->n_pos <= pcg::RANK_MAX) {
-            const int64_t cap = pcg_pos_sort_capacity(g->n_pos) / 2;
-            a.sort_out = const_cast<uint64_t *>(pos_keys);
-            a.raw_keys = pos_keys + cap;
-            a.sort_cap = (int32_t)cap;
-            a.n_sort = (g->n_pos + PCG_WAVE - 1) / PCG_WAVE;
-            a.sort_done = x.sync_words + 3;
-            a.rank_acc = x.sync_words + 4;
-            a.group_ticket = x.sync_words + 4 + pcg::RANK_MAX;
-        }
+    a.center_off = c.center_off;
+    if (c.sync_words) {
+        a.pending_clear = c.sync_words + 1;
+        if (c.train_flag && c.g->n_pos > 0 && c.g->n_pos <= pcg::RANK_MAX) wire_in_kernel_sort(a, c.pos_keys, c.sync_words, c.g->n_pos);
     }
     return pcg::launch_select(a, static_cast<hipStream_t>(stream), planned);
 }
@@ -785,8 +767,9 @@ int pcg_choose_select(const pcg_graph_desc *g, const int32_t *nodes, const int32
                       const float *center_s0, const uint64_t *pos_keys, const double *thresholds, const double *rho,
                       int32_t train_flag, int32_t add_self, int32_t *cnt, void *workspace, int64_t list_capacity,
                       uint32_t *status, void *stream) {
-    return choose_select(false, g, nodes, labels, B, s0, center_s0, pos_keys, thresholds, rho, train_flag, add_self, cnt,
-                         workspace, list_capacity, status, stream);
+    const pcg_batch batch = {nodes, labels, cnt, nullptr, B};
+    const pcg_select_ws ws = {thresholds, rho, workspace, status, list_capacity, add_self};
+    return choose_select(false, select_call(g, train_flag, s0, pos_keys, &batch, &ws, center_s0), stream);
 }
 
 int pcg_choose_select_planned(const pcg_graph_desc *g, const int32_t *nodes, const int32_t *labels, int32_t B,
@@ -795,12 +778,11 @@ int pcg_choose_select_planned(const pcg_graph_desc *g, const int32_t *nodes, con
                               const void *plan, int64_t list_capacity, uint32_t *status, uint32_t *sync_words,
                               int64_t center_id_offset, void *stream) {
     if (center_id_offset < 0 || (center_id_offset > 0 && center_s0)) return PCG_E_ARG;
-    PlannedExtra x;
-    x.sync_words = sync_words;
-    x.center_off = center_id_offset;
-    x.plan = plan;
-    return choose_select(true, g, nodes, labels, B, s0, center_s0, pos_keys, thresholds, rho, train_flag, add_self, cnt,
-                         workspace, list_capacity, status, stream, x);
+    const pcg_batch batch = {nodes, labels, cnt, plan, B};
+    const pcg_select_ws ws = {thresholds, rho, workspace, status, list_capacity, add_self};
+    pcg::SelectCall c = select_call(g, train_flag, s0, pos_keys, &batch, &ws, center_s0);
+    c.sync_words = sync_words; c.center_off = center_id_offset;
+    return choose_select(true, c, stream);
 }
 
 /* The plans of all batches of an epoch (or of one batch: n_total <= B): ONE launch per epoch, off every step's critical path. */
@@ -821,14 +803,14 @@ int pcg_plan_epochs(const pcg_graph_desc *g, const int32_t *nodes, const int32_t
     if ((int64_t)slots_per_epoch * n_epochs > (1 << 20)) return PCG_E_ARG;
     const int n_slots = slots_per_epoch * n_epochs;
     const int B_tail = n_total - (slots_per_epoch - 1) * B;
-    if (n_slots > 1 && plan_stride < pcg::carve(g, B, list_capacity, nullptr, nullptr, nullptr).plan_bytes) return PCG_E_ARG;
-    // (the data part is not touched by the plan: any non-null base will do for the argument check)
+    if (n_slots > 1 && plan_stride < pcg::carve(g, B, list_capacity).plan_bytes) return PCG_E_ARG;
+    // (the data part is not touched by the plan: any non-null base will do for the argument check - `plans` is both)
+    const pcg_batch full_batch = {nodes, labels, nullptr, plans, B}, tail_batch = {nodes, labels, nullptr, plans, B_tail};
+    const pcg_select_ws ws = {thresholds, rho, plans, status, list_capacity, add_self};
     pcg::ChooseArgs full, tail;
-    int rc = choose_args(full, g, nodes, labels, B, nullptr, nullptr, nullptr, thresholds, rho, train_flag, add_self, nullptr, plans,
-                         list_capacity, status, true, plans);
+    int rc = choose_args(full, select_call(g, train_flag, nullptr, nullptr, &full_batch, &ws), true);
     if (rc != PCG_OK) return rc;
-    rc = choose_args(tail, g, nodes, labels, B_tail, nullptr, nullptr, nullptr, thresholds, rho, train_flag, add_self, nullptr, plans,
-                     list_capacity, status, true, plans);
+    rc = choose_args(tail, select_call(g, train_flag, nullptr, nullptr, &tail_batch, &ws), true);
     if (rc != PCG_OK) return rc;
     const int nb_full = (g->n_rel * B + pcg::PLAN_THREADS - 1) / pcg::PLAN_THREADS;
     const int tail_b = B_tail == B ? -1 : slots_per_epoch - 1;
@@ -840,49 +822,46 @@ int pcg_plan_epochs(const pcg_graph_desc *g, const int32_t *nodes, const int32_t
     return PCG_OK;
 }
 
-/* first half: class-0 logits of rows [row_begin, row_end) -> s0_out[row]  ||  plan pass 1  (|| a deferred Adam update) */
-// no_plan: the launch is [train-pos keys || deferred Adam || score pass] only (the batch's plan was made elsewhere: pcg_plan_batches)
-static int front_a(const pcg_graph_desc *g, const float *W, const float *b, int64_t row_begin, int64_t row_end,
-                   float *s0_out, const int32_t *row_ids, uint64_t *pos_keys, const int32_t *nodes, const int32_t *labels, int32_t B,
-                   const double *thresholds, const double *rho, int32_t train_flag, int32_t add_self, void *workspace,
-                   int64_t list_capacity, uint32_t *status, const pcg::DeferredAdam *ad, void *stream, bool no_plan = false,
-                   uint32_t *zero_word = nullptr, int64_t pos_row_base = -1, const uint8_t *touched = nullptr) {
-    if (!g || !g->X || !W || !b || !s0_out || B < 0) return PCG_E_ARG;
-    if (touched && (row_ids || row_begin != 0)) return PCG_E_ARG;
-    if (g->feat_dim < 1 || g->feat_stride < g->feat_dim || g->feat_stride % 4 != 0) return PCG_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(g->X) & 15u) != 0) return PCG_E_ARG;
-    if (row_begin < 0 || row_end > g->n_nodes || row_begin > row_end) return PCG_E_ARG;
+struct FrontOpts {                             // what a score / key front covers besides the table itself
+    int64_t row_begin = 0, row_end = 0;        // the rows scored: s0[row], or s0[row_ids[row]]
+    const int32_t *row_ids = nullptr;
+    int64_t pos_row_base = -1;                 // >= 0: train positive i is table row pos_row_base + i (else row train_pos[i])
+    const uint8_t *touched = nullptr;          // byte map of the rows to score, or null: all of them (the whole table only, no row_ids)
+    uint32_t *zero_word = nullptr;             // device word the launch zeroes (the select kernel's arrival counter), or null
+    const pcg::DeferredAdam *ad = nullptr;     // an update that rides along, or null
+    bool no_plan = false;                      // the batch's plan was made elsewhere (pcg_plan_batches): no batch, no plan pass
+};
+
+/* first half: class-0 logits of rows [row_begin, row_end) -> c.s0[row]  ||  plan pass 1  (|| a deferred Adam update) */
+static int front_a(const pcg::SelectCall &c, const float *W, const float *b, const FrontOpts &o, void *stream) {
+    const pcg_graph_desc *g = c.g;
+    const int32_t B = o.no_plan ? 0 : c.batch->B;
+    if (!g || !g->X || !W || !b || !c.s0 || B < 0) return PCG_E_ARG;
+    if (o.touched && (o.row_ids || o.row_begin != 0)) return PCG_E_ARG;
+    if (o.row_begin < 0 || o.row_end > g->n_nodes || o.row_begin > o.row_end) return PCG_E_ARG;
     // (score_table_body / score_marked_body: a lane holds at most two float4 chunks of a row - wider rows would lose their columns
     //  from 512 on, while pos_key_body's general loop kept them)
-    if (g->feat_stride > 512) return PCG_E_UNSUPPORTED;
-    if (B == 0 && row_ids && !no_plan) return PCG_E_ARG;
-    if (B == 0 && !no_plan) return pcg_score_table(g, W, b, row_begin, row_end, s0_out, stream);   // (then _b gathers its keys itself)
-    pcg::ChooseArgs a;
-    if (no_plan) {
-        a = pcg::ChooseArgs();
-        a.g = *g;
-        a.B = 0;
-    } else {
-        const int rc = choose_args(a, g, nodes, labels, B, nullptr, nullptr, nullptr, thresholds, rho, train_flag, add_self, nullptr,
-                                   workspace, list_capacity, status, true);
-        if (rc != PCG_OK) return rc;
-    }
-    a.sort_done = zero_word;                 // (front_a_kernel zeroes it: the select kernel's arrival counter)
+    int rc = pcg::check_table(pcg::feat_table(g), pcg::TABLE_SCORE);
+    if (rc != PCG_OK) return rc;
+    if (B == 0 && o.row_ids && !o.no_plan) return PCG_E_ARG;
+    if (B == 0 && !o.no_plan) return pcg_score_table(g, W, b, o.row_begin, o.row_end, c.s0, stream);   // (then _b gathers its keys itself)
+    pcg::ChooseArgs a = {};
+    a.g = *g;                                // (no_plan: nothing else, B = 0)
+    rc = o.no_plan ? PCG_OK : choose_args(a, c, true);
+    if (rc != PCG_OK) return rc;
+    a.sort_done = o.zero_word;               // (front_a_kernel zeroes it: the select kernel's arrival counter)
     const int rows = g->n_rel * B;
-    pcg::PlanTotals *tot = no_plan ? nullptr : reinterpret_cast<pcg::PlanTotals *>(a.w.plan_totals);
+    pcg::PlanTotals *tot = o.no_plan ? nullptr : reinterpret_cast<pcg::PlanTotals *>(a.w.plan_totals);
     const int n_count = (rows + pcg::FRONT_COUNT_THREADS - 1) / pcg::FRONT_COUNT_THREADS;
-    const int n_score = (int)pcg::score_table_blocks(row_end - row_begin, g->feat_stride);
+    const int n_score = (int)pcg::score_table_blocks(o.row_end - o.row_begin, g->feat_stride);
     // the train positives' unsorted keys go to the scratch half of pos_keys (rank-sort sizes only)
-    const bool raw = pos_keys && train_flag && g->n_pos > 0 && g->n_pos <= pcg::RANK_MAX && (g->train_pos || pos_row_base >= 0);
-    const int rows_per_block = 4 * (PCG_WAVE / pcg::lanes_per_row(g->feat_stride));
-    int n_key = raw ? (g->n_pos + rows_per_block - 1) / rows_per_block : 0;
-    if (n_key > 256) n_key = 256;
-    uint64_t *raw_keys = raw ? pos_keys + pcg_pos_sort_capacity(g->n_pos) / 2 : nullptr;
-    pcg::DeferredAdam none = {};
-    const int n_adam = ad ? (int)((ad->p_end + PCG_WAVE - 1) / PCG_WAVE) : 0;
+    const bool raw = c.pos_keys && c.train_flag && g->n_pos > 0 && g->n_pos <= pcg::RANK_MAX && (g->train_pos || o.pos_row_base >= 0);
+    const int n_key = raw ? pcg::key_blocks(g->n_pos, g->feat_stride) : 0;
+    uint64_t *raw_keys = raw ? pcg::raw_half(c.pos_keys, g->n_pos) : nullptr;
+    const int n_adam = o.ad ? (int)((o.ad->p_end + PCG_WAVE - 1) / PCG_WAVE) : 0;
     hipLaunchKernelGGL(pcg::front_a_kernel, dim3(n_count + n_key + n_adam + n_score), dim3(pcg::FRONT_COUNT_THREADS), 0,
-                       static_cast<hipStream_t>(stream), a, tot, n_count, n_key, raw_keys, W, b, row_begin, row_end, s0_out,
-                       ad ? *ad : none, n_adam, row_ids, pos_row_base, touched);
+                       static_cast<hipStream_t>(stream), a, tot, n_count, n_key, raw_keys, W, b, o.row_begin, o.row_end, c.s0,
+                       o.ad ? *o.ad : pcg::DeferredAdam{}, n_adam, o.row_ids, o.pos_row_base, o.touched);
     PCG_LAUNCH_CHECK();
     return PCG_OK;
 }
@@ -892,22 +871,25 @@ int pcg_step_front_a(const pcg_graph_desc *g, const float *W, const float *b, in
                      int32_t B, const double *thresholds, const double *rho, int32_t train_flag, int32_t add_self,
                      void *workspace, int64_t list_capacity, uint32_t *status, void *stream) {
     if (row_ids && pos_keys) return PCG_E_ARG;       // (the keys-from-feature-rows group indexes X by node id)
-    return front_a(g, W, b, row_begin, row_end, s0_out, row_ids, pos_keys, nodes, labels, B, thresholds, rho, train_flag, add_self,
-                   workspace, list_capacity, status, nullptr, stream);
+    const pcg_batch batch = {nodes, labels, nullptr, nullptr, B};
+    const pcg_select_ws ws = {thresholds, rho, workspace, status, list_capacity, add_self};
+    FrontOpts o;
+    o.row_begin = row_begin; o.row_end = row_end; o.row_ids = row_ids;
+    return front_a(select_call(g, train_flag, s0_out, pos_keys, &batch, &ws), W, b, o, stream);
 }
 
-/* second half: train-pos sort by s0 (if train_flag and n_pos > 0)  ||  plan pass 2 */
-static int front_b(const pcg_graph_desc *g, const float *s0, uint64_t *pos_keys, int32_t raw_keys_ready,
-                   const int32_t *nodes, const int32_t *labels, int32_t B, const double *thresholds, const double *rho,
-                   int32_t train_flag, int32_t add_self, void *workspace, int64_t list_capacity, uint32_t *status,
-                   uint32_t *pending, float *center_out, int64_t center_id_offset, void *stream) {
-    if (!g || !s0 || B < 0 || (center_out && center_id_offset < 0)) return PCG_E_ARG;
-    const bool sort = train_flag && g->n_pos > 0;
-    if (sort && (!pos_keys || !g->train_pos)) return PCG_E_ARG;
-    if (B == 0) return sort ? pcg_pos_sort(g, s0, pos_keys, stream) : PCG_OK;
+/* second half: train-pos sort by c.s0 (if train_flag and n_pos > 0)  ||  plan pass 2 */
+// pending: device word the launch zeroes ("front_a has applied the deferred update"), or null
+static int front_b(const pcg::SelectCall &c, int32_t raw_keys_ready, uint32_t *pending, float *center_out, int64_t center_id_offset,
+                   void *stream) {
+    const pcg_graph_desc *g = c.g;
+    const int32_t B = c.batch->B;
+    if (!g || !c.s0 || B < 0 || (center_out && center_id_offset < 0)) return PCG_E_ARG;
+    const bool sort = c.train_flag && g->n_pos > 0;
+    if (sort && (!c.pos_keys || !g->train_pos)) return PCG_E_ARG;
+    if (B == 0) return sort ? pcg_pos_sort(g, c.s0, c.pos_keys, stream) : PCG_OK;
     pcg::ChooseArgs a;
-    const int rc = choose_args(a, g, nodes, labels, B, s0, nullptr, pos_keys, thresholds, rho, train_flag, add_self, nullptr,
-                               workspace, list_capacity, status);
+    const int rc = choose_args(a, c);
     if (rc != PCG_OK) return rc;
     const int rows = g->n_rel * B;
     pcg::PlanTotals *tot = reinterpret_cast<pcg::PlanTotals *>(a.w.plan_totals);
@@ -915,12 +897,13 @@ static int front_b(const pcg_graph_desc *g, const float *s0, uint64_t *pos_keys,
     const int n_write = (rows + pcg::PLAN_THREADS - 1) / pcg::PLAN_THREADS;
     const bool rank = sort && g->n_pos <= pcg::RANK_MAX;
     const int n_sort = rank ? (g->n_pos + PCG_WAVE - 1) / PCG_WAVE : 0;
-    const int64_t cap = sort ? pcg_pos_sort_capacity(g->n_pos) / 2 : 0;
-    const uint64_t *raw_keys = (rank && raw_keys_ready) ? pos_keys + cap : nullptr;
+    const uint64_t *raw = sort ? pcg::raw_half(c.pos_keys, g->n_pos) : nullptr;
+    const int cap = raw ? (int)(raw - c.pos_keys) : 0;
+    const uint64_t *raw_keys = (rank && raw_keys_ready) ? raw : nullptr;
     hipLaunchKernelGGL(pcg::front_b_kernel, dim3(n_write + n_sort), dim3(pcg::PLAN_THREADS), 0, static_cast<hipStream_t>(stream), a,
-                       tot, n_write, n_count, pos_keys, (int)cap, raw_keys, pending, center_out, center_id_offset);
+                       tot, n_write, n_count, c.pos_keys, cap, raw_keys, pending, center_out, center_id_offset);
     PCG_LAUNCH_CHECK();
-    if (sort && !rank) return pcg_pos_sort(g, s0, pos_keys, stream);    // many positives: the bucket sort's own launches
+    if (sort && !rank) return pcg_pos_sort(g, c.s0, c.pos_keys, stream);    // many positives: the bucket sort's own launches
     return PCG_OK;
 }
 
@@ -928,8 +911,9 @@ int pcg_step_front_b(const pcg_graph_desc *g, const float *s0, uint64_t *pos_key
                      const int32_t *nodes, const int32_t *labels, int32_t B, const double *thresholds, const double *rho,
                      int32_t train_flag, int32_t add_self, void *workspace, int64_t list_capacity, uint32_t *status,
                      float *center_s0_out, int64_t center_id_offset, void *stream) {
-    return front_b(g, s0, pos_keys, raw_keys_ready, nodes, labels, B, thresholds, rho, train_flag, add_self, workspace,
-                   list_capacity, status, nullptr, center_s0_out, center_id_offset, stream);
+    const pcg_batch batch = {nodes, labels, nullptr, nullptr, B};
+    const pcg_select_ws ws = {thresholds, rho, workspace, status, list_capacity, add_self};
+    return front_b(select_call(g, train_flag, s0, pos_keys, &batch, &ws), raw_keys_ready, nullptr, center_s0_out, center_id_offset, stream);
 }
 
 // the deferred Adam update of parameters [0, p_end) from `slabs` (per-tile gradient slabs, or ONE all-reduced gradient) over an
@@ -938,20 +922,33 @@ static pcg::DeferredAdam deferred_adam(const pcg_train_state *st, const float *s
     return {st->theta, st->m, st->v, slabs, n_params, p_end, st->step_counter, st->sync_words + 1, pcg::adam_hyper(st->hyper)};
 }
 
+// what every training entry point wants of an engine's state (slabs: unless the gradient comes from elsewhere), and the model's
+// parameter count and label-classifier offset (false: no such model).  Two steps: some calls answer a too wide table in between
+static bool state_missing(const pcg_train_state *st, bool need_slabs = true) {
+    return !st->theta || !st->m || !st->v || (need_slabs && !st->slabs) || !st->step_counter || !st->sync_words;
+}
+static bool train_offsets(const pcg_graph_desc *g, const pcg_train_state *st, int64_t *n_params, int64_t *o_clf) {
+    *n_params = pcg_dense_n_params(g->feat_dim, st->emb, g->n_rel);
+    *o_clf = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 3, 0);
+    return *n_params >= 0 && *o_clf >= 0;
+}
+
 /* pcg_step_front of a TRAINING step, with the previous step's deferred Adam update riding along the score pass */
 int pcg_step_front_train(const pcg_graph_desc *g, const pcg_train_state *st, float *s0, uint64_t *pos_keys, const pcg_batch *batch,
                          const pcg_select_ws *sel, void *stream) {
     if (!g || !st || !batch || !sel) return PCG_E_ARG;
-    if (!st->theta || !st->m || !st->v || !st->slabs || !st->step_counter || !st->sync_words || batch->B < 1) return PCG_E_ARG;
-    const int64_t n_params = pcg_dense_n_params(g->feat_dim, st->emb, g->n_rel);
-    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 3, 0), o_b = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 4, 0);
-    if (n_params < 0 || o_clf < 0) return PCG_E_ARG;
+    int64_t n_params, o_clf;
+    if (batch->B < 1 || state_missing(st) || !train_offsets(g, st, &n_params, &o_clf)) return PCG_E_ARG;
     const pcg::DeferredAdam ad = deferred_adam(st, st->slabs, n_params, o_clf);
-    const int rc = front_a(g, st->theta + o_clf, st->theta + o_b, 0, g->n_nodes, s0, nullptr, pos_keys, batch->ids, batch->labels, batch->B,
-                           sel->thresholds, sel->rho, 1, sel->add_self, sel->workspace, sel->list_capacity, sel->status, &ad, stream);
+    // (the two-launch front plans into the workspace, whatever plan the batch carries, and counts nothing)
+    const pcg_batch front = {batch->ids, batch->labels, nullptr, nullptr, batch->B};
+    const pcg::SelectCall c = select_call(g, 1, s0, pos_keys, &front, sel);
+    FrontOpts o;
+    o.row_end = g->n_nodes; o.ad = &ad;
+    const float *bias = st->theta + pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 4, 0);
+    const int rc = front_a(c, st->theta + o_clf, bias, o, stream);
     if (rc != PCG_OK) return rc;
-    return front_b(g, s0, pos_keys, 1, batch->ids, batch->labels, batch->B, sel->thresholds, sel->rho, 1, sel->add_self, sel->workspace,
-                   sel->list_capacity, sel->status, st->sync_words + 1, nullptr, 0, stream);
+    return front_b(c, 1, st->sync_words + 1, nullptr, 0, stream);
 }
 
 /* The front of a training step whose plan exists already (pcg_plan_batches): ONE launch
@@ -961,14 +958,15 @@ int pcg_step_front_train(const pcg_graph_desc *g, const pcg_train_state *st, flo
 int pcg_step_scores_train(const pcg_graph_desc *g, const pcg_train_state *st, float *s0, uint64_t *pos_keys, const uint8_t *touched,
                           void *stream) {
     if (!g || !st) return PCG_E_ARG;
-    if (!st->theta || !st->m || !st->v || !st->slabs || !st->step_counter || !st->sync_words) return PCG_E_ARG;
     if (g->n_pos > 0 && (!pos_keys || !g->train_pos)) return PCG_E_ARG;
-    const int64_t n_params = pcg_dense_n_params(g->feat_dim, st->emb, g->n_rel);
-    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 3, 0), o_b = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 4, 0);
-    if (n_params < 0 || o_clf < 0) return PCG_E_ARG;
+    int64_t n_params, o_clf;
+    if (state_missing(st) || !train_offsets(g, st, &n_params, &o_clf)) return PCG_E_ARG;
     const pcg::DeferredAdam ad = deferred_adam(st, st->slabs, n_params, o_clf);
-    const int rc = front_a(g, st->theta + o_clf, st->theta + o_b, 0, g->n_nodes, s0, nullptr, pos_keys, nullptr, nullptr, 0, nullptr, nullptr, 1, 0,
-                           nullptr, 1, nullptr, &ad, stream, true, st->sync_words + 3, -1, touched);
+    FrontOpts o;
+    o.row_end = g->n_nodes; o.touched = touched;
+    o.zero_word = st->sync_words + 3; o.ad = &ad; o.no_plan = true;
+    const float *bias = st->theta + pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 4, 0);
+    const int rc = front_a(select_call(g, 1, s0, pos_keys), st->theta + o_clf, bias, o, stream);
     if (rc != PCG_OK) return rc;
     if (g->n_pos > pcg::RANK_MAX) return pcg_pos_sort(g, s0, pos_keys, stream);
     return PCG_OK;
@@ -983,8 +981,10 @@ int pcg_step_scores(const pcg_graph_desc *g, const float *W, const float *b, int
     if (!g || !sync_words) return PCG_E_ARG;
     if (pos_keys && row_ids && pos_row_base < 0) return PCG_E_ARG;     // (with row_ids a node id is not a table row)
     if (pos_row_base >= 0 && pos_row_base + g->n_pos > g->n_nodes) return PCG_E_ARG;
-    const int rc = front_a(g, W, b, row_begin, row_end, s0_out, row_ids, pos_keys, nullptr, nullptr, 0, nullptr, nullptr, 1, 0, nullptr, 1,
-                           nullptr, nullptr, stream, true, sync_words + 3, pos_row_base, touched);
+    FrontOpts o;
+    o.row_begin = row_begin; o.row_end = row_end; o.row_ids = row_ids; o.touched = touched;
+    o.pos_row_base = pos_row_base; o.zero_word = sync_words + 3; o.no_plan = true;
+    const int rc = front_a(select_call(g, 1, s0_out, pos_keys), W, b, o, stream);
     if (rc != PCG_OK) return rc;
     // (too many train positives for the select kernel's own sort: the bucket sort's launches, by node id - not for row_ids tables)
     if (pos_keys && !row_ids && pos_row_base < 0 && g->n_pos > pcg::RANK_MAX) return pcg_pos_sort(g, s0_out, pos_keys, stream);
@@ -1003,32 +1003,24 @@ int pcg_step_scores_dist(const pcg_graph_desc *g, const pcg_train_state *st, con
                          int64_t row_begin, int64_t row_end, float *s0_out, const int32_t *row_ids, uint64_t *pos_keys,
                          int64_t pos_row_base, void *stream) {
     if (!g || !st) return PCG_E_ARG;
-    if (!g->X || !st->theta || !st->m || !st->v || !grad || !clf_snap || !s0_out || !st->step_counter || !st->sync_words) return PCG_E_ARG;
-    if (g->feat_dim < 1 || g->feat_dim > 512 || g->feat_stride < g->feat_dim || g->feat_stride % 4 != 0) return PCG_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(g->X) & 15u) != 0) return PCG_E_ARG;
+    if (!g->X || !grad || !clf_snap || !s0_out || state_missing(st, false)) return PCG_E_ARG;
+    if (g->feat_dim > 512) return PCG_E_ARG;                 // (FRONT_DIST_NC: the classifier each workgroup keeps in LDS)
     if (row_begin < 0 || row_end > g->n_nodes || row_begin > row_end) return PCG_E_ARG;
     if (pos_keys && (pos_row_base < 0 || pos_row_base + g->n_pos > g->n_nodes || g->n_pos > pcg::RANK_MAX)) return PCG_E_ARG;
-    if (g->feat_stride > 512) return PCG_E_UNSUPPORTED;      // (score_table_body; feat_dim <= 512 alone lets a stride of 516 in)
-    const int64_t n_params = pcg_dense_n_params(g->feat_dim, st->emb, g->n_rel);
-    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 3, 0);
-    if (n_params < 0 || o_clf < 0) return PCG_E_ARG;
+    int64_t n_params, o_clf;
+    int rc = pcg::check_table(pcg::feat_table(g), pcg::TABLE_SCORE);      // (score_table_body; feat_dim <= 512 alone lets a stride of 516 in)
+    if (rc == PCG_OK && !train_offsets(g, st, &n_params, &o_clf)) rc = PCG_E_ARG;
+    if (rc != PCG_OK) return rc;
     pcg::FrontDist f;
     f.g = *g;
-    f.row_begin = row_begin;
-    f.row_end = row_end;
-    f.s0 = s0_out;
-    f.row_ids = row_ids;
-    f.pos_row_base = pos_row_base;
+    f.row_begin = row_begin; f.row_end = row_end; f.row_ids = row_ids;
+    f.s0 = s0_out; f.pos_row_base = pos_row_base;
     const bool raw = pos_keys && g->n_pos > 0;
-    f.raw_keys = raw ? pos_keys + pcg_pos_sort_capacity(g->n_pos) / 2 : nullptr;
-    const int rows_per_block = 4 * (PCG_WAVE / pcg::lanes_per_row(g->feat_stride));
-    int n_key = raw ? (g->n_pos + rows_per_block - 1) / rows_per_block : 0;
-    f.n_key_blocks = n_key > 256 ? 256 : n_key;
+    f.raw_keys = raw ? pcg::raw_half(pos_keys, g->n_pos) : nullptr;
+    f.n_key_blocks = raw ? pcg::key_blocks(g->n_pos, g->feat_stride) : 0;
     f.n_adam_blocks = (int)((n_params + PCG_WAVE - 1) / PCG_WAVE);
     f.ad = deferred_adam(st, grad, n_params, n_params);
-    f.snap = clf_snap;
-    f.nc = 2 * g->feat_dim + 2;
-    f.off_clf = o_clf;
+    f.snap = clf_snap; f.nc = 2 * g->feat_dim + 2; f.off_clf = o_clf;
     f.zero_word = st->sync_words + 3;
     const int n_score = (int)pcg::score_table_blocks(row_end - row_begin, g->feat_stride);
     hipLaunchKernelGGL(pcg::front_dist_kernel, dim3(f.n_adam_blocks + f.n_key_blocks + n_score), dim3(pcg::FRONT_COUNT_THREADS), 0,
@@ -1077,11 +1069,8 @@ int pcg_choose_gather_planned(const pcg_graph_desc *g, const int32_t *nodes, con
     if (!g || B < 0) return PCG_E_ARG;
     if (B == 0) return PCG_OK;
     if (!g->X || !agg) return PCG_E_ARG;
-    PlannedExtra x;
-    x.plan = plan;
-    x.sync_words = sync_words;
-    const int rc = choose_select(true, g, nodes, labels, B, s0, center_s0, pos_keys, thresholds, rho, train_flag, add_self, cnt,
-                                 workspace, list_capacity, status, stream, x);
+    const int rc = pcg_choose_select_planned(g, nodes, labels, B, s0, center_s0, pos_keys, thresholds, rho, train_flag, add_self, cnt,
+                                             workspace, plan, list_capacity, status, sync_words, 0, stream);
     if (rc != PCG_OK) return rc;
     return pcg_gather_lists_planned(g->X, g->feat_dim, g->feat_stride, g->n_nodes, g->n_rel * B, cnt, g, B, workspace, plan, list_capacity,
                                     agg, agg_stride, status, stream);
@@ -1091,23 +1080,25 @@ int pcg_choose_gather_planned(const pcg_graph_desc *g, const int32_t *nodes, con
 struct TrainParts {
     pcg::ChooseArgs a;
     pcg::SideJob sd;
-    bool rank, one_launch;
-    int64_t cap;
+    bool one_launch;
+};
+struct TrainOpts {                 // what a training step's select + gather calls are told about the steps around them
+    int32_t score_next;            // the gather launch also scores the table and forms the keys for the NEXT step
+    const uint8_t *next_touched;   // ... only the rows of this byte map (null: all)
+    int32_t keys_sorted;           // pos_keys' first half holds THIS step's keys sorted already
 };
 
 // the label classifier's step for `batch` over an engine's state: everything of a ClfStep but who runs it and for whom
 // (clf_out, count_step, nodes / labels / B, t_ahead)
 static void clf_step_of(pcg::ClfStep &c, const pcg_train_state *st, const pcg_batch *batch, int64_t o_clf, int64_t n_params) {
     c.clf_next = st->clf_next;
-    c.theta_clf = st->theta + o_clf;
-    c.m = st->m + o_clf;
-    c.v = st->v + o_clf;
+    c.theta_clf = st->theta + o_clf; c.m = st->m + o_clf; c.v = st->v + o_clf;
     c.step_counter = st->step_counter;
     c.scale = batch->inv_count * st->lambda_1;
     c.h = pcg::adam_hyper(st->hyper);
-    // (a slice of <= 1024 rows per workgroup, at most 8 of them; their gradients meet in the first slabs' classifier entries -
-    //  free until this step's dense launch writes them -, the arrival ticket is the dense kernel's unused one)
-    c.n_wg = (batch->B + 1023) / 1024 > 8 ? 8 : (batch->B + 1023) / 1024;
+    // (the workgroups' gradients meet in the first slabs' classifier entries - free until this step's dense launch writes them -,
+    //  the arrival ticket is the dense kernel's unused one)
+    c.n_wg = pcg::clf_workgroups(batch->B);
     c.part = st->slabs + o_clf;
     c.part_stride = n_params;
     c.ticket = st->sync_words;
@@ -1115,41 +1106,28 @@ static void clf_step_of(pcg::ClfStep &c, const pcg_train_state *st, const pcg_ba
 
 // wgrad_in_select: the A/B option PCG_WGRAD_IN_SELECT may move the weight-gradient workgroups into the select launch - only
 // when one call makes both launches (the split calls keep them in the gather launch)
-// (the caller has checked g, batch, sel, st; B >= 1)
-static int train_parts(TrainParts &t, bool wgrad_in_select, const pcg_graph_desc *g, const pcg_batch *batch, float *s0,
-                       uint64_t *pos_keys, const pcg_select_ws *sel, const float *agg, const pcg_train_state *st, int32_t score_next,
-                       const uint8_t *next_touched, int32_t keys_sorted) {
-    const int32_t B = batch->B;
-    if (!g->X || !agg || !s0 || !st->sync_words || !st->theta || !st->m || !st->v || !st->clf_next || !st->slabs || !st->step_counter ||
-        !batch->labels)
-        return PCG_E_ARG;
+// (st: everything is read from it - the fused launch hands in a copy without activations; the caller has checked c.g, c.batch,
+//  c.ws, st; B >= 1)
+static int train_parts(TrainParts &t, bool wgrad_in_select, const pcg::SelectCall &c, const float *agg, const pcg_train_state *st,
+                       const TrainOpts &opt) {
+    const pcg_graph_desc *g = c.g;
+    const pcg_batch *batch = c.batch;
+    if (!g->X || !agg || !c.s0 || state_missing(st) || !st->clf_next || !batch->labels) return PCG_E_ARG;
     if (st->acts && (st->act_ld < 16 || st->act_ld % 16 != 0 || (reinterpret_cast<uintptr_t>(st->acts) & 15u) != 0 || st->emb % 16 != 0))
         return PCG_E_ARG;
     if (st->acts && pcg::wgrad_kparts(st->act_ld / 16) > 1 && !st->wg_scratch) return PCG_E_ARG;
-    if (g->feat_stride > 512) return PCG_E_UNSUPPORTED;
-    const int64_t n_params = pcg_dense_n_params(g->feat_dim, st->emb, g->n_rel);
-    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 3, 0);
-    if (n_params < 0 || o_clf < 0) return PCG_E_ARG;
+    if (pcg::table_too_wide(pcg::feat_table(g))) return PCG_E_UNSUPPORTED;
+    int64_t n_params, o_clf;
+    if (!train_offsets(g, st, &n_params, &o_clf)) return PCG_E_ARG;
     pcg::ChooseArgs &a = t.a;
-    int rc = choose_args(a, g, batch->ids, batch->labels, B, s0, nullptr, pos_keys, sel->thresholds, sel->rho, 1, sel->add_self, batch->cnt,
-                         sel->workspace, sel->list_capacity, sel->status, false, batch->plan);
+    const int rc = choose_args(a, c);
     if (rc != PCG_OK) return rc;
     if (!batch->cnt) return PCG_E_ARG;
-    const bool rank = t.rank = g->n_pos > 0 && g->n_pos <= pcg::RANK_MAX;
-    const int64_t cap = t.cap = g->n_pos > 0 ? pcg_pos_sort_capacity(g->n_pos) / 2 : 0;
+    const bool rank = g->n_pos > 0 && g->n_pos <= pcg::RANK_MAX;
     // keys_sorted: pos_keys' first half holds THIS step's keys sorted already (the previous step's pcg_train_dense(sort_keys), or
     // pcg_pos_sort behind pcg_step_scores): no in-kernel sort, no row waits, a hub row's window search runs beside its key pass
-    if (rank && !keys_sorted) {                        // the select kernel sorts the unsorted keys itself
-        a.sort_out = pos_keys;
-        a.raw_keys = pos_keys + cap;
-        a.sort_cap = (int32_t)cap;
-        a.n_sort = (g->n_pos + PCG_WAVE - 1) / PCG_WAVE;
-        a.sort_done = st->sync_words + 3;
-        a.rank_acc = st->sync_words + 4;
-        a.group_ticket = st->sync_words + 4 + pcg::RANK_MAX;
-    }
+    if (rank && !opt.keys_sorted) wire_in_kernel_sort(a, c.pos_keys, st->sync_words, g->n_pos);      // the select kernel sorts the unsorted keys itself
     clf_step_of(a.clf, st, batch, o_clf, n_params);
-    const pcg::AdamHyper h = a.clf.h;
     // the deferred update's weight-gradient workgroups (acts): in the gather launch (where they cost ~3 us of its ~10) - or, an
     // option that measured slower, as the first units of the select launch
     pcg::WgradArgs wga = {};
@@ -1159,16 +1137,13 @@ static int train_parts(TrainParts &t, bool wgrad_in_select, const pcg_graph_desc
         wga.F = g->feat_dim; wga.E = st->emb; wga.R = g->n_rel;
         wga.theta = st->theta; wga.m = st->m; wga.v = st->v;
         wga.step_counter = st->step_counter;
-        wga.h = h;
+        wga.h = a.clf.h;
         wga.pending = st->sync_words + 1;
         wga.n_kblocks = st->act_ld / 16;         // (the batch size the engine's buffers were made for: the expected one)
         wga.kparts = pcg::wgrad_kparts(st->act_ld / 16);
         wga.tickets = reinterpret_cast<uint32_t *>(st->wg_scratch);
         wga.partials = st->wg_scratch ? st->wg_scratch + (pcg::wgrad_tiles(g->feat_dim, st->emb, g->n_rel, 1) + 63) / 64 * 64 : nullptr;
-        wga.grad_out = nullptr;
-        wga.flag_set = nullptr;
         wga.apply = 1;
-        wga.with_clf = 0;
         wg_tiles = pcg::wgrad_tiles(g->feat_dim, st->emb, g->n_rel, 0);
         // (A/B knob PCG_WGRAD_IN_SELECT=1.  Measured, YelpChi-like batch 1024: select_rows 16.2 -> 19.9 us, gather launch 10.5 -> 8.2:
         //  43.8 vs 42.9 us per step - the workgroups that start on their rows ~7 us late end the launch later than the gather's
@@ -1200,29 +1175,26 @@ static int train_parts(TrainParts &t, bool wgrad_in_select, const pcg_graph_desc
         sd.wg_prio = prio;
         if (off) sd.n_wgrad_blocks = 0;
     }
-    sd.W = score_next ? st->clf_next : nullptr;
+    sd.W = opt.score_next ? st->clf_next : nullptr;
     sd.bias = st->clf_next + 2 * g->feat_dim;
-    sd.s0 = s0;
-    sd.touched = next_touched;
+    sd.s0 = c.s0; sd.touched = opt.next_touched;
     // (the one-launch bucket sort - 16384 < n_pos <= 131072 - works on raw keys formed here too)
     const bool one_launch = t.one_launch = pcg_pos_sort_one_launch(g->n_pos) != 0;
-    sd.raw_keys = (score_next && (rank || one_launch) && g->train_pos) ? pos_keys + cap : nullptr;
-    const int rows_per_block = 4 * (PCG_WAVE / pcg::lanes_per_row(g->feat_stride));
-    int n_key = sd.raw_keys ? (g->n_pos + rows_per_block - 1) / rows_per_block : 0;
-    sd.n_key_blocks = n_key > 256 ? 256 : n_key;
-    sd.n_score_blocks = score_next ? (int)pcg::score_table_blocks(g->n_nodes, g->feat_stride) : 0;
+    sd.raw_keys = (opt.score_next && (rank || one_launch) && g->train_pos) ? pcg::raw_half(c.pos_keys, g->n_pos) : nullptr;
+    sd.n_key_blocks = sd.raw_keys ? pcg::key_blocks(g->n_pos, g->feat_stride) : 0;
+    sd.n_score_blocks = opt.score_next ? (int)pcg::score_table_blocks(g->n_nodes, g->feat_stride) : 0;
     sd.zero_word = st->sync_words + 3;
     return PCG_OK;
 }
 
 // parts: 1 = the select launch, 2 = the gather launch (+ the sort of the next step's keys where that is a launch of its own), 3 = both
-static int train_launch(int parts, float *clf_out, const pcg_graph_desc *g, const pcg_batch *batch, float *s0, uint64_t *pos_keys,
-                        const pcg_select_ws *sel, float *agg, int32_t agg_stride, const pcg_train_state *st, int32_t score_next,
-                        const uint8_t *next_touched, int32_t keys_sorted, void *stream) {
-    if (!g || !batch || !sel || !st || batch->B < 0) return PCG_E_ARG;
-    if (batch->B == 0) return PCG_OK;
+static int train_launch(int parts, float *clf_out, const pcg::SelectCall &c, float *agg, int32_t agg_stride, const pcg_train_state *st,
+                        const TrainOpts &opt, void *stream) {
+    if (!c.g || !c.batch || !c.ws || !st || c.batch->B < 0) return PCG_E_ARG;
+    if (c.batch->B == 0) return PCG_OK;
+    const pcg_graph_desc *g = c.g;
     TrainParts t;
-    int rc = train_parts(t, parts == 3, g, batch, s0, pos_keys, sel, agg, st, score_next, next_touched, keys_sorted);
+    int rc = train_parts(t, parts == 3, c, agg, st, opt);
     if (rc != PCG_OK) return rc;
     t.a.clf.clf_out = clf_out;
     hipStream_t stm = static_cast<hipStream_t>(stream);
@@ -1231,11 +1203,12 @@ static int train_launch(int parts, float *clf_out, const pcg_graph_desc *g, cons
         if (rc != PCG_OK) return rc;
     }
     if (!(parts & 2)) return PCG_OK;
-    rc = pcg::launch_gather_train(g->X, g->feat_dim, g->feat_stride, g->n_nodes, batch->cnt, g, batch->B, t.a.w, agg, agg_stride, sel->status,
-                                  t.sd, stm);
+    const pcg::GatherOut out = {agg, agg_stride, PCG_NORM_COUNT, c.batch->cnt, c.ws->status};
+    rc = pcg::launch_gather_train(pcg::feat_table(g), out, g, c.batch->B, t.a.w, t.sd, stm);
     if (rc != PCG_OK) return rc;
-    if (score_next && t.one_launch) return pcg::launch_bk_onepass(pos_keys + t.cap, g->n_pos, pos_keys, (int)t.cap, sel->status, stm);
-    if (score_next && g->n_pos > pcg::RANK_MAX) return pcg_pos_sort(g, s0, pos_keys, stream);
+    if (opt.score_next && t.one_launch)        // (sd.raw_keys: the raw half - choose_args has seen train_pos)
+        return pcg::launch_bk_onepass(t.sd.raw_keys, g->n_pos, c.pos_keys, (int)(t.sd.raw_keys - c.pos_keys), c.ws->status, stm);
+    if (opt.score_next && g->n_pos > pcg::RANK_MAX) return pcg_pos_sort(g, c.s0, c.pos_keys, stream);
     return PCG_OK;
 }
 
@@ -1248,33 +1221,47 @@ static int train_launch(int parts, float *clf_out, const pcg_graph_desc *g, cons
 int pcg_choose_gather_train(const pcg_graph_desc *g, const pcg_batch *batch, float *s0, uint64_t *pos_keys, const pcg_select_ws *sel,
                             float *agg, int32_t agg_stride, const pcg_train_state *st, int32_t score_next,
                             const uint8_t *next_touched, int32_t keys_sorted, void *stream) {
-    return train_launch(3, nullptr, g, batch, s0, pos_keys, sel, agg, agg_stride, st, score_next, next_touched, keys_sorted, stream);
+    return train_launch(3, nullptr, select_call(g, 1, s0, pos_keys, batch, sel), agg, agg_stride, st, {score_next, next_touched, keys_sorted},
+                        stream);
 }
 
 int pcg_choose_train_part(int32_t part, const pcg_graph_desc *g, const pcg_batch *batch, float *s0, uint64_t *pos_keys,
                           const pcg_select_ws *sel, float *agg, int32_t agg_stride, const pcg_train_state *st, int32_t score_next,
                           const uint8_t *next_touched, int32_t keys_sorted, float *clf_out, void *stream) {
     if (part != 1 && part != 2) return PCG_E_ARG;
-    return train_launch(part, clf_out, g, batch, s0, pos_keys, sel, agg, agg_stride, st, score_next, next_touched, keys_sorted, stream);
+    return train_launch(part, clf_out, select_call(g, 1, s0, pos_keys, batch, sel), agg, agg_stride, st,
+                        {score_next, next_touched, keys_sorted}, stream);
 }
 
 int32_t pcg_dense_select_blocks(const pcg_graph_desc *g, int32_t emb, int32_t B) {
     return g ? pcg::dense_select_blocks(*g, emb, B) : 0;
 }
 
-// The fused launch.  clf_batch / sort_keys: what pcg_dense_select_ahead adds (ahead == false: pcg_dense_select_train, the select
-// half stepping its own batch's classifier and sorting its own keys).  clf_batch->ids: the batch whose classifier step rides here
-// (null: none - the tiles count the step); sort_keys [sorted half | raw half]: the riders sort the raw half into the sorted one
-static int dense_select_launch(const pcg_graph_desc *g, const pcg_train_state *st, const pcg_select_ws *sel, const pcg_batch *batch,
-                               const pcg_batch *next, const float *agg, int32_t agg_stride, const float *clf_in,
-                               const pcg_dense_out *out, float *clf_out, float *s0, uint64_t *pos_keys, bool ahead,
-                               const pcg_batch *clf_batch, uint64_t *sort_keys, void *stream) {
-    if (!g || !st || !sel || !batch || !next || !out || (ahead && !clf_batch)) return PCG_E_ARG;
-    if (batch->B < 1 || next->B < 1 || !clf_in || !st->acts || !batch->cnt || !next->cnt || !sel->workspace || !st->sync_words ||
-        !st->step_counter)
+// The fused launch: the tiles of d.batch (their input, the classifier they read: clf_in) beside the selection `next` (batch t + 1),
+// which leaves its classifier in clf_out.  ahead == false: pcg_dense_select_train, the select half stepping its own batch's
+// classifier and sorting its own keys
+struct FusedCall {
+    const pcg_batch *batch;
+    const float *agg;
+    int32_t agg_stride;
+    const float *clf_in;
+    const pcg_dense_out *out;
+    float *clf_out;
+    bool ahead;
+    const pcg_batch *clf_batch;    // ->ids: the batch whose classifier step rides here (null: none - the tiles count the step)
+    uint64_t *sort_keys;           // [sorted half | raw half]: the riders sort the raw half into the sorted one
+};
+static int dense_select_launch(const pcg::SelectCall &next, const pcg_train_state *st, const FusedCall &d, void *stream) {
+    const pcg_graph_desc *g = next.g;
+    const pcg_select_ws *sel = next.ws;
+    const pcg_batch *batch = d.batch, *clf_batch = d.clf_batch;
+    const bool ahead = d.ahead;
+    if (!g || !st || !sel || !batch || !next.batch || !d.out || (ahead && !clf_batch)) return PCG_E_ARG;
+    if (batch->B < 1 || next.batch->B < 1 || !d.clf_in || !st->acts || !batch->cnt || !next.batch->cnt || !sel->workspace ||
+        !st->sync_words || !st->step_counter)
         return PCG_E_ARG;
     const bool clf_on = !ahead || clf_batch->ids != nullptr;
-    if (clf_on && !clf_out) return PCG_E_ARG;
+    if (clf_on && !d.clf_out) return PCG_E_ARG;
     if (ahead && clf_batch->ids && (!clf_batch->labels || clf_batch->B < 1)) return PCG_E_ARG;
     if (sel->list_capacity < 1 || sel->list_capacity >= (1ll << 31)) return PCG_E_ARG;
     const int n_sel = pcg::dense_select_blocks(*g, st->emb, batch->B);
@@ -1283,64 +1270,49 @@ static int dense_select_launch(const pcg_graph_desc *g, const pcg_train_state *s
     // pcg_dense_select_train: its train-pos keys unsorted (it sorts them itself); pcg_dense_select_ahead: sorted a launch
     // earlier (keys_sorted = 1)
     pcg_train_state sel_st = *st;
-    sel_st.acts = nullptr;
-    sel_st.act_ld = 0;
-    sel_st.wg_scratch = nullptr;
+    sel_st.acts = nullptr; sel_st.act_ld = 0; sel_st.wg_scratch = nullptr;
     TrainParts t;
-    int rc = train_parts(t, false, g, next, s0, pos_keys, sel, agg, &sel_st, 1, nullptr, ahead ? 1 : 0);
+    int rc = train_parts(t, false, next, d.agg, &sel_st, {1, nullptr, ahead ? 1 : 0});
     if (rc != PCG_OK) return rc;
-    t.a.clf.clf_out = clf_out;
-    t.a.clf.count_step = st->step_counter;
+    t.a.clf.clf_out = d.clf_out; t.a.clf.count_step = st->step_counter;
     if (ahead && !clf_batch->ids) {
         t.a.clf.clf_next = nullptr;               // no classifier step in this launch: every select workgroup is a row workgroup
         t.a.clf.count_step = nullptr;
     } else if (ahead) {
         // the step of batch t + 2: the dense launches of t (beside it) and t + 1 have not counted themselves
-        t.a.clf.nodes = clf_batch->ids;
-        t.a.clf.labels = clf_batch->labels;
-        t.a.clf.B = clf_batch->B;
+        t.a.clf.nodes = clf_batch->ids; t.a.clf.labels = clf_batch->labels; t.a.clf.B = clf_batch->B;
         t.a.clf.scale = clf_batch->inv_count * st->lambda_1;
-        t.a.clf.n_wg = (clf_batch->B + 1023) / 1024 > 8 ? 8 : (clf_batch->B + 1023) / 1024;
-        t.a.clf.t_ahead = 3;
+        t.a.clf.n_wg = pcg::clf_workgroups(clf_batch->B); t.a.clf.t_ahead = 3;
     }
     // batch t's tiles as pcg_train_dense(adam_clf = 3) sets them up - without the riding key sort, without counting the step,
     // with the classifier the select launch of batch t left in clf_in
     pcg::DenseExtra x;
-    pcg::Workspace w;
-    pcg::carve1(g, batch->B, sel->list_capacity, static_cast<unsigned char *>(sel->workspace), &w,
-                static_cast<unsigned char *>(const_cast<void *>(batch->plan)));
-    x.chunk_begin = w.chunk_begin;
-    x.partial = w.partial;
+    const pcg::Workspace w = pcg::carve_for(g, batch->B, sel->list_capacity, sel->workspace, batch->plan);
+    x.chunk_begin = w.chunk_begin; x.partial = w.partial; x.partial_stride = g->feat_stride;
     x.cnt = batch->cnt;
-    x.partial_stride = g->feat_stride;
     x.pending = st->sync_words + 1;
-    x.acts = st->acts;
-    x.act_ld = st->act_ld;
-    pcg::DenseArgs d;
+    x.acts = st->acts; x.act_ld = st->act_ld;
+    pcg::DenseArgs da;
     int n_sort_blocks = 0;
     // (no classifier step beside the tiles: nothing in the launch reads the count, the tiles count the step themselves)
-    rc = pcg::dense_args(d, n_sort_blocks, g, st->theta, st->emb, batch->ids, batch->labels, batch->B, agg, agg_stride, st->lambda_1,
-                         batch->inv_count, out->logits, out->center, nullptr, out->row_loss, st->slabs,
+    rc = pcg::dense_args(da, n_sort_blocks, g, st->theta, st->emb, batch->ids, batch->labels, batch->B, d.agg, d.agg_stride, st->lambda_1,
+                         batch->inv_count, d.out->logits, d.out->center, nullptr, d.out->row_loss, st->slabs,
                          t.a.clf.clf_next ? nullptr : st->step_counter, x);
     if (rc != PCG_OK) return rc;
-    d.W_clf = clf_in;
-    d.b_clf = clf_in + 2 * g->feat_dim;
-    d.stamps = nullptr;
-    if (ahead && sort_keys && g->n_pos > 0) {
-        const int64_t cap = pcg_pos_sort_capacity(g->n_pos) / 2;
-        d.sort_out = sort_keys;
-        d.sort_raw = sort_keys + cap;
-        d.sort_n = g->n_pos;
-        d.sort_cap = (int32_t)cap;
+    da.W_clf = d.clf_in; da.b_clf = d.clf_in + 2 * g->feat_dim;
+    da.stamps = nullptr;
+    if (ahead && d.sort_keys && g->n_pos > 0) {
+        da.sort_out = d.sort_keys; da.sort_raw = pcg::raw_half(d.sort_keys, g->n_pos);
+        da.sort_n = g->n_pos; da.sort_cap = (int32_t)(da.sort_raw - d.sort_keys);
     }
-    return pcg::launch_dense_select(d, t.a, n_sel, static_cast<hipStream_t>(stream));
+    return pcg::launch_dense_select(da, t.a, n_sel, static_cast<hipStream_t>(stream));
 }
 
 int pcg_dense_select_train(const pcg_graph_desc *g, const pcg_train_state *st, const pcg_select_ws *sel, const pcg_batch *batch,
                            const pcg_batch *next, const float *agg, int32_t agg_stride, const float *clf_in,
                            const pcg_dense_out *out, float *clf_out, float *s0, uint64_t *pos_keys, void *stream) {
-    return dense_select_launch(g, st, sel, batch, next, agg, agg_stride, clf_in, out, clf_out, s0, pos_keys, false, nullptr, nullptr,
-                               stream);
+    const FusedCall d = {batch, agg, agg_stride, clf_in, out, clf_out};
+    return dense_select_launch(select_call(g, 1, s0, pos_keys, next, sel), st, d, stream);
 }
 
 /* 1: the fused launch of a batch of B rows has room for pcg_dense_select_ahead's sort riders beside the tiles and the select
@@ -1359,8 +1331,8 @@ int pcg_dense_select_ahead(const pcg_graph_desc *g, const pcg_train_state *st, c
                            const float *clf_in, const pcg_dense_out *out, float *clf_out, float *s0, uint64_t *pos_keys,
                            uint64_t *sort_keys, void *stream) {
     if (sort_keys && sort_keys == pos_keys) return PCG_E_ARG;       // (the select half reads pos_keys while the riders write)
-    return dense_select_launch(g, st, sel, batch, next, agg, agg_stride, clf_in, out, clf_out, s0, pos_keys, true, clf_batch, sort_keys,
-                               stream);
+    const FusedCall d = {batch, agg, agg_stride, clf_in, out, clf_out, true, clf_batch, sort_keys};
+    return dense_select_launch(select_call(g, 1, s0, pos_keys, next, sel), st, d, stream);
 }
 
 /* The label classifier's step for one batch as a launch of its own: clf_next <- the classifier after the step, theta's classifier
@@ -1368,20 +1340,13 @@ int pcg_dense_select_ahead(const pcg_graph_desc *g, const pcg_train_state *st, c
 int pcg_clf_step(const pcg_graph_desc *g, const pcg_batch *batch, const pcg_train_state *st, float *clf_out, int32_t t_ahead,
                  void *stream) {
     if (!g || !batch || !st) return PCG_E_ARG;
-    if (!g->X || !batch->ids || !batch->labels || batch->B < 1 || !st->theta || !st->m || !st->v || !st->clf_next || !st->slabs ||
-        !st->step_counter || !st->sync_words || t_ahead < 1)
-        return PCG_E_ARG;
-    const int64_t n_params = pcg_dense_n_params(g->feat_dim, st->emb, g->n_rel);
-    const int64_t o_clf = pcg_dense_param_offset(g->feat_dim, st->emb, g->n_rel, 3, 0);
-    if (n_params < 0 || o_clf < 0) return PCG_E_ARG;
+    if (!g->X || !batch->ids || !batch->labels || batch->B < 1 || !st->clf_next || t_ahead < 1 || state_missing(st)) return PCG_E_ARG;
+    int64_t n_params, o_clf;
+    if (!train_offsets(g, st, &n_params, &o_clf)) return PCG_E_ARG;
     pcg::ClfStep c;
     clf_step_of(c, st, batch, o_clf, n_params);
-    c.clf_out = clf_out;
-    c.count_step = nullptr;
-    c.nodes = batch->ids;
-    c.labels = batch->labels;
-    c.B = batch->B;
-    c.t_ahead = t_ahead;
+    c.clf_out = clf_out; c.count_step = nullptr; c.t_ahead = t_ahead;
+    c.nodes = batch->ids; c.labels = batch->labels; c.B = batch->B;
     return pcg::launch_clf_step(c, *g, static_cast<hipStream_t>(stream));
 }
 

@@ -68,7 +68,7 @@ int pcg_explain_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const floa
             if (rc != PCG_OK) return rc;
         }
         if (want_attr) {
-            rc = pcg::launch_gather_two(g->X, N, q->X, nq, F, g->feat_stride, R * B, d.cnt, w, agg, F, status, d.st);
+            rc = pcg::launch_gather_two(pcg::feat_table(g), q->X, nq, {agg, F, PCG_NORM_COUNT, d.cnt, status}, R * B, w, d.st);
             if (rc != PCG_OK) return rc;
             // dense: the centres are rows of the query table
             rc = pcg::attr_chunk(q, theta, emb, cid, B, w, agg, d.cnt, off, n, w0, w1, out->logits, center_scratch, out->d_self,

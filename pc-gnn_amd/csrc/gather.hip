@@ -318,38 +318,23 @@ static int launch_aggregate(const AggArgs &g, hipStream_t st, bool combine) {
     return PCG_OK;
 }
 
-static void fill_agg_args(AggArgs &a, const float *X, int32_t feat_dim, int32_t feat_stride, int64_t table_rows, int32_t n_rows,
-                          const int32_t *cnt, const Workspace &w, int32_t norm, float *agg, int32_t agg_stride, uint32_t *status) {
-    a.X = X;
-    a.feat_dim = feat_dim;
-    a.feat_stride = feat_stride;
+static AggArgs agg_args(const FeatTable &t, const GatherOut &out, int32_t n_rows, const Workspace &w) {
+    AggArgs a = {};                     // (hm: no translation)
+    a.X = t.X; a.feat_dim = t.feat_dim; a.feat_stride = t.feat_stride; a.table_rows = t.rows;
     a.n_rows = n_rows;
-    a.row_begin = w.row_begin;
-    a.chunk_begin = w.chunk_begin;
-    a.len = w.len;
-    a.cnt = cnt;
-    a.chunk_desc = w.chunk_desc;
-    a.chunk_cap = (int32_t)w.chunk_cap;
-    a.list = w.list;
+    a.row_begin = w.row_begin; a.chunk_begin = w.chunk_begin; a.len = w.len; a.list = w.list;
+    a.chunk_desc = w.chunk_desc; a.chunk_cap = (int32_t)w.chunk_cap; a.partial = w.partial;
     a.n_chunks = w.counters + C_NCHUNK;
-    a.partial = w.partial;
-    a.agg = agg;
-    a.agg_stride = agg_stride;
-    a.norm = norm;
-    a.table_rows = table_rows;
-    a.status = status;
-    a.hm = HaloMap{};
+    a.agg = out.agg; a.agg_stride = out.agg_stride; a.norm = out.norm; a.cnt = out.cnt; a.status = out.status;
+    return a;
 }
 
-int launch_gather_train(const float *X, int32_t feat_dim, int32_t feat_stride, int64_t table_rows, const int32_t *cnt,
-                        const pcg_graph_desc *g, int32_t B, const Workspace &w, float *agg, int32_t agg_stride, uint32_t *status,
+int launch_gather_train(const FeatTable &t, const GatherOut &out, const pcg_graph_desc *g, int32_t B, const Workspace &w,
                         const SideJob &side, hipStream_t st) {
-    if (!X || !cnt || !g || !agg || B < 1 || table_rows < 1) return PCG_E_ARG;
-    if (feat_stride % 4 != 0 || feat_stride < feat_dim || agg_stride < feat_dim) return PCG_E_ARG;
-    if (feat_stride > 512) return PCG_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(X) & 15u) != 0) return PCG_E_ARG;
-    AggArgs a;
-    fill_agg_args(a, X, feat_dim, feat_stride, table_rows, g->n_rel * B, cnt, w, PCG_NORM_COUNT, agg, agg_stride, status);
+    if (!t.X || !out.cnt || !g || !out.agg || B < 1 || t.rows < 1) return PCG_E_ARG;
+    const int rc = check_table(t, TABLE_GATHER, out.agg_stride);
+    if (rc != PCG_OK) return rc;
+    const AggArgs a = agg_args(t, out, g->n_rel * B, w);
     const int extra = side.n_adam_blocks + side.n_wgrad_blocks + side.n_key_blocks + side.n_score_blocks;
     // workgroups of the gather group: half the stand-alone launch's - the riders' workgroups are dispatched behind them, and at
     // dataset scale most of the 2048 found no chunk (measured, 2048 / 1024 / 512: YelpChi-like 53.3 / 51.9 / 52.8 us per step,
@@ -358,7 +343,7 @@ int launch_gather_train(const float *X, int32_t feat_dim, int32_t feat_stride, i
 #define PCG_GT_BLOCKS (GATHER_BLOCKS / 2)
 #endif
     const int gb = PCG_GT_BLOCKS;
-    if (feat_stride <= 256)
+    if (t.feat_stride <= 256)
         hipLaunchKernelGGL(gather_train_kernel<1>, dim3(gb + extra), dim3(256), 0, st, a, side, gb, g->n_nodes, g->train_pos, g->n_pos);
     else
         hipLaunchKernelGGL(gather_train_kernel<2>, dim3(gb + extra), dim3(256), 0, st, a, side, gb, g->n_nodes, g->train_pos, g->n_pos);
@@ -366,40 +351,36 @@ int launch_gather_train(const float *X, int32_t feat_dim, int32_t feat_stride, i
     return PCG_OK;
 }
 
-// (declared in infer.hip) lists of node ids -> rows of [ owned | train-pos ] in X or of the inference halo (hm: its hash table,
+// (declared in infer.hip) lists of node ids -> rows of [ owned | train-pos ] in t.X or of the inference halo (hm: its hash table,
 // halo_base = n_local + n_pos, halo_cap rows at halo_X); multi-chunk rows left as partial sums for the dense launch
-int launch_gather_infer(const float *X, int32_t feat_dim, int32_t feat_stride, int32_t n_rows, const int32_t *cnt, const Workspace &w,
-                        float *agg, int32_t agg_stride, uint32_t *status, const HaloMap &hm, const float *halo_X, hipStream_t st) {
-    if (!X || !cnt || !agg || !halo_X || n_rows < 1 || !hm.keys) return PCG_E_ARG;
-    if (feat_stride % 4 != 0 || feat_stride < feat_dim || agg_stride < feat_dim) return PCG_E_ARG;
-    if (feat_stride > 512) return PCG_E_UNSUPPORTED;
-    if (((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(halo_X)) & 15u) != 0) return PCG_E_ARG;
-    AggArgs a;
-    // (table_rows: every row number a translation can produce - the halo's rows are addressed in halo_X)
-    fill_agg_args(a, X, feat_dim, feat_stride, (int64_t)hm.halo_base + hm.halo_cap, n_rows, cnt, w, PCG_NORM_COUNT, agg, agg_stride,
-                  status);
+// (t.rows is not read: every row number a translation can produce is in range - the halo's rows are addressed in halo_X)
+int launch_gather_infer(const FeatTable &t, const GatherOut &out, int32_t n_rows, const Workspace &w, const HaloMap &hm,
+                        const float *halo_X, hipStream_t st) {
+    if (!t.X || !out.cnt || !out.agg || !halo_X || n_rows < 1 || !hm.keys) return PCG_E_ARG;
+    const int rc = check_table(t, TABLE_GATHER, out.agg_stride);
+    if (rc != PCG_OK) return rc;
+    if ((reinterpret_cast<uintptr_t>(halo_X) & 15u) != 0) return PCG_E_ARG;
+    AggArgs a = agg_args({t.X, t.feat_dim, t.feat_stride, (int64_t)hm.halo_base + hm.halo_cap}, out, n_rows, w);
     a.hm = hm;
-    if (feat_stride <= 256) hipLaunchKernelGGL(gather_chunks_infer<1>, dim3(GATHER_BLOCKS), dim3(256), 0, st, a, halo_X);
+    if (t.feat_stride <= 256) hipLaunchKernelGGL(gather_chunks_infer<1>, dim3(GATHER_BLOCKS), dim3(256), 0, st, a, halo_X);
     else hipLaunchKernelGGL(gather_chunks_infer<2>, dim3(GATHER_BLOCKS), dim3(256), 0, st, a, halo_X);
     PCG_LAUNCH_CHECK();
     return PCG_OK;
 }
 
-// (declared in infer_new.hip) lists of ids in [0, base_rows + query_rows): id < base_rows -> row id of X, else row id - base_rows
+// (declared in infer.h) lists of ids in [0, t.rows + query_rows): id < t.rows -> row id of t.X, else row id - t.rows
 // of query_X (both [.., feat_stride]); an id beyond both is skipped (PCG_ST_LIST_ID_RANGE); multi-chunk rows left as partial
 // sums for the dense launch.  Chunking and summation order per row: gather_chunks' (the same body).
-int launch_gather_two(const float *X, int64_t base_rows, const float *query_X, int64_t query_rows, int32_t feat_dim,
-                      int32_t feat_stride, int32_t n_rows, const int32_t *cnt, const Workspace &w, float *agg, int32_t agg_stride,
-                      uint32_t *status, hipStream_t st) {
-    if (!X || !query_X || !cnt || !agg || n_rows < 1 || base_rows < 1 || query_rows < 1) return PCG_E_ARG;
-    if (base_rows + query_rows >= (1ll << 31)) return PCG_E_ARG;
-    if (feat_stride % 4 != 0 || feat_stride < feat_dim || agg_stride < feat_dim) return PCG_E_ARG;
-    if (feat_stride > 512) return PCG_E_UNSUPPORTED;
-    if (((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(query_X)) & 15u) != 0) return PCG_E_ARG;
-    AggArgs a;
-    fill_agg_args(a, X, feat_dim, feat_stride, base_rows + query_rows, n_rows, cnt, w, PCG_NORM_COUNT, agg, agg_stride, status);
-    a.hm.halo_base = (int32_t)base_rows;
-    if (feat_stride <= 256) hipLaunchKernelGGL(gather_chunks_two<1>, dim3(GATHER_BLOCKS), dim3(256), 0, st, a, query_X);
+int launch_gather_two(const FeatTable &t, const float *query_X, int64_t query_rows, const GatherOut &out, int32_t n_rows,
+                      const Workspace &w, hipStream_t st) {
+    if (!t.X || !query_X || !out.cnt || !out.agg || n_rows < 1 || t.rows < 1 || query_rows < 1) return PCG_E_ARG;
+    if (t.rows + query_rows >= (1ll << 31)) return PCG_E_ARG;
+    const int rc = check_table(t, TABLE_GATHER, out.agg_stride);
+    if (rc != PCG_OK) return rc;
+    if ((reinterpret_cast<uintptr_t>(query_X) & 15u) != 0) return PCG_E_ARG;
+    AggArgs a = agg_args({t.X, t.feat_dim, t.feat_stride, t.rows + query_rows}, out, n_rows, w);
+    a.hm.halo_base = (int32_t)t.rows;
+    if (t.feat_stride <= 256) hipLaunchKernelGGL(gather_chunks_two<1>, dim3(GATHER_BLOCKS), dim3(256), 0, st, a, query_X);
     else hipLaunchKernelGGL(gather_chunks_two<2>, dim3(GATHER_BLOCKS), dim3(256), 0, st, a, query_X);
     PCG_LAUNCH_CHECK();
     return PCG_OK;
@@ -409,28 +390,30 @@ int launch_gather_two(const float *X, int64_t base_rows, const float *query_X, i
 
 extern "C" {
 
-static int aggregate(const float *X, int32_t feat_dim, int32_t feat_stride, int64_t table_rows, int32_t n_rows, const int32_t *cnt,
-                     const pcg_graph_desc *g, int32_t B, void *workspace, int64_t list_capacity, int32_t norm,
-                     float *agg, int32_t agg_stride, bool combine, uint32_t *status, void *stream, const void *plan = nullptr) {
-    if (!X || !cnt || !g || !workspace || !agg || n_rows < 0 || B < 0 || table_rows < 1) return PCG_E_ARG;
-    if (n_rows != g->n_rel * B) return PCG_E_ARG;       // the lists are those of the plan in `workspace`: n_rel * B rows
+struct ListsAt {               // where a batch's lists lie: the workspace a selection call of B centres wrote them to
+    const pcg_graph_desc *g;
+    int32_t B;
+    void *workspace;
+    const void *plan;          // null: inside the workspace
+    int64_t list_capacity;
+};
+
+static int aggregate(const pcg::FeatTable &t, const pcg::GatherOut &out, int32_t n_rows, const ListsAt &at, bool combine, void *stream) {
+    if (!t.X || !out.cnt || !at.g || !at.workspace || !out.agg || n_rows < 0 || at.B < 0 || t.rows < 1) return PCG_E_ARG;
+    if (n_rows != at.g->n_rel * at.B) return PCG_E_ARG;       // the lists are those of the plan in `workspace`: n_rel * B rows
     if (n_rows == 0) return PCG_OK;
-    if (feat_stride % 4 != 0 || feat_stride < feat_dim || agg_stride < feat_dim) return PCG_E_ARG;
-    if (feat_stride > 512) return PCG_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(X) & 15u) != 0) return PCG_E_ARG;
-    pcg::Workspace w;
-    pcg::carve1(g, B, list_capacity, static_cast<unsigned char *>(workspace), &w, static_cast<unsigned char *>(const_cast<void *>(plan)));
-    pcg::AggArgs a;
-    pcg::fill_agg_args(a, X, feat_dim, feat_stride, table_rows, n_rows, cnt, w, norm, agg, agg_stride, status);
+    const int rc = pcg::check_table(t, pcg::TABLE_GATHER, out.agg_stride);
+    if (rc != PCG_OK) return rc;
+    const pcg::AggArgs a = pcg::agg_args(t, out, n_rows, pcg::carve_for(at.g, at.B, at.list_capacity, at.workspace, at.plan));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return feat_stride <= 256 ? pcg::launch_aggregate<1>(a, st, combine) : pcg::launch_aggregate<2>(a, st, combine);
+    return t.feat_stride <= 256 ? pcg::launch_aggregate<1>(a, st, combine) : pcg::launch_aggregate<2>(a, st, combine);
 }
 
 int pcg_aggregate_lists(const float *X, int32_t feat_dim, int32_t feat_stride, int64_t table_rows, int32_t n_rows,
                         const int32_t *cnt, const pcg_graph_desc *g, int32_t B, void *workspace, int64_t list_capacity,
                         int32_t norm, float *agg, int32_t agg_stride, uint32_t *status, void *stream) {
-    return aggregate(X, feat_dim, feat_stride, table_rows, n_rows, cnt, g, B, workspace, list_capacity, norm, agg, agg_stride, true,
-                     status, stream);
+    return aggregate({X, feat_dim, feat_stride, table_rows}, {agg, agg_stride, norm, cnt, status}, n_rows,
+                     {g, B, workspace, nullptr, list_capacity}, true, stream);
 }
 
 /* gather only: rows of one chunk are finished (mean in agg), rows of several are left as per-chunk partial sums in the
@@ -438,16 +421,16 @@ int pcg_aggregate_lists(const float *X, int32_t feat_dim, int32_t feat_stride, i
 int pcg_gather_lists(const float *X, int32_t feat_dim, int32_t feat_stride, int64_t table_rows, int32_t n_rows,
                      const int32_t *cnt, const pcg_graph_desc *g, int32_t B, void *workspace, int64_t list_capacity, float *agg,
                      int32_t agg_stride, uint32_t *status, void *stream) {
-    return aggregate(X, feat_dim, feat_stride, table_rows, n_rows, cnt, g, B, workspace, list_capacity, PCG_NORM_COUNT, agg,
-                     agg_stride, false, status, stream);
+    return aggregate({X, feat_dim, feat_stride, table_rows}, {agg, agg_stride, PCG_NORM_COUNT, cnt, status}, n_rows,
+                     {g, B, workspace, nullptr, list_capacity}, false, stream);
 }
 
 /* the same with the batch's plan part outside the workspace (pcg_plan_batches; plan == NULL: inside, as pcg_gather_lists) */
 int pcg_gather_lists_planned(const float *X, int32_t feat_dim, int32_t feat_stride, int64_t table_rows, int32_t n_rows,
                              const int32_t *cnt, const pcg_graph_desc *g, int32_t B, void *workspace, const void *plan,
                              int64_t list_capacity, float *agg, int32_t agg_stride, uint32_t *status, void *stream) {
-    return aggregate(X, feat_dim, feat_stride, table_rows, n_rows, cnt, g, B, workspace, list_capacity, PCG_NORM_COUNT, agg,
-                     agg_stride, false, status, stream, plan);
+    return aggregate({X, feat_dim, feat_stride, table_rows}, {agg, agg_stride, PCG_NORM_COUNT, cnt, status}, n_rows,
+                     {g, B, workspace, plan, list_capacity}, false, stream);
 }
 
 /* pcg_gather_lists_planned for a partitioned rank (pc-gnn_amd/dist.py): the lists hold NODE ids; the gather translates them to rows
@@ -461,20 +444,18 @@ int pcg_gather_lists_dist(const float *X, int32_t feat_dim, int32_t feat_stride,
                           int32_t n_local, const int32_t *pos_ids, const int32_t *pos_idx, int32_t n_pos, const uint32_t *table,
                           int64_t table_slots, uint32_t *counts, int32_t halo_cap, int32_t halo_base, const float *theta,
                           const float *m, const float *v, int64_t clf_offset, int32_t clf_n, float *snap_dst, void *stream) {
+    const pcg::FeatTable t = {X, feat_dim, feat_stride, table_rows};
+    const pcg::GatherOut out = {agg, agg_stride, PCG_NORM_COUNT, cnt, status};
     if (!X || !cnt || !g || !workspace || !agg || n_rows < 0 || B < 0 || table_rows < 1) return PCG_E_ARG;
     if (n_rows != g->n_rel * B) return PCG_E_ARG;
     if (n_rows == 0) return PCG_OK;
-    if (feat_stride % 4 != 0 || feat_stride < feat_dim || agg_stride < feat_dim) return PCG_E_ARG;
-    if (feat_stride > 512) return PCG_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(X) & 15u) != 0) return PCG_E_ARG;
+    const int rc = pcg::check_table(t, pcg::TABLE_GATHER, agg_stride);
+    if (rc != PCG_OK) return rc;
     if (!table || !counts || table_slots < 1024 || (table_slots & (table_slots - 1)) != 0 || lo > hi || n_pos < 0 ||
         (n_pos > 0 && (!pos_ids || !pos_idx)))
         return PCG_E_ARG;
     if (snap_dst && (!theta || !m || !v || clf_n < 1 || clf_offset < 0)) return PCG_E_ARG;
-    pcg::Workspace w;
-    pcg::carve1(g, B, list_capacity, static_cast<unsigned char *>(workspace), &w, static_cast<unsigned char *>(const_cast<void *>(plan)));
-    pcg::AggArgs a;
-    pcg::fill_agg_args(a, X, feat_dim, feat_stride, table_rows, n_rows, cnt, w, PCG_NORM_COUNT, agg, agg_stride, status);
+    pcg::AggArgs a = pcg::agg_args(t, out, n_rows, pcg::carve_for(g, B, list_capacity, workspace, plan));
     a.hm.keys = table;
     a.hm.vals = table + table_slots;
     a.hm.mask = (uint32_t)(table_slots - 1);
@@ -486,8 +467,7 @@ int pcg_gather_lists_dist(const float *X, int32_t feat_dim, int32_t feat_stride,
     sc.src[0] = theta ? theta + clf_offset : nullptr;
     sc.src[1] = m ? m + clf_offset : nullptr;
     sc.src[2] = v ? v + clf_offset : nullptr;
-    sc.dst = snap_dst;
-    sc.n = clf_n;
+    sc.dst = snap_dst; sc.n = clf_n;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (feat_stride <= 256) hipLaunchKernelGGL(pcg::gather_chunks_dist<1>, dim3(pcg::GATHER_BLOCKS), dim3(256), 0, st, a, sc);
     else hipLaunchKernelGGL(pcg::gather_chunks_dist<2>, dim3(pcg::GATHER_BLOCKS), dim3(256), 0, st, a, sc);
@@ -499,8 +479,8 @@ int pcg_gather_lists_dist(const float *X, int32_t feat_dim, int32_t feat_stride,
 int pcg_aggregate_lists_planned(const float *X, int32_t feat_dim, int32_t feat_stride, int64_t table_rows, int32_t n_rows,
                                 const int32_t *cnt, const pcg_graph_desc *g, int32_t B, void *workspace, const void *plan,
                                 int64_t list_capacity, int32_t norm, float *agg, int32_t agg_stride, uint32_t *status, void *stream) {
-    return aggregate(X, feat_dim, feat_stride, table_rows, n_rows, cnt, g, B, workspace, list_capacity, norm, agg, agg_stride, true,
-                     status, stream, plan);
+    return aggregate({X, feat_dim, feat_stride, table_rows}, {agg, agg_stride, norm, cnt, status}, n_rows,
+                     {g, B, workspace, plan, list_capacity}, true, stream);
 }
 
 }  // extern "C"

@@ -114,10 +114,9 @@ int infer_new_descs(const pcg_graph_desc *g, const pcg_graph_desc *q);
 // table's scores -> s0[0, N), only when score_base] || the query rows' scores -> s0[N, N + nq) || d's look-back words zeroed
 int launch_infer_new_front(const pcg_graph_desc *g, const pcg_graph_desc *q, const float *theta, int32_t emb, float *s0,
                            int32_t score_base, const ChunkDriver &d);
-// gather.hip: lists of ids in [0, base_rows + query_rows): id < base_rows -> row id of X, else row id - base_rows of query_X
-int launch_gather_two(const float *X, int64_t base_rows, const float *query_X, int64_t query_rows, int32_t feat_dim,
-                      int32_t feat_stride, int32_t n_rows, const int32_t *cnt, const Workspace &w, float *agg, int32_t agg_stride,
-                      uint32_t *status, hipStream_t st);
+// gather.hip: lists of ids in [0, t.rows + query_rows): id < t.rows -> row id of t.X, else row id - t.rows of query_X
+int launch_gather_two(const FeatTable &t, const float *query_X, int64_t query_rows, const GatherOut &out, int32_t n_rows,
+                      const Workspace &w, hipStream_t st);
 
 // rank.hip: the two rank launches over the lists (and the plan) in `w` - rows (r, b), b < B, of a chunk that is ids
 // [b_off, b_off + B) of the call's n_total, written at out_begin[r * n_total + b_off + b].  g: the graph whose rows were planned

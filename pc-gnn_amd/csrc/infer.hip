@@ -190,8 +190,8 @@ int infer_dense(const pcg_graph_desc *g, const float *theta, int32_t emb, const 
 
 // ---- partitioned inference (pcg_infer_chunk_dist, pc-gnn_amd/dist.py) ------------------------------------------------------
 // gather.hip
-int launch_gather_infer(const float *X, int32_t feat_dim, int32_t feat_stride, int32_t n_rows, const int32_t *cnt, const Workspace &w,
-                        float *agg, int32_t agg_stride, uint32_t *status, const HaloMap &hm, const float *halo_X, hipStream_t st);
+int launch_gather_infer(const FeatTable &t, const GatherOut &out, int32_t n_rows, const Workspace &w, const HaloMap &hm,
+                        const float *halo_X, hipStream_t st);
 
 // A chunk's front: workgroups [0, n_tab) score the rank's table rows [0, n_tab_rows) (owned | train-pos: the first chunk of a
 // call only) -> s0[tab_ids[row]]; [n_tab, n_tab + n_halo) score the inference halo rows -> s0[halo_ids[row]] (-1: unused slot,
@@ -311,7 +311,7 @@ int pcg_infer_chunk_dist(const pcg_graph_desc *g, const float *theta, int32_t em
     hm.halo_cap = halo_cap; hm.halo_base = (int32_t)halo_base;
     hm.overflow = counts + 128;
     return d.run([&](int64_t, int32_t, const int32_t *, const pcg::Workspace &w) {
-        const int rc = pcg::launch_gather_infer(g->X, F, g->feat_stride, R * B, d.cnt, w, agg, F, status, hm, halo_X, d.st);
+        const int rc = pcg::launch_gather_infer(pcg::feat_table(g), {agg, F, PCG_NORM_COUNT, d.cnt, status}, R * B, w, hm, halo_X, d.st);
         if (rc != PCG_OK) return rc;
         // dense: the centres are local table rows
         return pcg::infer_dense(g, theta, emb, ids, B, w, agg, d.cnt, out_logits, out_center ? out_center : center_scratch, d.st);

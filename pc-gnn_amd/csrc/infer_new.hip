@@ -102,7 +102,7 @@ int pcg_infer_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float 
     if (rc != PCG_OK) return rc;
 
     return d.run([&](int64_t off, int32_t B, const int32_t *cid, const pcg::Workspace &w) {
-        const int rc = pcg::launch_gather_two(g->X, N, q->X, nq, F, g->feat_stride, R * B, d.cnt, w, agg, F, status, d.st);
+        const int rc = pcg::launch_gather_two(pcg::feat_table(g), q->X, nq, {agg, F, PCG_NORM_COUNT, d.cnt, status}, R * B, w, d.st);
         if (rc != PCG_OK) return rc;
         // dense: the centres are rows of the query table
         return pcg::infer_dense(q, theta, emb, cid, B, w, agg, d.cnt, out_logits + 2 * off,
