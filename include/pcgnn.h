@@ -654,6 +654,42 @@ int64_t pcg_infer_new_workspace_bytes(const pcg_graph_desc *g, const pcg_graph_d
 int pcg_infer_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float *theta, int32_t emb, const int32_t *ids, int32_t n,
                   int32_t chunk_rows, float *s0, int32_t score_base, const double *thresholds, void *workspace,
                   int64_t list_capacity, float *out_logits, float *out_center, uint32_t *status, void *stream);
+/* Node embeddings from the whole-set pass (FusedPCGNN.embed, embed_new).  pcg_embed_set / pcg_embed_new are pcg_infer_set /
+ * pcg_infer_new - the same arguments, checks, workspace (pcg_infer_workspace_bytes / pcg_infer_new_workspace_bytes) and launches -
+ * whose dense launch also stores what the classifier sees:
+ *   out_emb [n][emb]          row i = combined = relu([self | h_1 .. h_R] W_inter), the row W_cls multiplies;
+ *   out_rel [n][n_rel * emb]  row i = h_1 | .. | h_R, h_r = relu([self | agg_r] W_intra[r]); or NULL.
+ * out_logits, out_center and out_emb may each be NULL too; all four NULL is PCG_E_ARG.
+ * Parity: out_emb row i is bit for bit what pcg_train_dense (labels NULL) writes to pcg_dense_out.combined for that node, whatever
+ * the chunk, tile or position of the row; the logits are bit for bit pcg_infer_set's / pcg_infer_new's; pcg_embed_new's rows equal
+ * pcg_embed_set's for node N + j on the graph built with the query rows appended. */
+int pcg_embed_set(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *ids, int32_t n, int32_t chunk_rows,
+                  float *s0, const double *thresholds, void *workspace, int64_t list_capacity, float *out_logits, float *out_center,
+                  float *out_emb, float *out_rel, uint32_t *status, void *stream);
+int pcg_embed_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float *theta, int32_t emb, const int32_t *ids, int32_t n,
+                  int32_t chunk_rows, float *s0, int32_t score_base, const double *thresholds, void *workspace,
+                  int64_t list_capacity, float *out_logits, float *out_center, float *out_emb, float *out_rel, uint32_t *status,
+                  void *stream);
+/* The k most similar rows of bank [M][emb] for every row of Q [n][emb] (both float32, row-major, 16-byte aligned), without an
+ * [n][M] matrix: exact-f32 MFMA scores and a running top-k (FusedPCGNN.nearest, ops.topk_similar).
+ * metric - the score is always MAXIMISED: 0 dot q.c;  1 cosine q.c / (|q| |c|), 0 when either norm is 0;
+ *          2 l2 min(0, 2 q.c - |q|^2 - |c|^2).  A NaN score counts as -inf.
+ * q_ids [n], bank_ids [M]: both or neither (one alone: PCG_E_ARG); candidate c is skipped for row i when bank_ids[c] == q_ids[i].
+ * out_pos [n][k] (bank positions), out_score [n][k]: sorted by score descending, ties by lower position; slots beyond the number of
+ * eligible candidates hold position -1 and score -inf.  The result is a function of the scores alone: it does not depend on the
+ * grid, on how the bank is sliced over waves (partial lists are merged by the same (score, position) key), nor on any arrival
+ * order - there are no atomics.  A pair's score is its own arithmetic whatever tile it is in.
+ * Ranges: 1 <= k <= 64 (else PCG_E_ARG); emb % 16 == 0, 16 <= emb <= 512 (else PCG_E_UNSUPPORTED); n, M >= 0 (negative:
+ * PCG_E_ARG); n == 0: nothing is enqueued; M == 0: all padding.  workspace: pcg_topk_similar_workspace_bytes(n, M, emb, k) bytes
+ * (negative = rejected arguments; non-decreasing in n and M), no initial contents required.  status is reserved: nothing is
+ * detected on the device, the word is not written.  Launches: [row norms, metrics 1 and 2] -> scan -> [merge, when the bank was
+ * sliced].  Never synchronises, never allocates.
+ * pcg_debug_set_topk_slices(s): tests only - s > 0 asks for s bank slices (clamped to what the workspace holds), 0 = choose. */
+int64_t pcg_topk_similar_workspace_bytes(int32_t n, int32_t M, int32_t emb, int32_t k);
+int pcg_topk_similar(const float *Q, int32_t n, const float *bank, int32_t M, int32_t emb, int32_t k, int32_t metric,
+                     const int32_t *q_ids, const int32_t *bank_ids, int32_t *out_pos, float *out_score, void *workspace,
+                     uint32_t *status, void *stream);
+void pcg_debug_set_topk_slices(int32_t n_slices);
 /* The chosen neighbours of test-mode rows in the reference's order, with their distances (choose_step_test's samp_neighs /
  * samp_scores, src/layers.py:713-736; FusedPCGNN.chosen, ops.choose_ranked).
  * pcg_rank_lists: over the lists (and the plan) a pcg_choose_select* call in TEST mode (train_flag = 0, add_self = 0) left in

@@ -139,6 +139,11 @@ PROTOTYPES = {
                                        C.POINTER(_F64), _P, _I32, _I64, _P, _P, _P, _P]),
     "pcg_infer_new_workspace_bytes": (_I64, [_G, _G, _I32, _I32, _I64]),
     "pcg_infer_new": (C.c_int, [_G, _G, _P, _I32, _P, _I32, _I32, _P, _I32, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P]),
+    "pcg_embed_set": (C.c_int, [_G, _P, _I32, _P, _I32, _I32, _P, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "pcg_embed_new": (C.c_int, [_G, _G, _P, _I32, _P, _I32, _I32, _P, _I32, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "pcg_topk_similar_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
+    "pcg_topk_similar": (C.c_int, [_P, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "pcg_debug_set_topk_slices": (None, [_I32]),
     "pcg_explain_new_workspace_bytes": (_I64, [_G, _G, _I32, _I32, _I64]),
     "pcg_explain_new": (C.c_int, [_G, _G, _P, _I32, _P, _I32, _I32, _P, _I32, C.POINTER(_F64), _P, _I64, C.c_float, C.c_float, _XOUT,
                                   _P, _P]),

@@ -200,9 +200,11 @@ __device__ __forceinline__ float row16_sum(float p) {
 // only): row b's seeds are d_logits[2b], d_logits[2b + 1] (d loss / d gnn logits) and d_center[2b], d_center[2b + 1] (d loss / d
 // label-aware logits), used as given - no 1 / count, no lambda_1, no label read, no row loss; rows beyond the batch get zeros.
 // Everything behind the loss phase reads only s_dlog / s_dcl and the forward's LDS state, so nothing else differs.
+// h_out (INFER only, else not looked at; pcg_embed_set / pcg_embed_new): row b's relation embeddings h_1 | .. | h_R -> h_out[b][R * E],
+// copied out of s_cat behind the h_r phase's barrier.  The other launches leave it at its default and the copy folds away.
 template <bool WLDS, int F_, int E_, int R_, bool INFER = false, bool STAGE_W = true, bool EXT = false>
 __device__ __forceinline__ void dense_tile_body(const DenseArgs &a, int bid, float *sm, const float *__restrict__ d_logits = nullptr,
-                                                const float *__restrict__ d_center = nullptr) {
+                                                const float *__restrict__ d_center = nullptr, float *__restrict__ h_out = nullptr) {
     // bid: this workgroup's index among the tiles' workgroups (a.n_tile_blocks of them); sm: the launch's dynamic LDS
     const int F = F_ > 0 ? F_ : a.feat_dim, E = E_ > 0 ? E_ : a.emb, R = R_ > 0 ? R_ : a.n_rel;
     const int K1 = 2 * F, K1p = (K1 + KPAD - 1) / KPAD * KPAD, K2 = F + R * E, K2p = (K2 + KPAD - 1) / KPAD * KPAD;
@@ -410,6 +412,16 @@ __device__ __forceinline__ void dense_tile_body(const DenseArgs &a, int bid, flo
     }
     __syncthreads();
     DENSE_STAMP(2);
+    if constexpr (INFER) {
+        if (h_out) {                                                       // (uniform: a kernel argument)
+            // consecutive threads store consecutive floats of a row's R * E (s_cat's columns behind the self columns)
+            const int RE = R * E;
+            for (int i = tid; i < TB * RE; i += DENSE_THREADS) {
+                const int t = i / RE, c = i - t * RE, b = row0 + t;
+                if (b < a.B) h_out[(size_t)b * RE + c] = s_cat[t * ld2 + F + c];
+            }
+        }
+    }
     // ---- combined = relu(cat W)   (layers.py:284-289): the K dimension of every output tile split over `kparts` waves,
     //      their partial tiles added in a fixed order ----------------------------------------------------------------
     {

@@ -34,11 +34,13 @@ struct InferCarve {
 // infer.hip
 int infer_carve(const pcg_graph_desc *g, int n_slots, bool dense, int32_t emb, int32_t chunk_rows, int64_t list_capacity, InferCarve &c);
 bool infer_wlds(int F, int E, int R);
-int launch_infer_dense(const DenseArgs &a, int B, hipStream_t st);
+int launch_infer_dense(const DenseArgs &a, int B, hipStream_t st, float *h_out = nullptr);
 // the forward-only dense launch of a chunk whose lists were gathered into agg ([R][B][F]; rows of several chunks: partial sums in
-// w): centres `nodes` are rows of g's table -> out_logits, out_center [B][2]
+// w): centres `nodes` are rows of g's table -> out_logits, out_center [B][2]; out_emb [B][emb] (`combined`) and out_rel
+// [B][n_rel * emb] (h_1 | .. | h_R) where not NULL (pcg_embed_set, pcg_embed_new)
 int infer_dense(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *nodes, int32_t B, const Workspace &w,
-                float *agg, const int32_t *cnt, float *out_logits, float *out_center, hipStream_t st);
+                float *agg, const int32_t *cnt, float *out_logits, float *out_center, hipStream_t st, float *out_emb = nullptr,
+                float *out_rel = nullptr);
 // the zeroing workgroups a front kernel needs for z
 inline int infer_zero_blocks(const ZeroRegions &z) {
     return (int)((z.n[0] + z.n[1] + z.n[2] + z.n[3] + INFER_ZERO_WORDS - 1) / INFER_ZERO_WORDS);

@@ -42,15 +42,17 @@ int launch_infer_front(const pcg_graph_desc *g, const float *W, const float *bia
 
 // PERSIST: tile blockIdx.x, then + gridDim.x, ...; else one tile per workgroup (the run-time shapes: a loop around their
 // run-time index arithmetic needs more than the 128 VGPRs a 1024-thread workgroup has - it spilled)
+// h_out: NULL, or [B][n_rel * emb] for every row's h_1 | .. | h_R (pcg_embed_set, pcg_embed_new; a.combined is their out_emb).
+// No instantiation has scratch with the store in, and none lost occupancy (profiles/r26/kernel_resources.txt).
 template <bool WLDS, int F_, int E_, int R_, bool PERSIST>
-__global__ void __launch_bounds__(DENSE_THREADS) infer_dense_kernel(const DenseArgs a, int n_tiles) {
+__global__ void __launch_bounds__(DENSE_THREADS) infer_dense_kernel(const DenseArgs a, int n_tiles, float *__restrict__ h_out) {
     extern __shared__ __align__(16) float sm[];
     int tile = (int)blockIdx.x;                       // (gridDim.x <= n_tiles: every workgroup has a first tile)
-    dense_tile_body<WLDS, F_, E_, R_, true, true>(a, tile, sm);
+    dense_tile_body<WLDS, F_, E_, R_, true, true>(a, tile, sm, nullptr, nullptr, h_out);
     if constexpr (PERSIST) {
         for (tile += (int)gridDim.x; tile < n_tiles; tile += (int)gridDim.x) {
             __syncthreads();                          // (the tile before: its last phase's LDS reads)
-            dense_tile_body<WLDS, F_, E_, R_, true, false>(a, tile, sm);
+            dense_tile_body<WLDS, F_, E_, R_, true, false>(a, tile, sm, nullptr, nullptr, h_out);
         }
     }
 }
@@ -80,11 +82,11 @@ static int infer_blocks(int B) {
     return n_tiles < cus ? n_tiles : cus;
 }
 
-int launch_infer_dense(const DenseArgs &a, int B, hipStream_t st) {
+int launch_infer_dense(const DenseArgs &a, int B, hipStream_t st, float *h_out) {
     const int F = a.feat_dim, E = a.emb, R = a.n_rel;
     const bool wlds = infer_wlds(F, E, R);
     const size_t smem = dense_smem_bytes(F, E, R, wlds);
-    typedef void (*kern_t)(const DenseArgs, int);
+    typedef void (*kern_t)(const DenseArgs, int, float *);
     kern_t kern;
     bool persist = true;
     if (R == 3 && F == 32 && E == 64 && wlds) kern = infer_dense_kernel<true, 32, 64, 3, true>;
@@ -109,7 +111,7 @@ int launch_infer_dense(const DenseArgs &a, int B, hipStream_t st) {
             }
     }
     const int n_tiles = (B + TB - 1) / TB;
-    hipLaunchKernelGGL(kern, dim3(persist ? infer_blocks(B) : n_tiles), dim3(DENSE_THREADS), smem, st, a, n_tiles);
+    hipLaunchKernelGGL(kern, dim3(persist ? infer_blocks(B) : n_tiles), dim3(DENSE_THREADS), smem, st, a, n_tiles, h_out);
     PCG_LAUNCH_CHECK();
     return PCG_OK;
 }
@@ -173,7 +175,7 @@ ChunkDriver infer_driver(const pcg_graph_desc *g, const int32_t *ids, int32_t n,
 }
 
 int infer_dense(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *nodes, int32_t B, const Workspace &w,
-                float *agg, const int32_t *cnt, float *out_logits, float *out_center, hipStream_t st) {
+                float *agg, const int32_t *cnt, float *out_logits, float *out_center, hipStream_t st, float *out_emb, float *out_rel) {
     DenseExtra x;
     x.chunk_begin = w.chunk_begin;
     x.partial = w.partial;
@@ -182,10 +184,10 @@ int infer_dense(const pcg_graph_desc *g, const float *theta, int32_t emb, const 
     DenseArgs a;
     int n_sort_blocks = 0;
     const int rc = dense_args(a, n_sort_blocks, g, theta, emb, nodes, nullptr, B, agg, g->feat_dim, 0.f, 1.f, out_logits, out_center,
-                              nullptr, nullptr, nullptr, nullptr, x);
+                              out_emb, nullptr, nullptr, nullptr, x);
     if (rc != PCG_OK) return rc;
     a.stamps = nullptr;
-    return launch_infer_dense(a, B, st);
+    return launch_infer_dense(a, B, st, out_rel);
 }
 
 // ---- partitioned inference (pcg_infer_chunk_dist, pc-gnn_amd/dist.py) ------------------------------------------------------
@@ -228,10 +230,13 @@ int64_t pcg_infer_workspace_bytes(const pcg_graph_desc *g, int32_t emb, int32_t 
 
 int32_t pcg_infer_blocks(int32_t chunk_rows) { return chunk_rows < 1 ? PCG_E_ARG : pcg::infer_blocks(chunk_rows); }
 
-int pcg_infer_set(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *ids, int32_t n, int32_t chunk_rows,
-                  float *s0, const double *thresholds, void *workspace, int64_t list_capacity, float *out_logits, float *out_center,
-                  uint32_t *status, void *stream) {
-    if (!g || !g->X || !theta || !ids || n < 0 || !s0 || !thresholds || !workspace || !out_logits || !status) return PCG_E_ARG;
+// pcg_infer_set (out_emb, out_rel NULL, out_logits required by its caller) and pcg_embed_set: a NULL out_logits / out_center goes
+// to the workspace's centre scratch (the same lane stores both pairs; nobody reads them)
+static int infer_set_impl(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *ids, int32_t n, int32_t chunk_rows,
+                          float *s0, const double *thresholds, void *workspace, int64_t list_capacity, float *out_logits,
+                          float *out_center, float *out_emb, float *out_rel, uint32_t *status, void *stream) {
+    if (!g || !g->X || !theta || !ids || n < 0 || !s0 || !thresholds || !workspace || !status) return PCG_E_ARG;
+    if (!out_logits && !out_center && !out_emb && !out_rel) return PCG_E_ARG;
     if (!pcg::infer_table_ok(g)) return PCG_E_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(g->X) & 15u) != 0) return PCG_E_ARG;
     pcg::InferCarve c;
@@ -254,9 +259,25 @@ int pcg_infer_set(const pcg_graph_desc *g, const float *theta, int32_t emb, cons
         const int rc = pcg_gather_lists_planned(g->X, F, g->feat_stride, g->n_nodes, R * B, d.cnt, g, B, d.data, w.counters,
                                                 list_capacity, agg, F, status, stream);
         if (rc != PCG_OK) return rc;
-        return pcg::infer_dense(g, theta, emb, cid, B, w, agg, d.cnt, out_logits + 2 * off,
-                                out_center ? out_center + 2 * off : center_scratch, d.st);
+        return pcg::infer_dense(g, theta, emb, cid, B, w, agg, d.cnt, out_logits ? out_logits + 2 * off : center_scratch,
+                                out_center ? out_center + 2 * off : center_scratch, d.st,
+                                out_emb ? out_emb + (int64_t)E * off : nullptr, out_rel ? out_rel + (int64_t)R * E * off : nullptr);
     });
+}
+
+int pcg_infer_set(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *ids, int32_t n, int32_t chunk_rows,
+                  float *s0, const double *thresholds, void *workspace, int64_t list_capacity, float *out_logits, float *out_center,
+                  uint32_t *status, void *stream) {
+    if (!out_logits) return PCG_E_ARG;
+    return infer_set_impl(g, theta, emb, ids, n, chunk_rows, s0, thresholds, workspace, list_capacity, out_logits, out_center, nullptr,
+                          nullptr, status, stream);
+}
+
+int pcg_embed_set(const pcg_graph_desc *g, const float *theta, int32_t emb, const int32_t *ids, int32_t n, int32_t chunk_rows,
+                  float *s0, const double *thresholds, void *workspace, int64_t list_capacity, float *out_logits, float *out_center,
+                  float *out_emb, float *out_rel, uint32_t *status, void *stream) {
+    return infer_set_impl(g, theta, emb, ids, n, chunk_rows, s0, thresholds, workspace, list_capacity, out_logits, out_center, out_emb,
+                          out_rel, status, stream);
 }
 
 int64_t pcg_infer_dist_workspace_bytes(const pcg_graph_desc *g, int32_t emb, int32_t chunk_rows, int64_t list_capacity) {

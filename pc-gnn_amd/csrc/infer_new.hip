@@ -76,12 +76,15 @@ int64_t pcg_infer_new_workspace_bytes(const pcg_graph_desc *g, const pcg_graph_d
     return rc != PCG_OK ? rc : c.total;
 }
 
-int pcg_infer_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float *theta, int32_t emb, const int32_t *ids, int32_t n,
-                  int32_t chunk_rows, float *s0, int32_t score_base, const double *thresholds, void *workspace,
-                  int64_t list_capacity, float *out_logits, float *out_center, uint32_t *status, void *stream) {
+// pcg_infer_new (out_emb, out_rel NULL) and pcg_embed_new: a NULL out_logits / out_center goes to the workspace's centre scratch
+static int infer_new_impl(const pcg_graph_desc *g, const pcg_graph_desc *q, const float *theta, int32_t emb, const int32_t *ids,
+                          int32_t n, int32_t chunk_rows, float *s0, int32_t score_base, const double *thresholds, void *workspace,
+                          int64_t list_capacity, float *out_logits, float *out_center, float *out_emb, float *out_rel,
+                          bool need_logits, uint32_t *status, void *stream) {
     int rc = pcg::infer_new_descs(g, q);
     if (rc != PCG_OK) return rc;
     if (n < 0) return PCG_E_ARG;
+    if (!need_logits && !out_logits && !out_center && !out_emb && !out_rel) return PCG_E_ARG;
     if (!pcg::infer_table_ok(g)) return PCG_E_UNSUPPORTED;
     pcg::InferCarve c;
     rc = pcg::infer_carve(q, 2, true, emb, chunk_rows, list_capacity, c);
@@ -89,7 +92,7 @@ int pcg_infer_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float 
     const int F = g->feat_dim, E = emb, R = g->n_rel;
     if (pcg::dense_smem_bytes(F, E, R, pcg::infer_wlds(F, E, R)) > 160 * 1024) return PCG_E_UNSUPPORTED;
     if (n == 0 || q->n_nodes == 0) return PCG_OK;
-    if (!g->X || !q->X || !theta || !ids || !s0 || !thresholds || !workspace || !out_logits || !status) return PCG_E_ARG;
+    if (!g->X || !q->X || !theta || !ids || !s0 || !thresholds || !workspace || (need_logits && !out_logits) || !status) return PCG_E_ARG;
     if (((reinterpret_cast<uintptr_t>(g->X) | reinterpret_cast<uintptr_t>(q->X)) & 15u) != 0) return PCG_E_ARG;
     const int64_t N = g->n_nodes, nq = q->n_nodes;
     unsigned char *ws = static_cast<unsigned char *>(workspace);
@@ -105,9 +108,25 @@ int pcg_infer_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float 
         const int rc = pcg::launch_gather_two(pcg::feat_table(g), q->X, nq, {agg, F, PCG_NORM_COUNT, d.cnt, status}, R * B, w, d.st);
         if (rc != PCG_OK) return rc;
         // dense: the centres are rows of the query table
-        return pcg::infer_dense(q, theta, emb, cid, B, w, agg, d.cnt, out_logits + 2 * off,
-                                out_center ? out_center + 2 * off : center_scratch, d.st);
+        return pcg::infer_dense(q, theta, emb, cid, B, w, agg, d.cnt, out_logits ? out_logits + 2 * off : center_scratch,
+                                out_center ? out_center + 2 * off : center_scratch, d.st,
+                                out_emb ? out_emb + (int64_t)E * off : nullptr, out_rel ? out_rel + (int64_t)R * E * off : nullptr);
     });
+}
+
+int pcg_infer_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float *theta, int32_t emb, const int32_t *ids, int32_t n,
+                  int32_t chunk_rows, float *s0, int32_t score_base, const double *thresholds, void *workspace,
+                  int64_t list_capacity, float *out_logits, float *out_center, uint32_t *status, void *stream) {
+    return infer_new_impl(g, q, theta, emb, ids, n, chunk_rows, s0, score_base, thresholds, workspace, list_capacity, out_logits,
+                          out_center, nullptr, nullptr, true, status, stream);
+}
+
+int pcg_embed_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float *theta, int32_t emb, const int32_t *ids, int32_t n,
+                  int32_t chunk_rows, float *s0, int32_t score_base, const double *thresholds, void *workspace,
+                  int64_t list_capacity, float *out_logits, float *out_center, float *out_emb, float *out_rel, uint32_t *status,
+                  void *stream) {
+    return infer_new_impl(g, q, theta, emb, ids, n, chunk_rows, s0, score_base, thresholds, workspace, list_capacity, out_logits,
+                          out_center, out_emb, out_rel, false, status, stream);
 }
 
 }  // extern "C"

@@ -41,7 +41,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .graph import Attribution, ChosenLists, DeviceGraph, QueryBatch
+from .graph import Attribution, ChosenLists, DeviceGraph, NearestExamples, QueryBatch
 from .model import PCALayer
 
 _p = ops._p
@@ -1479,6 +1479,126 @@ class FusedPCGNN:
         inf["new_s0_version"] = self._param_version
         self._infer_status()
         return (logits, center) if want_center else logits
+
+    # -- embeddings and nearest labelled examples --------------------------------------------------------
+    # Out of scope: DistributedPCGNN, the GraphSAGE / GCN models, train-mode selection (the embeddings are the test-mode ones).
+    def _embed_outputs(self, n: int, relations: bool, want_logits: bool):
+        emb = torch.empty(n, self.E, dtype=torch.float32, device=self.dev)
+        rel = torch.empty(n, self.g.R * self.E, dtype=torch.float32, device=self.dev) if relations else None
+        logits = torch.empty(n, 2, dtype=torch.float32, device=self.dev) if want_logits else None
+        return emb, rel, logits
+
+    def _embed_result(self, emb, rel, logits):
+        res = (emb,)
+        if rel is not None:
+            res += (rel.view(rel.shape[0], self.g.R, self.E),)
+        if logits is not None:
+            res += (logits,)
+        return res[0] if len(res) == 1 else res
+
+    def embed(self, ids=None, chunk: Optional[int] = None, relations: bool = False, want_logits: bool = False):
+        """The vector the classifier sees, for a whole node set in one call (pcg_embed_set: ``infer``'s launches, whose dense
+        launch also stores the rows): emb [n, E] = relu([self | h_1 .. h_R] W), the row W_cls multiplies - bit for bit what
+        ``predict(ids[b:b + B], want_combined=True)`` returns batch by batch, for any B and any chunk.  relations=True: also
+        h [n, R, E], the per-relation embeddings h_r = relu([self | agg_r] W_r) (a view of an [n, R * E] buffer);
+        want_logits=True: also the gnn logits [n, 2], bit for bit ``infer``'s.  ids and chunk as ``infer``'s; the training
+        engine is left alone as by ``infer`` (a deferred update is applied first).  Synchronises once (the status word).
+        Test mode only; not for DistributedPCGNN or the GraphSAGE / GCN models."""
+        g, lib, inf = self.g, self.lib, self._inf
+        self.flush()
+        ids_host, ids_dev, n = whole_set_ids(ids, g.n_nodes, self.dev, "embed: ids", all_ids=inf.get("all_ids"))
+        if ids is None:
+            inf["all_ids"] = ids_dev
+        emb, rel, logits = self._embed_outputs(n, relations, want_logits)
+        if n == 0:
+            return self._embed_result(emb, rel, logits)
+        ws_bytes = lambda c, cap: int(lib.pcg_infer_workspace_bytes(g.desc_ref(), self.E, c, cap))
+        chunk, cap, ws = whole_set_chunk(inf, "ws", self.dev, ws_bytes, "pcg_infer_workspace_bytes",
+                                         infer_row_caps(g.deg_host, self.thresholds, ids_host), chunk, self.infer_workspace_bytes)
+        whole_set_buffers(inf, self.dev, "s0", g.n_nodes)
+        _lib.check(lib.pcg_embed_set(g.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk, _p(inf["s0"]), self._thr,
+                                     _p(ws), cap, _p(logits), None, _p(emb), _p(rel), _p(inf["status"]), self._stream()),
+                   "pcg_embed_set")
+        self._infer_status()
+        return self._embed_result(emb, rel, logits)
+
+    def embed_new(self, query: QueryBatch, ids=None, chunk: Optional[int] = None, relations: bool = False,
+                  want_logits: bool = False, reuse_scores: bool = True):
+        """``embed`` for nodes that are NOT in the graph (pcg_embed_new over ``infer_new``'s launches): the rows ``ids``
+        (query-local; None = all nq) of a ``graph.QueryBatch`` -> emb [n, E] (+ h [n, R, E], + logits [n, 2]), bit for bit
+        what ``embed`` returns for node N + j on a graph built with the query rows appended.  Shares ``infer_new``'s base-score
+        cache (reuse_scores as there).  Synchronises once (the status word)."""
+        g, lib, inf = self.g, self.lib, self._inf
+        ids_host, ids_dev, n = self._new_query(query, ids, "embed_new")
+        emb, rel, logits = self._embed_outputs(n, relations, want_logits)
+        if n == 0:
+            return self._embed_result(emb, rel, logits)
+        ws_bytes = lambda c, cap: int(lib.pcg_infer_new_workspace_bytes(g.desc_ref(), query.desc_ref(), self.E, c, cap))
+        chunk, cap, ws = whole_set_chunk(inf, "new_ws", self.dev, ws_bytes, "pcg_infer_new_workspace_bytes",
+                                         infer_row_caps(query.deg_host, self.thresholds, ids_host), chunk,
+                                         self.infer_workspace_bytes)
+        score_base = self._new_scores(query, reuse_scores)
+        _lib.check(lib.pcg_embed_new(g.desc_ref(), query.desc_ref(), _p(self.theta), self.E, _p(ids_dev), n, chunk, _p(inf["new_s0"]),
+                                     1 if score_base else 0, self._thr, _p(ws), cap, _p(logits), None, _p(emb), _p(rel),
+                                     _p(inf["status"]), self._stream()), "pcg_embed_new")
+        inf["new_s0_version"] = self._param_version
+        self._infer_status()
+        return self._embed_result(emb, rel, logits)
+
+    def _nearest_bank(self, among, chunk):
+        """(among ids on the device, their embeddings [M, E]): cached until the parameters or ``among`` change"""
+        g, inf = self.g, self._inf
+        if among is None:
+            among_host = np.asarray(g.train_pos_host, dtype=np.int64)
+        else:
+            among_host = (among.detach().cpu().numpy() if torch.is_tensor(among) else np.asarray(among)).reshape(-1).astype(np.int64)
+        self.flush()                                       # (a pending update bumps the version: before it is compared)
+        b = inf.get("bank")
+        if b is not None and b["version"] == self._param_version and np.array_equal(b["among_host"], among_host):
+            return b["among"], b["emb"]
+        inf["bank"] = None
+        emb = self.embed(among_host, chunk=chunk)
+        among_dev = torch.from_numpy(among_host.astype(np.int32)).to(self.dev)
+        inf["bank"] = {"version": self._param_version, "among_host": among_host, "among": among_dev, "emb": emb}
+        return among_dev, emb
+
+    def nearest(self, ids=None, k: int = 5, among=None, metric: str = "cosine", exclude_self: bool = True,
+                chunk: Optional[int] = None, query: Optional[QueryBatch] = None) -> NearestExamples:
+        """Which labelled examples each node looks like: the k nodes of ``among`` (node ids; None = the graph's training
+        positives, ``g.train_pos``) whose embeddings (``embed``) are most similar to each requested node's, as
+        ``graph.NearestExamples`` (ids / pos / score [n, k], sorted by score descending, ties by lower position in ``among``,
+        padded with -1 / -inf).  metric: "cosine" (0 for an all-zero embedding), "dot", or "l2" (minus the squared distance).
+        exclude_self: a node is never its own example.  query: the searched rows are ``embed_new(query, ids)`` instead (ids
+        query-local; query node j has the global id N + j, which is never in ``among``).
+        The bank ``embed(among)`` is kept on the engine and rebuilt when the parameters or ``among`` change.  The requested
+        rows are embedded and searched a chunk at a time (``chunk`` rows, default as ``infer``'s): the call holds the outputs,
+        the bank and one chunk of embeddings - never an [n, M] matrix (pcg_topk_similar).  Test mode only; not for
+        DistributedPCGNN or the GraphSAGE / GCN models."""
+        g = self.g
+        if metric not in ops.TOPK_METRICS:
+            raise ValueError(f"nearest: metric {metric!r} is none of {sorted(ops.TOPK_METRICS)}")
+        among_dev, bank = self._nearest_bank(among, chunk)
+        if query is None:
+            ids_host, ids_dev, n = whole_set_ids(ids, g.n_nodes, self.dev, "nearest: ids", all_ids=self._inf.get("all_ids"))
+            gid = ids_dev
+        else:
+            ids_host, ids_dev, n = self._new_query(query, ids, "nearest")
+            gid = ids_dev + g.n_nodes
+        k = int(k)
+        pos = torch.empty(n, k, dtype=torch.int32, device=self.dev)
+        score = torch.empty(n, k, dtype=torch.float32, device=self.dev)
+        step = n if chunk is None else max(int(chunk), 1)
+        if chunk is None and n > (1 << 20):
+            step = 1 << 20
+        for lo in range(0, n, max(step, 1)):
+            hi = min(lo + step, n)
+            part = ids_dev[lo:hi]
+            q = self.embed(part, chunk=chunk) if query is None else self.embed_new(query, part, chunk=chunk)
+            p, s = ops.topk_similar(q, bank, k, metric, gid[lo:hi] if exclude_self else None, among_dev if exclude_self else None)
+            pos[lo:hi], score[lo:hi] = p, s
+        safe = pos.clamp(min=0).long()
+        ex_ids = torch.where(pos >= 0, among_dev[safe] if among_dev.numel() else torch.zeros_like(pos), torch.full_like(pos, -1))
+        return NearestExamples(ex_ids, pos, score, among_dev, metric)
 
     def _new_query(self, query: QueryBatch, ids, what: str):
         """What every query call does first: a deferred update applied, the batch checked against this engine's graph and

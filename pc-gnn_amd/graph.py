@@ -331,6 +331,28 @@ class Attribution:
         return self.chosen.ids[lo:hi][order], c[order]
 
 
+class NearestExamples:
+    """The k labelled examples each of n requested nodes looks most like (``FusedPCGNN.nearest``; the kernel:
+    pcg_topk_similar) - device tensors, a row per requested node, sorted by score descending with ties by lower position:
+
+    ids [n, k] int32: global node ids of the examples, -1 where a node has fewer than k eligible examples |
+    pos [n, k] int32: their positions in ``among`` (-1 likewise) | score [n, k] float32 (-inf likewise) |
+    among: the searched node ids [M] | metric: "cosine", "dot" or "l2" (always maximised: l2 is minus the squared distance)."""
+
+    def __init__(self, ids: torch.Tensor, pos: torch.Tensor, score: torch.Tensor, among: torch.Tensor, metric: str):
+        self.ids, self.pos, self.score, self.among, self.metric = ids, pos, score, among, metric
+        self.n, self.k = int(pos.shape[0]), int(pos.shape[1])
+
+    def row(self, i: int):
+        """(ids, pos, score) of requested node i, without its padding."""
+        keep = self.pos[i] >= 0
+        return self.ids[i][keep], self.pos[i][keep], self.score[i][keep]
+
+    def to_numpy(self):
+        """(ids, pos, score) as host arrays [n, k]."""
+        return self.ids.cpu().numpy(), self.pos.cpu().numpy(), self.score.cpu().numpy()
+
+
 class BaseShape:
     """What a ``QueryBatch`` is validated against: the base graph's node count, feature width and relation count.  A
     ``DeviceGraph`` has the same three attributes; this stands in for one where there is no GPU (host-side checks, tests)."""

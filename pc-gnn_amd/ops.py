@@ -485,3 +485,54 @@ def eval_status(device) -> torch.Tensor:
     if cache.get("status") is None:
         cache["status"] = torch.zeros(1, dtype=torch.int32, device=dev)
     return cache["status"]
+
+
+TOPK_METRICS = {"dot": 0, "cosine": 1, "l2": 2}
+_TOPK_CACHE: dict = {}
+
+
+def topk_similar(Q: torch.Tensor, bank: torch.Tensor, k: int, metric: str = "cosine", q_ids: Optional[torch.Tensor] = None,
+                 bank_ids: Optional[torch.Tensor] = None, _slices: int = 0):
+    """The k rows of ``bank`` [M, E] most similar to each row of ``Q`` [n, E] (float32 device tensors, E a multiple of 16 in
+    16 .. 512, 1 <= k <= 64) -> (pos [n, k] int32 bank positions, score [n, k] float32), sorted by score descending with ties
+    by lower position; slots beyond the number of eligible rows hold -1 / -inf (pcg_topk_similar: exact-f32 MFMA scores and a
+    running top-k, no [n, M] matrix).  metric - always maximised: "dot" q.c | "cosine" q.c / (|q| |c|), 0 when either norm is
+    0 | "l2" min(0, 2 q.c - |q|^2 - |c|^2).  q_ids [n], bank_ids [M] (both or neither): bank row c is skipped for query row i
+    when bank_ids[c] == q_ids[i].  The result does not depend on how the kernel slices the bank (_slices: the tests' way to
+    force a slice count; 0 = the kernel's choice).  Enqueues on the current stream; does not synchronise."""
+    lib = _lib.load()
+    if metric not in TOPK_METRICS:
+        raise ValueError(f"topk_similar: metric {metric!r} is none of {sorted(TOPK_METRICS)}")
+    if Q.dim() != 2 or bank.dim() != 2 or Q.shape[1] != bank.shape[1]:
+        raise ValueError(f"topk_similar: Q {tuple(Q.shape)} and bank {tuple(bank.shape)} are not [n, E] and [M, E]")
+    if Q.dtype != torch.float32 or bank.dtype != torch.float32 or Q.device != bank.device or Q.device.type != "cuda":
+        raise _lib.PcgnnLibraryError("topk_similar: Q and bank must be float32 tensors on one GPU (there is no CPU path)")
+    if (q_ids is None) != (bank_ids is None):
+        raise ValueError("topk_similar: q_ids and bank_ids go together")
+    dev = Q.device
+    Q, bank = Q.detach().contiguous(), bank.detach().contiguous()
+    n, E, M, k = int(Q.shape[0]), int(Q.shape[1]), int(bank.shape[0]), int(k)
+    if q_ids is not None:
+        q_ids, bank_ids = _i32(q_ids, dev).view(-1), _i32(bank_ids, dev).view(-1)
+        if q_ids.numel() != n or bank_ids.numel() != M:
+            raise ValueError("topk_similar: q_ids / bank_ids must have one id per row of Q / bank")
+        if n == 0 or M == 0:                                # (nothing to exclude; an empty tensor has no address to pass)
+            q_ids = bank_ids = None
+    nbytes = int(lib.pcg_topk_similar_workspace_bytes(n, M, E, k))
+    if nbytes < 0:
+        _lib.check(nbytes, f"pcg_topk_similar_workspace_bytes(n={n}, M={M}, emb={E}, k={k})")
+    cache = _TOPK_CACHE.setdefault((dev.type, dev.index if dev.index is not None else torch.cuda.current_device()), {})
+    if cache.get("ws") is None or cache["ws"].numel() < nbytes:
+        cache["ws"] = None
+        cache["ws"] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        cache["status"] = torch.zeros(1, dtype=torch.int32, device=dev)
+    pos = torch.empty(n, k, dtype=torch.int32, device=dev)
+    score = torch.empty(n, k, dtype=torch.float32, device=dev)
+    lib.pcg_debug_set_topk_slices(int(_slices))
+    try:
+        _lib.check(lib.pcg_topk_similar(_p(Q), n, _p(bank), M, E, k, TOPK_METRICS[metric], _p(q_ids), _p(bank_ids), _p(pos), _p(score),
+                                        _p(cache["ws"]), _p(cache["status"]), _stream(dev)), "pcg_topk_similar")
+    finally:
+        if _slices:
+            lib.pcg_debug_set_topk_slices(0)
+    return pos, score

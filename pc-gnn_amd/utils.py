@@ -184,6 +184,22 @@ def explain_new(engine, query, ids=None, attribute: bool = False):
         return ch, torch.sigmoid(engine.infer_new(query, ids=ids)).float()
 
 
+def similar_examples(engine, ids, k: int = 5, labels=None, query=None):
+    """Example-based explanation in one call: (``engine.nearest(ids, k)`` - the k training positives each node's embedding is
+    closest to (cosine), as ``graph.NearestExamples`` -, the test-mode class probabilities [n, 2] of the same ids), on the
+    device.  labels (one per graph node, 0 / 1; a tensor, array or list): a third value, the labels of the examples
+    [n, k] int64, -1 where a row is padded.  query: the ids are rows of that ``graph.QueryBatch`` (new nodes)."""
+    with torch.no_grad():
+        near = engine.nearest(ids, k=k, query=query)
+        logits = engine.infer(ids) if query is None else engine.infer_new(query, ids=ids)
+        prob = torch.sigmoid(logits).float()
+        if labels is None:
+            return near, prob
+        lab = torch.as_tensor(np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)).to(near.ids.device).long().view(-1)
+        ex = torch.where(near.ids >= 0, lab[near.ids.clamp(min=0).long()], torch.full_like(near.ids, -1, dtype=torch.long))
+        return near, prob, ex
+
+
 def predict_proba(test_nodes, model, batch_size: int, labels=None) -> np.ndarray:
     """Test-mode class probabilities [n, 2] of ``test_nodes`` (sigmoid of the gnn logits, utils.py:305), on the host.
     A FusedPCGNN runs its whole-set pass (``infer``: one call, one score pass) - test-mode results do not depend on how the
