@@ -183,8 +183,8 @@ def plan_infer_chunks(csr_host, bounds, rank: int, pos_sorted: np.ndarray, ids: 
     """Cut ids (local rows, in their given order) into chunks [a, b) of at most max_rows ids whose distinct remote, non-train-pos
     neighbours number at most `pitch` per owner (so the chunk's halo exchange cannot overflow; pitch >= infer_pitch's single-row
     demand), each as long as both allow.  Returns (chunks, list_capacity): the selection-list capacity that covers the largest
-    chunk's test-mode lists exactly (fused.infer_row_caps; >= 1)."""
-    from .fused import infer_row_caps
+    chunk's test-mode lists exactly (wholeset.infer_row_caps; >= 1)."""
+    from .wholeset import infer_row_caps
     ids = np.asarray(ids, dtype=np.int64).reshape(-1)
     n = ids.size
     if n == 0:
@@ -933,7 +933,7 @@ class DistributedPCGNN:
         lists or halo went over capacity, every rank raises."""
         g, part, lib, _p = self.g, self.part, self.lib, self.ops._p
         self.flush()
-        from .fused import default_infer_chunk, infer_row_caps, whole_set_buffers, whole_set_ids, whole_set_workspace
+        from .wholeset import default_infer_chunk, infer_row_caps, whole_set_buffers, whole_set_ids, whole_set_workspace
         inf = self._inf
         ids_host, ids_dev, n = whole_set_ids(ids_local, part.n_local, self.dev, "infer: ids_local", all_ids=inf.get("all_dev"))
         if ids_local is None:

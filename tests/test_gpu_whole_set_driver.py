@@ -2,6 +2,8 @@
 chunk of ids, two plan slots): every layout of chunks a call can have - chunks of one row, full chunks plus a shorter tail, a
 tail equal to the chunk, one chunk, a chunk larger than the set - gives bit for bit what one chunk gives, and what the per-batch
 ``predict`` loop gives; the status word is left zero, and a call after an overflow works."""
+from unittest import mock
+
 import numpy as np
 import pytest
 import torch
@@ -92,3 +94,70 @@ def test_a_call_after_an_overflow_works(case):
     assert torch.equal(fz.infer(ids, chunk=7), want["gnn"])
     assert status_word(fz) == 0
     fz.check()
+
+
+def status_reads(fz, call) -> int:
+    """the number of times `call` reads the whole-set status word - its host synchronisations"""
+    with mock.patch.object(fz, "_infer_status", wraps=fz._infer_status) as reads:
+        call()
+    return reads.call_count
+
+
+@pytest.mark.parametrize("chunk", [7, None])
+def test_every_public_call_synchronises_as_often_as_documented(case, chunk):
+    """"Synchronises once (the status word; once more per ``chosen`` call)", whatever the number of chunks: 7 = seven chunks and
+    a tail of one row.  ``nearest`` embeds the bank once (while it is cold) and then the requested rows ``chunk`` at a time."""
+    fz, ids, query, _ = case
+    labels = (ids % 2).astype(np.int64)
+    once = {
+        "infer": lambda: fz.infer(ids, chunk=chunk),
+        "chosen": lambda: fz.chosen(ids, chunk=chunk),
+        "chosen(train)": lambda: fz.chosen(ids, chunk=chunk, train_flag=True, labels=labels),
+        "attribute": lambda: fz.attribute(ids, chunk=chunk),
+        "infer_new": lambda: fz.infer_new(query, chunk=chunk),
+        "chosen_new": lambda: fz.chosen_new(query, chunk=chunk),
+        "attribute_new": lambda: fz.attribute_new(query, chunk=chunk),
+        "attribute_new(neighbours)": lambda: fz.attribute_new(query, chunk=chunk, neighbours=True),
+        "embed": lambda: fz.embed(ids, chunk=chunk),
+        "embed_new": lambda: fz.embed_new(query, chunk=chunk),
+        "evaluate": lambda: fz.evaluate(ids, labels, chunk=chunk),
+    }
+    for what, call in once.items():
+        assert status_reads(fz, call) == 1, what
+    assert status_reads(fz, lambda: fz.attribute(ids, chunk=chunk, neighbours=True)) == 2
+    parts = 1 if chunk is None else -(-NQ // chunk)          # (nearest searches `chunk` rows at a time: one embed each)
+    fz._inf.pop("bank", None)                                # a cold bank: its embed, then the parts'
+    assert status_reads(fz, lambda: fz.nearest(ids, chunk=chunk)) == 1 + parts
+    assert status_reads(fz, lambda: fz.nearest(ids, chunk=chunk)) == parts
+    assert status_word(fz) == 0
+
+    # an empty id list: the empty result, nothing launched, nothing read
+    empty = {
+        "infer": lambda: fz.infer([], chunk=chunk),
+        "chosen": lambda: fz.chosen([], chunk=chunk),
+        "chosen(train)": lambda: fz.chosen([], chunk=chunk, train_flag=True, labels=[]),
+        "attribute": lambda: fz.attribute([], chunk=chunk),
+        "attribute(neighbours)": lambda: fz.attribute([], chunk=chunk, neighbours=True),     # (through chosen, which returns early)
+        "infer_new": lambda: fz.infer_new(query, [], chunk=chunk),
+        "chosen_new": lambda: fz.chosen_new(query, [], chunk=chunk),
+        "attribute_new": lambda: fz.attribute_new(query, [], chunk=chunk),
+        "attribute_new(neighbours)": lambda: fz.attribute_new(query, [], chunk=chunk, neighbours=True),
+        "embed": lambda: fz.embed([], chunk=chunk),
+        "embed_new": lambda: fz.embed_new(query, [], chunk=chunk),
+        "nearest": lambda: fz.nearest([], chunk=chunk),                                      # (the bank is warm)
+    }
+    sizes = {}
+    for what, call in empty.items():
+        assert status_reads(fz, lambda: sizes.__setitem__(what, call())) == 0, what
+    assert sizes["infer"].shape == (0, 2) and sizes["infer_new"].shape == (0, 2)
+    assert sizes["embed"].shape == (0, EMB) and sizes["embed_new"].shape == (0, EMB)
+    assert sizes["chosen"].n == sizes["chosen(train)"].n == sizes["chosen_new"].n == 0
+    for what in ("attribute", "attribute(neighbours)", "attribute_new", "attribute_new(neighbours)"):
+        assert sizes[what].logits.shape == (0, 2), what
+    assert sizes["attribute(neighbours)"].chosen.n == 0 and sizes["attribute_new(neighbours)"].chosen.n == 0
+    assert sizes["nearest"].ids.shape == (0, 5)
+    # (evaluate has no empty result - no metric is defined without labels -: its infer returns early all the same)
+    with mock.patch.object(fz, "_infer_status", wraps=fz._infer_status) as reads:
+        with pytest.raises(ValueError, match="Only one class present"):
+            fz.evaluate([], [], chunk=chunk)
+    assert reads.call_count == 0

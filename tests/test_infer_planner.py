@@ -79,3 +79,65 @@ def test_ids_helper_accepts_tensor_array_list_and_none():
             whole_set_ids(torch.tensor([bad]), rows, dev, "infer_new: ids", " (query-local rows)")
         with pytest.raises(ValueError, match=r"^infer: ids_local outside 0 \.\. 39$"):
             whole_set_ids([bad], rows, dev, "infer: ids_local")
+
+
+# the number of output arguments of each whole-set entry point (include/pcgnn.h): logits, center | + emb, rel | logits, d_self,
+# d_agg, self_contrib, rel_contrib | out_begin, out_ids, out_dist | the ExplainOut struct
+ENTRY_OUTPUTS = {"pcg_infer_set": 2, "pcg_embed_set": 4, "pcg_attr_set": 5, "pcg_chosen_set": 3,
+                 "pcg_infer_new": 2, "pcg_embed_new": 4, "pcg_explain_new": 1}
+QUERY_CALLS = {"pcg_infer_new", "pcg_embed_new", "pcg_explain_new"}
+WEIGHTED_CALLS = {"pcg_attr_set", "pcg_explain_new"}
+
+
+def test_argument_tuples_match_the_prototypes():
+    from pcgnn_amd import _lib
+    from pcgnn_amd.wholeset import whole_set_args
+    head = ("g", "theta", "E", "ids", "n", "chunk", "s0")
+    for name, n_out in ENTRY_OUTPUTS.items():
+        outputs = tuple(f"out{i}" for i in range(n_out))
+        args = whole_set_args(head, ("thr", "ws", "cap"), outputs, ("status", "stream"),
+                              ("q", "score_base") if name in QUERY_CALLS else None, ("w0", "w1") if name in WEIGHTED_CALLS else ())
+        assert len(args) == len(_lib.PROTOTYPES[name][1]), name
+        assert len(set(args)) == len(args) and args[0] == "g" and args[-2:] == ("status", "stream"), name
+        assert (args[1] == "q") == (name in QUERY_CALLS) == ("q" in args), name
+        assert (args[args.index("s0") + 1] == "score_base") == (name in QUERY_CALLS) == ("score_base" in args), name
+        cap = args.index("cap")
+        assert args[cap - 2:cap + 1] == ("thr", "ws", "cap") and args[args.index("s0") + 1:cap - 2] in ((), ("score_base",)), name
+        assert (args[cap + 1:cap + 3] == ("w0", "w1")) == (name in WEIGHTED_CALLS) == ("w0" in args), name
+        assert args[-2 - n_out:-2] == outputs, name
+        without_q = tuple(a for a in args if a != "q")
+        assert without_q[:7] == head, name
+
+
+def test_workspace_table_covers_the_seven_entry_points():
+    from pcgnn_amd import _lib
+    from pcgnn_amd.wholeset import WORKSPACES
+    assert set(WORKSPACES) == set(ENTRY_OUTPUTS)
+    for name, (key, size_fn) in WORKSPACES.items():
+        assert key in ("ws", "chosen_ws", "new_ws") and size_fn in _lib.PROTOTYPES and size_fn.endswith("_workspace_bytes"), name
+        # the size function takes the call's graph descriptors, (the embedding width,) the chunk and the list capacity
+        n_desc = 2 if name in QUERY_CALLS else 1
+        assert len(_lib.PROTOTYPES[size_fn][1]) == n_desc + (0 if size_fn == "pcg_chosen_workspace_bytes" else 1) + 2, name
+        assert (key == "new_ws") == (name in QUERY_CALLS), name
+
+
+def test_target_weights_are_two_finite_floats():
+    import pytest
+    from pcgnn_amd.wholeset import _target_weights
+    assert _target_weights("attribute", (0.0, 1.0)) == (0.0, 1.0)
+    w = _target_weights("attribute_new", (-1, 1))
+    assert w == (-1.0, 1.0) and all(type(v) is float for v in w)
+    for what in ("attribute", "attribute_new", "chosen_new"):
+        for bad in ((float("nan"), 1), (float("inf"), 0), "ab", (1,), None):
+            with pytest.raises(ValueError, match=rf"^{what}: target must be two finite floats, got "):
+                _target_weights(what, bad)
+
+
+def test_fused_keeps_the_planner_names_and_the_alias_imports_the_module():
+    import pcgnn_amd.fused as fused
+    import pcgnn_amd.wholeset as wholeset
+    for name in ("infer_row_caps", "infer_chunks", "default_infer_chunk", "whole_set_ids", "whole_set_workspace", "whole_set_chunk",
+                 "whole_set_buffers"):
+        assert getattr(fused, name) is getattr(wholeset, name)
+    assert issubclass(fused.FusedPCGNN, wholeset.WholeSetCalls)
+    assert "__init__" not in vars(wholeset.WholeSetCalls)
