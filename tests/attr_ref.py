@@ -128,6 +128,11 @@ def host_test_sets(case, ids):
 # GradCase.batch's salt per shape: the first at which every batch keeps the ReLU-kink condition with the band DOUBLED (a batch of
 # 17 rows may leave out none: one row a few per cent inside the band on one CPU is outside it on another)
 BATCH_SALT = {(32, 64, 3): 2, (25, 128, 3): 1}
+# the edge and wide shapes of dense_ref.EDGE_ATTR_SHAPES (tests/test_gpu_edge_shapes.py): a salt at which no row of any batch lies
+# in the doubled band (E = 272 has 544 activations a row: one row in twenty of its graph has one in the band), the batch of 65
+# draws a node twice, and the lone row keeps COND_CAP below (tests/test_edge_shapes_host.py asserts all three)
+BATCH_SALT.update({(16, 64, 4): 388, (30, 64, 3): 443, (20, 128, 1): 86, (20, 32, 7): 1111, (17, 32, 8): 137, (32, 64, 8): 1509,
+                   (64, 64, 3): 1919, (16, 272, 1): 5484, (100, 64, 3): 685, (260, 16, 1): 1022, (360, 16, 1): 225, (24, 16, 1): 11})
 
 
 def id_sets(case):
@@ -136,6 +141,35 @@ def id_sets(case):
     out = {f"n{B}": case.batch(B, salt)[0] for B in BATCH_SIZES}
     out["whole"] = np.arange(case.n)
     return out
+
+
+# A batch of ONE row: self_contrib and rel_contrib are tensors of one element, so "relative to the tensor's largest element" is
+# relative to the inner product itself, and where its terms cancel the figure is the sum's condition number (sum |terms| /
+# |sum terms|) times the rounding of its inputs, whatever computes it: merely rounding one factor of every term to float32 moves
+# the sum by up to 2^-24 * condition, and the float32 yardstick of a single element is one draw - at (16, 272, 1) a row with
+# <a_1, ds / da_1> = 0.0088 from terms of 0.21 in all (condition 24) has float32 torch at 5e-8 or 1.7e-6 of it depending on the
+# order of the set alone, and a device error of 2.1e-6, under ONE ulp of the summands, missed the bound (8 * 4.9e-8 + 2^-20).
+# The lone row of the edge shapes is therefore one whose inner products - the self product and every relation's, both targets -
+# keep 2^-24 * condition under the tolerance's floor 2^-20: condition <= COND_CAP = 16 (a condition on the float64 reference
+# alone, like the ReLU-kink one).  Batches of several rows need none: their largest element is the yardstick of every row.
+COND_CAP = 16.0
+
+
+def contrib_condition(X, ids, index, r64):
+    """max over the rows, and over the self product and every relation's, of sum |terms| / |sum terms| (float64; r64: attr_ref's
+    float64 result for the same ids and index)"""
+    X = torch.as_tensor(X).double()
+    x = X[torch.as_tensor(np.asarray(ids)).long()]
+    a = aggregates(X, sets_to_index(index), len(ids), torch.float64)
+    terms = [x * r64["d_self"]] + [a[r] * r64["d_agg"][r] for r in range(len(a))]
+    return max(float((t.abs().sum(1) / t.sum(1).abs()).max()) for t in terms)
+
+
+def hub_ids(case):
+    """the batch of 65 with the graph's two largest rows at its first two positions (lists of more than 128 chosen entries:
+    the neighbour kernel's tail slices)"""
+    hub, second = case.hubs(2)
+    return case.batch(65, BATCH_SALT.get((case.f, case.emb, case.R), 0), pins={0: hub, 1: second})[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

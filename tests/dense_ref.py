@@ -154,7 +154,8 @@ WIDE_SHAPES = {
     (400, 16, 1): ("dense_step_kernel<false, 0, 0, 0>", BATCHES_SHORT, 11),
 }
 WIDE_LDS_BYTES = {(100, 64, 3): 98432, (68, 16, 2): 63104, (260, 16, 1): 123392, (400, 16, 1): 101216}
-REL_DEG = {1: (12,), 2: (12, 3), 3: (4, 12, 3), 5: (4, 12, 3, 6, 2)}
+REL_DEG = {1: (12,), 2: (12, 3), 3: (4, 12, 3), 4: (4, 12, 3, 6), 5: (4, 12, 3, 6, 2), 7: (4, 12, 3, 6, 2, 5, 3),
+           8: (4, 12, 3, 6, 2, 5, 3, 8)}
 MAX_BATCH = 2049
 TILE_ROWS, STAGED_DIRECT, CHUNK = 16, 2048, 128     # rows of a dense tile | aggregate elements loaded two per thread | a gather chunk
 
@@ -181,6 +182,102 @@ def dense_wlds(F, E, R):
             and kparts * tb * E <= R * k1p * (E + 4))
 
 
+def infer_wlds(F, E, R):
+    """infer_wlds of csrc/infer.hip, restated: a forward-only launch (whole-set inference, attribution) keeps the weights' LDS
+    copy alive across tiles, so its K-split partial tiles go where the backward's dcomb / dh_r arrays are - if they fit there"""
+    tb, waves = 16, 16
+    ntile_e = E // 16
+    kparts = waves // ntile_e if ntile_e <= waves else 1
+    return dense_wlds(F, E, R) and kparts * tb * E <= (1 + R) * tb * (E + 1)
+
+
+def attr_dcat_over_cat(F, E, R):
+    """attr_dcat_over_cat of csrc/attr.hip, restated: dcat [R][16][2F + 1] lies over the forward's [self | h_1 .. h_R] tile"""
+    k2p = (F + R * E + 15) // 16 * 16
+    return R * (2 * F + 1) <= k2p + 1
+
+
+def attr_dx0_over_comb(F, E):
+    """attr_dx0_over_comb of csrc/attr.hip, restated: dx0 [16][F + 1] lies over `combined` [16][E + 1]"""
+    return F <= E
+
+
+def attr_smem_bytes(F, E, R):
+    """attr_smem_bytes of csrc/attr.hip with the forward's own choice of the weights' copy, restated: the attribution launch's LDS"""
+    extra = (0 if attr_dcat_over_cat(F, E, R) else R * 16 * (2 * F + 1)) + (0 if attr_dx0_over_comb(F, E) else 16 * (F + 1))
+    return dense_smem_bytes(F, E, R, infer_wlds(F, E, R)) + 4 * extra
+
+
+def attr_shape_ok(F, E, R):
+    return attr_smem_bytes(F, E, R) <= 160 * 1024
+
+
+# the four users of dense_tile_body and the six instantiations of each: four fixed shapes (the weights' LDS copy: a template
+# argument the host's rule must agree with, else the shape falls through to the run-time kernels) and two run-time-shape ones
+USERS = {"train": "dense_step_kernel", "vjp": "dense_vjp_kernel", "infer": "infer_dense_kernel", "attr": "attr_dense_kernel"}
+FIXED = {(32, 64, 3): True, (25, 64, 3): True, (32, 128, 3): False, (25, 128, 3): False}
+INSTANTIATIONS = [(True, 32, 64, 3), (True, 25, 64, 3), (False, 32, 128, 3), (False, 25, 128, 3), (True, 0, 0, 0), (False, 0, 0, 0)]
+
+
+def kernel_of(user, F, E, R):
+    """The instantiation a user's launch picks for a shape - launch_dense (csrc/dense.hip), pcg_dense_vjp (csrc/vjp.hip),
+    launch_infer_dense (csrc/infer.hip), launch_attr_dense (csrc/attr.hip), restated - as the kernel's name; None: refused"""
+    forward_only = user in ("infer", "attr")
+    wlds = (infer_wlds if forward_only else dense_wlds)(F, E, R)
+    if E < 16 or E % 16 or not 1 <= R <= 8 or dense_smem_bytes(F, E, R, wlds) > 160 * 1024:
+        return None
+    if user == "attr" and not attr_shape_ok(F, E, R):
+        return None
+    fixed = FIXED.get((F, E, R)) == wlds
+    args = f"{str(wlds).lower()}, {F}, {E}, {R}" if fixed else f"{str(wlds).lower()}, 0, 0, 0"
+    return f"{USERS[user]}<{args}" + ((", true>" if fixed else ", false>") if forward_only else ">")
+
+
+# Edge shapes: what the host rules accept and the tables above do not reach.  Per shape: (the training kernel, batch sizes, seed
+# of the case).  tests/test_edge_shapes_host.py re-derives every statement below from the restated rules:
+#   (16, 64, 4)   the run-time LDS-weight kernels of all four users; R = 4
+#   (30, 64, 3)   next to the fixed shapes (the dispatch falls through); F % 4 != 0 (stride 32)
+#   (20, 128, 1)  LDS weights at E = 128 (kparts 2), R = 1
+#   (20, 32, 7)   E = 32 (kparts 8), R = 7; attribution: dcat appended with dx0 over `combined`
+#   (17, 32, 8)   R = PCG_MAX_REL with the weights' copy; odd F (stride 20)
+#   (32, 64, 8)   R = 8 streamed; R * E / 16 = 32 h-tiles: two turns of the wave loop
+#   (64, 64, 3)   attribution: dcat appended with dx0 over `combined`, streamed; the last width before the F > 64 staging loop
+#   (16, 272, 1)  E / 16 = 17 > 16 waves: kparts 1, every E-tiled wave loop takes a second turn
+EDGE_SHAPES = {
+    (16, 64, 4): ("dense_step_kernel<true, 0, 0, 0>", BATCHES_SHORT, 12),
+    (30, 64, 3): ("dense_step_kernel<true, 0, 0, 0>", BATCHES_SHORT, 11),
+    (20, 128, 1): ("dense_step_kernel<true, 0, 0, 0>", BATCHES_SHORT, 11),
+    (20, 32, 7): ("dense_step_kernel<true, 0, 0, 0>", BATCHES_SHORT, 11),
+    (17, 32, 8): ("dense_step_kernel<true, 0, 0, 0>", BATCHES_SHORT, 11),
+    (32, 64, 8): ("dense_step_kernel<false, 0, 0, 0>", BATCHES_SHORT, 11),
+    (64, 64, 3): ("dense_step_kernel<false, 0, 0, 0>", BATCHES_SHORT, 11),
+    (16, 272, 1): ("dense_step_kernel<false, 0, 0, 0>", BATCHES_SHORT, 11),
+}
+EDGE_TRAIN_SHAPES = [(16, 64, 4), (17, 32, 8), (16, 272, 1)]      # the first-moment train-step cases, at B = 17 and 1025
+# the widest rows attribution accepts at (F, 16, 1) and the first it refuses -> seed of the case ((122 | 123, 64, 3): the same
+# limit at the project's E and R, through the C ABI only)
+ATTR_LIMIT_SHAPES = {(360, 16, 1): 11, (361, 16, 1): 11}
+ATTR_LIMITS = [((360, 16, 1), (361, 16, 1)), ((122, 64, 3), (123, 64, 3))]
+# what whole-set inference / embed and attribution run beyond EDGE_SHAPES
+EDGE_INFER_SHAPES = list(EDGE_SHAPES) + [(260, 16, 1)]
+EDGE_ATTR_SHAPES = list(EDGE_SHAPES) + [(100, 64, 3), (260, 16, 1), (360, 16, 1), (24, 16, 1)]
+# (24, 16, 1): the attribution's fourth LDS overlay - dcat over the [self | h_1] tile with dx0 appended - which only R = 1 with
+# E < F <= E + 8 and 2F <= K2p reaches; here dcat [16][49] fills the tile [16][K2p + 1] to the float.  -> seed of the case
+ATTR_OVERLAY_SHAPES = {(24, 16, 1): 11}
+# (the attribution batches are attr_ref.id_sets', with attr_ref.BATCH_SALT's salt per shape)
+EDGE_CUS = 256                                       # an MI355X's; the host test draws the long id set for it
+EDGE_SET_SIZES = lambda cus: (1, 17, 16 * cus + 17)  # a lone row, a ragged second tile, a second tile on every workgroup
+
+
+def edge_id_sets(case, cus=EDGE_CUS):
+    """n -> ids of the inference tests' sets: n = 1, 17 (no duplicates), 16 * CUs + 17 (drawn with replacement)"""
+    rs = np.random.RandomState(case.seed * 7919 + 13)
+    out = {}
+    for n in EDGE_SET_SIZES(cus):
+        out[n] = rs.choice(case.n, size=n, replace=False) if n <= 17 else rs.randint(0, case.n, size=n)
+    return out
+
+
 class GradCase:
     """The fields ``tests.util.build_model`` reads (n, f, emb, R, alpha, train_pos, X, params()) over a ``synth_graph`` of 2000
     nodes, ~15 % positives, the train positives those among the first half of the nodes; seeded Xavier-scale parameters."""
@@ -203,7 +300,10 @@ class GradCase:
 
     @classmethod
     def of(cls, shape):
-        return cls(*shape, seed=(SHAPES[shape] if shape in SHAPES else WIDE_SHAPES[shape])[2])
+        for table in (SHAPES, WIDE_SHAPES, EDGE_SHAPES):
+            if shape in table:
+                return cls(*shape, seed=table[shape][2])
+        return cls(*shape, seed={**ATTR_LIMIT_SHAPES, **ATTR_OVERLAY_SHAPES}[shape])
 
     def params(self):
         return {k: v.clone() for k, v in self._params.items()}

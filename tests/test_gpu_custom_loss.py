@@ -35,6 +35,15 @@ Measured on an MI355X (profiles/r19/custom_loss_ratios.txt): `ratio` = e_kernel 
     (10, 16, 1)      dense_vjp_kernel<false, 0, 0, 0>       2.13 / 0.12  1.99 / 0.09  2.40 / 0.11  1.15 / 0.16 | 4.86 / 0.31   2.93 / 0.38
     (24, 16, 5)      dense_vjp_kernel<true, 0, 0, 0>        1.78 / 0.09  1.83 / 0.12  1.33 / 0.08  1.25 / 0.09 | -
 
+The other two fixed-shape kernels, a wide row and three of dense_ref.EDGE_SHAPES (profiles/r28/edge_shape_ratios.txt):
+
+    (25, 64, 3)      dense_vjp_kernel<true, 25, 64, 3>      2.30 / 0.22  1.80 / 0.11  1.22 / 0.10  1.36 / 0.10
+    (25, 128, 3)     dense_vjp_kernel<false, 25, 128, 3>    2.64 / 0.17  1.29 / 0.11  1.53 / 0.13  1.44 / 0.12
+    (100, 64, 3)     dense_vjp_kernel<false, 0, 0, 0>       1.00 / 0.06  1.94 / 0.12  1.76 / 0.12  1.21 / 0.10
+    (16, 64, 4)      dense_vjp_kernel<true, 0, 0, 0>        2.78 / 0.19  2.87 / 0.12  1.37 / 0.09  1.37 / 0.10
+    (20, 128, 1)     dense_vjp_kernel<true, 0, 0, 0>        1.80 / 0.12  1.46 / 0.11  1.31 / 0.10  1.00 / 0.12
+    (16, 272, 1)     dense_vjp_kernel<false, 0, 0, 0>       2.40 / 0.19  1.71 / 0.12  1.70 / 0.15  1.29 / 0.09
+
 Every exact statement held; no batch came near the ReLU-kink cap (at most 6.1e-5 of the activations ambiguous).
 """
 import numpy as np

@@ -98,7 +98,7 @@ def assert_explained(base, oracle, query, ids=None, chunk=None, groups_alone=Fal
     return at
 
 
-# ---- 1. the golden fixtures' graphs: every dense / attribution instantiation ------------------------------------------------
+# ---- 1. the golden fixtures' graphs: the fixed-shape and the streamed run-time attribution instantiations -------------------
 GOLDEN_CASES = ["yelp_small", "yelp_emb128", "feat100", "amazon_small", "five_rel", "single_rel"]
 
 

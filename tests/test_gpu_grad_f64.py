@@ -42,6 +42,20 @@ pinned row is staged by the first 2048 elements and - every batch of a whole til
     (260, 16, 1)     dense_step_kernel<true, 0, 0, 0>        2.09               0.20     | 4.11              0.19
     (400, 16, 1)     dense_step_kernel<false, 0, 0, 0>       2.80               0.24     | -                 -
 
+Edge shapes (dense_ref.EDGE_SHAPES; profiles/r28/edge_shape_ratios.txt; what each reaches: the table's comment, asserted by
+tests/test_edge_shapes_host.py): the run-time-shape kernel with the weights' LDS copy at E = 32, 64 and 128, R = 4, 7 and 8, E / 16
+= 17 column tiles on 16 waves; plain batches (BATCHES_SHORT), train steps at B = 17 / 1025:
+
+    shape (F, E, R)  kernel                                  gradients() ratio  of bound | train step ratio  of bound
+    (16, 64, 4)      dense_step_kernel<true, 0, 0, 0>        2.81               0.19     | 3.03              0.18
+    (30, 64, 3)      dense_step_kernel<true, 0, 0, 0>        1.64               0.12     | -                 -
+    (20, 128, 1)     dense_step_kernel<true, 0, 0, 0>        1.18               0.12     | -                 -
+    (20, 32, 7)      dense_step_kernel<true, 0, 0, 0>        1.87               0.14     | -                 -
+    (17, 32, 8)      dense_step_kernel<true, 0, 0, 0>        3.48               0.15     | 2.90              0.33
+    (32, 64, 8)      dense_step_kernel<false, 0, 0, 0>       2.11               0.13     | -                 -
+    (64, 64, 3)      dense_step_kernel<false, 0, 0, 0>       1.58               0.12     | -                 -
+    (16, 272, 1)     dense_step_kernel<false, 0, 0, 0>       2.12               0.13     | 4.42              0.23
+
 Every kernel error is a few 1e-7 of the tensor's largest element - the size of the float32 CPU run's own - so the bound is
 mostly its floor; nothing came near the margin of 8.  ((10, 16, 1) runs the run-time-shape kernel WITHOUT the weights' LDS copy:
 its K-split partial tiles do not fit where the W_intra copy would be; (24, 16, 5) is here for the run-time-shape kernel with it.)
@@ -61,7 +75,8 @@ WIDE_TRAIN_SHAPES = [(100, 64, 3), (260, 16, 1)]      # gather_train_kernel<1> a
 # (shape, B) of the first-moment test: the four boundary sizes for the project's shapes, a short and a long batch for the wide ones
 TRAIN_CASES = ([pytest.param(s, B, id=f"shape{i}-{B}") for i, s in enumerate(TRAIN_SHAPES) for B in (17, 1024, 1025, 2049)]
                + [pytest.param(s, B, id=f"shape{len(TRAIN_SHAPES) + i}-{B}") for i, s in enumerate(WIDE_TRAIN_SHAPES)
-                  for B in (17, 1025)])
+                  for B in (17, 1025)]
+               + [pytest.param(s, B, id=f"edge{i}-{B}") for i, s in enumerate(D.EDGE_TRAIN_SHAPES) for B in (17, 1025)])
 
 
 @pytest.fixture(scope="module")
@@ -86,7 +101,7 @@ def on_dev(ids, lab):
 
 
 def table_of(shape):
-    return D.SHAPES if shape in D.SHAPES else D.WIDE_SHAPES
+    return next(t for t in (D.SHAPES, D.WIDE_SHAPES, D.EDGE_SHAPES) if shape in t)
 
 
 def draw(c, shape, B, salt=0):
@@ -120,7 +135,7 @@ def reference(c, fz, ids, lab, sets, B, params=None):
     return r64, r32
 
 
-@pytest.mark.parametrize("shape", list(D.SHAPES) + list(D.WIDE_SHAPES))
+@pytest.mark.parametrize("shape", list(D.SHAPES) + list(D.WIDE_SHAPES) + list(D.EDGE_SHAPES))
 def test_gradients_against_float64(P, shape):
     kernel, batches, _ = table_of(shape)[shape]   # (which dense kernel runs: asserted by the shared-memory rule on the host)
     c = D.GradCase.of(shape)

@@ -16,7 +16,9 @@ from tests.util import GoldenCase
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN_CASES = ["yelp_small", "yelp_emb128", "feat100", "five_rel", "single_rel"]     # every dense instantiation
+# two fixed-shape inference kernels (with / without the weights' LDS copy) and the run-time-shape one that streams the weights:
+# no fixture's shape passes infer_wlds outside the fixed ones - the run-time LDS-weight kernel is tests/test_gpu_edge_shapes.py's
+GOLDEN_CASES = ["yelp_small", "yelp_emb128", "feat100", "five_rel", "single_rel"]
 
 
 def dev():

@@ -15,6 +15,9 @@ from tests import dense_ref as D
 
 # dense_ref.SHAPES' two fixed-shape kernels (with / without the weights' LDS copy) and the two run-time-shape ones (without / with)
 SHAPES = [(32, 64, 3), (32, 128, 3), (10, 16, 1), (24, 16, 5)]
+# the other two fixed-shape kernels (F = 25), a wide row (the F > 64 staging loops), and dense_ref.EDGE_SHAPES' run-time-shape
+# kernels with the weights' LDS copy at E = 64 (R = 4) and E = 128, and without it at E = 272 (17 column tiles for 16 waves)
+SHAPES += [(25, 64, 3), (25, 128, 3), (100, 64, 3), (16, 64, 4), (20, 128, 1), (16, 272, 1)]
 # a lone row, a full tile, a ragged tile, the first size at which pcg_wgrad shares a weight tile between workgroups
 BATCHES = [1, 16, 17, 1025]
 FOCAL_GAMMA, FOCAL_WEIGHT = 2.0, (0.25, 0.75)
