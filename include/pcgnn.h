@@ -56,9 +56,10 @@ enum {
     PCG_ST_SORT_OVERFLOW = 8, /* the one-launch bucket sort of the train positives met a bucket of more than 4096 keys (eight times
                                  the mean): its surplus keys were dropped - minority picks of that step may be wrong */
     PCG_ST_EVAL_INPUT = 16,   /* pcg_eval_counts met a label outside {0, 1} or a NaN probability: its counts describe no valid input */
-    PCG_ST_RANK_MISMATCH = 32 /* pcg_rank_lists / pcg_chosen_set: a row's kept count on the device is not the extent the caller's
+    PCG_ST_RANK_MISMATCH = 32,/* pcg_rank_lists / pcg_chosen_set: a row's kept count on the device is not the extent the caller's
                                  out_begin gives it (or its list region / extent leaves its array); nothing was written for that row.
                                  pcg_rank_minority: a row's extent is negative, above n_pos or leaves its array; not written */
+    PCG_ST_PR_OVERFLOW = 64   /* pcg_pr_counts: more precision-recall points than `cap`; nothing was written past it */
 };
 
 enum { PCG_NORM_COUNT = 0, PCG_NORM_SQRT_COUNT = 1 };
@@ -919,6 +920,41 @@ int pcg_gather_rows(const pcg_graph_desc *g, const int32_t *ids, int32_t n_ids,
 int64_t pcg_eval_workspace_bytes(int64_t n, int32_t n_thresholds);
 int pcg_eval_counts(const float *prob, const int32_t *labels, int64_t n, const double *thresholds, int32_t n_thresholds,
                     void *workspace, uint64_t *out, uint32_t *status, void *stream);
+
+/* ---- ranking counts and the alert list -----------------------------------------
+ * What average precision, precision / recall at k and the top-k alert list are functions of, without leaving the device.
+ * Throughout a row's key is p1 + 0.0f compared as a float (-0.0 ties with +0.0), p1 = prob[i, 1].
+ *
+ * pcg_pr_counts: prob [n, 2] f32, labels [n] i32 in {0, 1}, n <= 2^31 - 1, cap >= 0;
+ *   hdr [8] u64 = tp, fp, fn, tn (of the argmax prediction: 1 iff p1 > p0), n1, n0, G, 0 - the first six are pcg_eval_counts';
+ *   with u_1 > u_2 > ... > u_G the distinct values of p1 over the rows with y = 1 (the only points at which recall changes; G <= n1):
+ *   tp_g [cap] u32 = #{y = 1, p1 >= u_g}, npred_g [cap] u32 = #{p1 >= u_g}; entries [0, min(G, cap)) are written, in descending
+ *   score order.  G > cap: nothing is written past cap and PCG_ST_PR_OVERFLOW is set in *status (cap = n1 always suffices; cap = 0:
+ *   tp_g / npred_g may be NULL, the header alone).
+ * Launches: zero | count pass (confusion words, the positives' keys) | finish | LSD radix sort of the positives' keys (one workgroup
+ * up to 65536 keys; for n above that also three launches per 8-bit pass, which return at once unless n1 is above it too) | bin pass
+ * (every row: a binary search in the sorted keys, one integer add - in LDS per window of 16384 bins up to 524288 positives) | group heads: tile sums, their scan, the compaction (three).
+ * Integer sums only: the output is the same bits on every run.  workspace: pcg_pr_workspace_bytes(n) bytes, 256-byte aligned,
+ * contents irrelevant on entry (capturable).  A label outside {0, 1} (counted as 1) or a NaN probability sets PCG_ST_EVAL_INPUT in
+ * *status.  n == 0: hdr is all zeros.  The float64 statements (average precision, G-mean) are the host's: pc-gnn_amd/utils.py.
+ *
+ * pcg_topk_alerts: the alert order is the stable sort of the rows by key, descending - among equal keys the lower position comes
+ * first, so a tie at the cut is resolved by input position; the call returns its first min(k, n) positions.
+ *   p1: f32, row i at p1[i * stride] (stride 2 with p1 = prob + 1 reads column 1 of [n, 2]; stride 1 a vector), stride >= 1;
+ *   1 <= k <= PCG_ALERTS_MAX_K (else PCG_E_ARG), 0 <= n <= 2^31 - 1;
+ *   out_pos [k] i32, out_score [k] f32 (p1 at that position, bit for bit) in alert order; slots at and beyond n hold -1 / -inf.
+ * Launches: zero | four histogram passes of a radix select of the min(k, n)-th largest key (each picks the previous digit itself) |
+ * per-tile counts of the rows above / equal to it | their scan | position-ordered scatter of every row above it and of the first
+ * rows equal to it | a stable radix sort of the (key, position) pairs by one workgroup.  Integer sums only; the same bits on every
+ * run.  workspace: pcg_topk_alerts_workspace_bytes(n, k) bytes, 256-byte aligned, contents irrelevant on entry (capturable).  A
+ * NaN sets PCG_ST_EVAL_INPUT in *status (it is then ranked above +inf or below -inf by its sign bit). */
+#define PCG_ALERTS_MAX_K 65536
+int64_t pcg_pr_workspace_bytes(int64_t n);
+int pcg_pr_counts(const float *prob, const int32_t *labels, int64_t n, int64_t cap, void *workspace, uint64_t *hdr, uint32_t *tp_g,
+                  uint32_t *npred_g, uint32_t *status, void *stream);
+int64_t pcg_topk_alerts_workspace_bytes(int64_t n, int32_t k);
+int pcg_topk_alerts(const float *p1, int32_t stride, int64_t n, int32_t k, void *workspace, int32_t *out_pos, float *out_score,
+                    uint32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,8 @@ PCG_ST_SYNC_TIMEOUT = 4
 PCG_ST_SORT_OVERFLOW = 8
 PCG_ST_EVAL_INPUT = 16
 PCG_ST_RANK_MISMATCH = 32
+PCG_ST_PR_OVERFLOW = 64
+PCG_ALERTS_MAX_K = 65536
 PCG_NORM_COUNT, PCG_NORM_SQRT_COUNT = 0, 1
 ABI_VERSION = 13
 
@@ -156,6 +158,10 @@ PROTOTYPES = {
     "pcg_attr_neighbours": (C.c_int, [_G, _P, _P, _I32, _I32, _P, _P, _P, _P]),
     "pcg_eval_workspace_bytes": (_I64, [_I64, _I32]),
     "pcg_eval_counts": (C.c_int, [_P, _P, _I64, _P, _I32, _P, _P, _P, _P]),
+    "pcg_pr_workspace_bytes": (_I64, [_I64]),
+    "pcg_pr_counts": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "pcg_topk_alerts_workspace_bytes": (_I64, [_I64, _I32]),
+    "pcg_topk_alerts": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _P, _P]),
     "pcg_step_front_train": (C.c_int, [_G, _ST, _P, _P, _B, _SEL, _P]),
     "pcg_grad_reduce": (C.c_int, [_P, _I32, _I64, _P, _P, _P]),
     "pcg_adam_apply_pending": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _I32, _H, _P]),

@@ -353,6 +353,26 @@ class NearestExamples:
         return self.ids.cpu().numpy(), self.pos.cpu().numpy(), self.score.cpu().numpy()
 
 
+class AlertList:
+    """The k highest-scoring rows of a requested set, in alert order (``FusedPCGNN.alerts``; the kernel: pcg_topk_alerts) -
+    device tensors.  The alert order is the stable sort by positive-class probability, descending: among equal probabilities
+    the lower position in the requested set comes first, so a tie at the cut k is resolved by input position and the list is
+    the same on every run.
+
+    ids [k] int32: node ids (query-local for a query batch) | pos [k] int32: positions in the requested set | prob [k]
+    float32: the positive-class probability; slots beyond the set's size hold -1 / -1 / -inf | hits [k] int64 (only with
+    labels): positives among the alerts up to and including each slot | n: rows that were ranked."""
+
+    def __init__(self, ids: torch.Tensor, pos: torch.Tensor, prob: torch.Tensor, n: int, hits: Optional[torch.Tensor] = None):
+        self.ids, self.pos, self.prob, self.hits = ids, pos, prob, hits
+        self.n, self.k = int(n), int(pos.shape[0])
+
+    def to_numpy(self):
+        """(ids, pos, prob) - with labels (ids, pos, prob, hits) - as host arrays [k]."""
+        out = (self.ids.cpu().numpy(), self.pos.cpu().numpy(), self.prob.cpu().numpy())
+        return out if self.hits is None else out + (self.hits.cpu().numpy(),)
+
+
 class BaseShape:
     """What a ``QueryBatch`` is validated against: the base graph's node count, feature width and relation count.  A
     ``DeviceGraph`` has the same three attributes; this stands in for one where there is no GPU (host-side checks, tests)."""

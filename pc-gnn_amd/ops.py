@@ -487,6 +487,79 @@ def eval_status(device) -> torch.Tensor:
     return cache["status"]
 
 
+def _eval_cache(dev) -> dict:
+    return _EVAL_CACHE.setdefault((dev.type, dev.index if dev.index is not None else torch.cuda.current_device()), {})
+
+
+def _cached_ws(cache: dict, key: str, nbytes: int, dev) -> torch.Tensor:
+    if cache.get(key) is None or cache[key].numel() < nbytes:
+        cache[key] = None
+        cache[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    return cache[key]
+
+
+def pr_counts(prob: torch.Tensor, labels: torch.Tensor, cap: Optional[int] = None, stream=None, status: Optional[torch.Tensor] = None):
+    """The integers average precision and the G-mean are functions of (pcg_pr_counts) -> (hdr, tp_g, npred_g) on the device:
+    hdr int64 [8] = tp, fp, fn, tn, n1, n0, G, 0 (the first six are eval_counts'); tp_g / npred_g int32 [cap] (uint32 words), of
+    which the first min(G, cap) are written, in descending score order: with u_1 > ... > u_G the distinct p1 of the positives,
+    tp_g = #{y = 1, p1 >= u_g}, npred_g = #{p1 >= u_g}.  prob: float32 [n, 2] on the device, labels: int32 [n] on the device;
+    cap: None = n (n1 always suffices); G > cap sets PCG_ST_PR_OVERFLOW in ``status``, a bad label / a NaN PCG_ST_EVAL_INPUT
+    (the per-device default word is read by utils.device_ranking).  Nothing synchronises; the workspace is kept per device."""
+    lib = _lib.load()
+    dev = prob.device
+    if dev.type != "cuda":
+        raise _lib.PcgnnLibraryError("pr_counts runs on the GPU only: there is no CPU fallback for the product path")
+    if prob.dtype != torch.float32 or prob.dim() != 2 or prob.shape[1] != 2 or labels.dtype != torch.int32 or labels.numel() != prob.shape[0]:
+        raise ValueError("pr_counts: prob float32 [n, 2], labels int32 [n]")
+    prob, labels = prob.contiguous(), labels.contiguous()
+    n = prob.shape[0]
+    cap = n if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError("pr_counts: cap >= 0")
+    cache = _eval_cache(dev)
+    nbytes = lib.pcg_pr_workspace_bytes(n)
+    if nbytes < 0:
+        raise _lib.PcgnnLibraryError(f"pcg_pr_workspace_bytes rejected n {n}")
+    ws = _cached_ws(cache, "pr_ws", nbytes, dev)
+    status = eval_status(dev) if status is None else status
+    hdr = torch.empty(8, dtype=torch.int64, device=dev)
+    tp_g = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)     # (an empty tensor has no address)
+    npred_g = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    st = _stream(dev) if stream is None else C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
+    _lib.check(lib.pcg_pr_counts(_p(prob), _p(labels), n, cap, _p(ws), _p(hdr), _p(tp_g), _p(npred_g), _p(status), st), "pcg_pr_counts")
+    return hdr, tp_g[:cap], npred_g[:cap]
+
+
+def topk_alerts(prob: torch.Tensor, k: int, stream=None, status: Optional[torch.Tensor] = None):
+    """The first k rows of the alert order (pcg_topk_alerts) -> (pos int32 [k], score float32 [k]) on the device.  The alert
+    order is the stable sort of the rows by p1 + 0.0f, descending: among equal scores the lower position in the input comes
+    first, so a tie at the cut is resolved by input position.  prob: float32 on the device, [n, 2] (column 1 is ranked) or a
+    vector [n]; 1 <= k <= PCG_ALERTS_MAX_K (65536); slots at and beyond n hold -1 / -inf.  A NaN sets PCG_ST_EVAL_INPUT in
+    ``status`` (default: the per-device word of eval_status).  Nothing synchronises; the workspace is kept per device."""
+    lib = _lib.load()
+    dev = prob.device
+    if dev.type != "cuda":
+        raise _lib.PcgnnLibraryError("topk_alerts runs on the GPU only: there is no CPU fallback for the product path")
+    if prob.dtype != torch.float32 or not (prob.dim() == 1 or (prob.dim() == 2 and prob.shape[1] == 2)):
+        raise ValueError("topk_alerts: prob float32 [n, 2] or [n]")
+    k = int(k)
+    if k < 1 or k > _lib.PCG_ALERTS_MAX_K:
+        raise ValueError(f"topk_alerts: 1 <= k <= {_lib.PCG_ALERTS_MAX_K}")
+    prob = prob.contiguous()
+    n, stride = prob.shape[0], (2 if prob.dim() == 2 else 1)
+    nbytes = lib.pcg_topk_alerts_workspace_bytes(n, k)
+    if nbytes < 0:
+        raise _lib.PcgnnLibraryError(f"pcg_topk_alerts_workspace_bytes rejected n {n} / k {k}")
+    ws = _cached_ws(_eval_cache(dev), "alerts_ws", nbytes, dev)
+    status = eval_status(dev) if status is None else status
+    pos = torch.empty(k, dtype=torch.int32, device=dev)
+    score = torch.empty(k, dtype=torch.float32, device=dev)
+    p1 = None if n == 0 else C.c_void_p(prob.data_ptr() + 4 * (stride - 1))
+    st = _stream(dev) if stream is None else C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
+    _lib.check(lib.pcg_topk_alerts(p1, stride, n, k, _p(ws), _p(pos), _p(score), _p(status), st), "pcg_topk_alerts")
+    return pos, score
+
+
 TOPK_METRICS = {"dot": 0, "cosine": 1, "l2": 2}
 _TOPK_CACHE: dict = {}
 

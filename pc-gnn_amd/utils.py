@@ -145,6 +145,208 @@ def _device_eval(test_nodes, labels, model, batch_size: int, thresholds=None) ->
     return device_metrics(prob, y, thresholds)
 
 
+# ---- ranking metrics: average precision, G-mean, precision / recall at k ---------------------------------------------------------
+# A row's key is its positive-class score p1 compared as a number (-0.0 ties with +0.0).  The ALERT ORDER is the stable sort of the
+# rows by key, descending: among equal keys the lower position in the input comes first.
+_ONE_CLASS = "Only one class present in y_true. ROC AUC score is not defined in that case."
+
+
+def _ranking_inputs(labels, score):
+    y = np.asarray(labels).astype(np.int64).reshape(-1)
+    s = np.asarray(score).reshape(-1)
+    if s.dtype.kind != "f":
+        s = s.astype(np.float64)
+    if len(y) != len(s):
+        raise ValueError(f"{len(y)} labels for {len(s)} scores")
+    if np.any((y != 0) & (y != 1)) or np.any(np.isnan(s)):
+        raise ValueError("evaluation input: a label outside {0, 1} or a NaN probability")
+    return y, s
+
+
+def pr_points(labels, score):
+    """(n1, tp_g, npred_g): with u_1 > ... > u_G the distinct scores of the rows with label 1 - the only points at which recall
+    changes - tp_g = #{y = 1, p1 >= u_g} and npred_g = #{p1 >= u_g}, int64, in descending score order (what pcg_pr_counts
+    forms on the device)."""
+    y, s = _ranking_inputs(labels, score)
+    ps = np.sort(s[y == 1])
+    n1 = len(ps)
+    u, head = np.unique(ps, return_index=True)                         # ascending; head = first index of each value
+    tp = (n1 - head).astype(np.int64)[::-1]
+    npred = (len(s) - np.searchsorted(np.sort(s), u, side="left")).astype(np.int64)[::-1]
+    return n1, tp, npred
+
+
+def _average_precision_from_points(n1: int, tp, npred) -> float:
+    import math
+    tp = np.asarray(tp, dtype=np.int64)
+    d = np.diff(np.concatenate([np.zeros(1, np.int64), tp]))
+    terms = (d.astype(np.float64) / np.float64(n1)) * (tp.astype(np.float64) / np.asarray(npred).astype(np.float64))
+    return math.fsum(terms.tolist())                                   # (exactly rounded: independent of any order)
+
+
+def average_precision(labels, score) -> float:
+    """Average precision (sklearn.metrics.average_precision_score's definition: the sum over the points where recall changes of
+    (recall step) * precision), from integers: terms (d tp / n1) * (tp / npred) in float64, added with math.fsum.  ValueError
+    when there is no positive."""
+    n1, tp, npred = pr_points(labels, score)
+    if n1 == 0:
+        raise ValueError(_ONE_CLASS)
+    return _average_precision_from_points(n1, tp, npred)
+
+
+def conf_gmean(conf) -> float:
+    """The reference's G-mean of a 2 x 2 confusion matrix [[tn, fp], [fn, tp]] (src/utils.py:454-456), on Python ints.
+    ValueError when a class is absent."""
+    tn, fp, fn, tp = (int(v) for v in np.asarray(conf).ravel())
+    if tp + fn == 0 or tn + fp == 0:
+        raise ValueError(_ONE_CLASS)
+    return (tp * tn / ((tp + fn) * (tn + fp))) ** 0.5
+
+
+def alert_order(score) -> np.ndarray:
+    """Positions of the rows in alert order: the stable sort by score, descending (equal scores: the lower position first)."""
+    s = np.asarray(score).reshape(-1)
+    return np.argsort(-(s + s.dtype.type(0)), kind="stable")
+
+
+def _rates_at_k(hits_at, ks, n: int, n1: int):
+    """precision_at / recall_at from hits_at(ke) = positives among the first ke alerts (int / int in Python)."""
+    if n == 0 or n1 == 0:
+        raise ValueError(_ONE_CLASS if n else "precision / recall at k of an empty set")
+    prec, rec = {}, {}
+    for k in ks:
+        k = int(k)
+        if k < 1:
+            raise ValueError("precision / recall at k: k >= 1")
+        ke = min(k, n)
+        h = int(hits_at(ke))
+        prec[k], rec[k] = h / ke, h / n1
+    return prec, rec
+
+
+def precision_recall_at_k(labels, score, ks):
+    """(precision_at, recall_at), dicts keyed by k: with hits = the positives among the first ke = min(k, n) rows of the alert
+    order, precision_at[k] = hits / ke and recall_at[k] = hits / n1.  A tie at the cut is resolved by input position: among
+    equal scores the lower position in the input is ranked first."""
+    y, s = _ranking_inputs(labels, score)
+    hits = np.cumsum(y[alert_order(s)])
+    return _rates_at_k(lambda ke: hits[ke - 1], ks, len(y), int(y.sum()))
+
+
+def ranking_from_counts(hdr, tp_g, npred_g) -> dict:
+    """PURE HOST.  average_precision, gmean, n_pos, n_neg and n_points from what ``pcg_pr_counts`` forms (ops.pr_counts):
+    hdr [8] = tp, fp, fn, tn, n1, n0, G, 0 and the first G entries of tp_g / npred_g.  The float64 statements are
+    ``average_precision``'s and ``conf_gmean``'s, so the values are ``==`` theirs; the same ValueError when a class is absent."""
+    h = [int(v) & 0xFFFFFFFFFFFFFFFF for v in np.asarray(hdr).reshape(-1).tolist()]
+    if len(h) != 8:
+        raise ValueError(f"ranking_from_counts: a header of {len(h)} words (8 expected)")
+    tp, fp, fn, tn, n1, n0, G = h[:7]
+    if n1 != tp + fn or n0 != fp + tn:
+        raise ValueError("ranking_from_counts: n1 / n0 are not the confusion words' sums")
+    if G > n1:
+        raise ValueError(f"ranking_from_counts: {G} points for {n1} positives")
+    tpg = np.asarray(tp_g).reshape(-1).astype(np.int64) & 0xFFFFFFFF
+    npg = np.asarray(npred_g).reshape(-1).astype(np.int64) & 0xFFFFFFFF
+    if len(tpg) < G or len(npg) < G:
+        raise ValueError(f"ranking_from_counts: {G} points, {min(len(tpg), len(npg))} entries")
+    if n1 == 0 or n0 == 0:
+        raise ValueError(_ONE_CLASS)
+    return {"average_precision": _average_precision_from_points(n1, tpg[:G], npg[:G]),
+            "gmean": conf_gmean([[tn, fp], [fn, tp]]), "n_pos": n1, "n_neg": n0, "n_points": G}
+
+
+def host_ranking(labels, prob, ks=()) -> dict:
+    """The ranking metrics of class probabilities [n, 2] that are on the host - what ``device_ranking`` returns: average_precision,
+    gmean (of the argmax prediction, p1 > p0), precision_at / recall_at (dicts keyed by k; ties at the cut by input position),
+    n_pos, n_points."""
+    prob = np.asarray(prob).reshape(-1, 2)
+    y, s = _ranking_inputs(labels, prob[:, 1])
+    if np.any(np.isnan(prob[:, 0])):
+        raise ValueError("evaluation input: a label outside {0, 1} or a NaN probability")
+    pred = prob.argmax(axis=1)
+    conf = [[int(np.sum((pred == 0) & (y == 0))), int(np.sum((pred == 1) & (y == 0)))],
+            [int(np.sum((pred == 0) & (y == 1))), int(np.sum((pred == 1) & (y == 1)))]]
+    n1, tp, npred = pr_points(y, s)
+    if n1 == 0 or n1 == len(y):
+        raise ValueError(_ONE_CLASS)
+    prec, rec = precision_recall_at_k(y, s, ks) if len(ks) else ({}, {})
+    return {"average_precision": _average_precision_from_points(n1, tp, npred), "gmean": conf_gmean(conf),
+            "precision_at": prec, "recall_at": rec, "n_pos": n1, "n_points": len(tp)}
+
+
+def device_ranking(prob_dev, labels, ks=(), cap: Optional[int] = None) -> dict:
+    """``host_ranking`` of class probabilities that are on the device: ops.pr_counts and - for the k below n - ops.topk_alerts, a
+    gather of the labels and a cumulative sum (HIP / torch on the device), then the host arithmetic (``ranking_from_counts``).
+    cap: the capacity for the precision-recall points; the number of positives suffices.  With a cap ONE copy brings the header,
+    the status word, the hit counts and the cap pairs; cap None (n would be needed): the pairs follow in a second copy of
+    exactly G.  labels: int32 on the device, or anything ops._i32 takes.  A k below n is at most PCG_ALERTS_MAX_K (65536).  A
+    tie at the cut k is resolved by input position."""
+    from . import _lib, ops
+    dev = prob_dev.device
+    lab = labels if torch.is_tensor(labels) and labels.dtype == torch.int32 and labels.device == dev else ops._i32(labels, dev)
+    lab = lab.view(-1)
+    n = int(prob_dev.shape[0])
+    ks = [int(k) for k in ks]
+    if any(k < 1 for k in ks):
+        raise ValueError("precision / recall at k: k >= 1")
+    cut = sorted({k for k in ks if k < n})                             # (k >= n: every row, hits = n1)
+    if cut and cut[-1] > _lib.PCG_ALERTS_MAX_K:
+        raise ValueError(f"device_ranking: k {cut[-1]} is above PCG_ALERTS_MAX_K {_lib.PCG_ALERTS_MAX_K} and below n {n}")
+    status = ops.eval_status(dev)
+    hdr, tp_g, npred_g = ops.pr_counts(prob_dev, lab, cap)
+    parts = [hdr, status.to(torch.int64)]
+    if cut:
+        pos, _ = ops.topk_alerts(prob_dev, cut[-1])
+        hits = torch.cumsum((lab[pos.long()] != 0).to(torch.int64), 0)
+        parts.append(hits[torch.tensor([k - 1 for k in cut], dtype=torch.int64, device=dev)])
+    if cap is not None:
+        parts += [tp_g.to(torch.int64), npred_g.to(torch.int64)]
+    words = torch.cat(parts).cpu().numpy()
+    st = int(words[8])
+    if st:
+        status.zero_()
+        if st & _lib.PCG_ST_EVAL_INPUT:
+            raise _lib.PcgnnLibraryError("evaluation input: a label outside {0, 1} or a NaN probability")
+        if st & _lib.PCG_ST_PR_OVERFLOW:
+            raise _lib.PcgnnLibraryError(f"pr_counts: {int(words[6])} precision-recall points do not fit cap {tp_g.numel()}")
+        raise _lib.PcgnnLibraryError(f"device status {st}")
+    hits_at = {k: int(h) for k, h in zip(cut, words[9:9 + len(cut)])}
+    if cap is not None:
+        c = tp_g.numel()
+        pairs = words[9 + len(cut):]
+        m = ranking_from_counts(words[:8], pairs[:c], pairs[c:2 * c])
+    else:
+        G = min(int(words[6]), tp_g.numel())
+        pairs = torch.cat([tp_g[:G], npred_g[:G]]).cpu().numpy()
+        m = ranking_from_counts(words[:8], pairs[:G], pairs[G:])
+    hits_at[n] = m["n_pos"]
+    prec, rec = _rates_at_k(lambda ke: hits_at[ke], ks, n, m["n_pos"]) if ks else ({}, {})
+    return {"average_precision": m["average_precision"], "gmean": m["gmean"], "precision_at": prec, "recall_at": rec,
+            "n_pos": m["n_pos"], "n_points": m["n_points"]}
+
+
+def test_ranking(test_nodes, labels, model, batch_size: int, ks=(100, 1000), on_device: bool = False,
+                 print_line: Optional[bool] = True) -> dict:
+    """The ranking metrics of ``model`` on ``test_nodes``: average_precision, gmean, precision_at / recall_at (dicts keyed by k),
+    n_pos, n_points - the same dict both ways.  Host way (every model): ``predict_proba`` -> ``host_ranking``.  on_device: an
+    engine that has ``evaluate_ranking`` (FusedPCGNN) keeps the probabilities on the device.  A tie at the cut k is resolved
+    by input position.  Prints one line in the style of ``test``."""
+    labels = np.asarray(labels)
+    if on_device:
+        if not hasattr(model, "evaluate_ranking"):
+            raise ValueError("test_ranking(on_device=True) needs an engine that has evaluate_ranking")
+        m = model.evaluate_ranking(np.asarray(test_nodes), labels, ks=ks)
+    else:
+        prob = predict_proba(test_nodes, model, batch_size, labels)
+        if hasattr(model, "check"):
+            model.check()
+        m = host_ranking(labels, prob, ks)
+    if print_line:
+        at = "".join(f"\t- P@{k}: {m['precision_at'][k]:.4f}\t- R@{k}: {m['recall_at'][k]:.4f}" for k in m["precision_at"])
+        print(f"- AveragePrecision: {m['average_precision']:.4f}\t- G-mean: {m['gmean']:.4f}{at}\t\n", end="")
+    return m
+
+
 def predict_proba_new(query, model, ids=None, chunk=None) -> np.ndarray:
     """Positive-class probabilities (float32, on the host) of the rows ``ids`` (None = all) of a ``graph.QueryBatch`` - new
     nodes scored against the resident graph by ``FusedPCGNN.infer_new``: column 1 of the same sigmoid statement as

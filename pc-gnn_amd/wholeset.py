@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .graph import Attribution, ChosenLists, NearestExamples, QueryBatch
+from .graph import AlertList, Attribution, ChosenLists, NearestExamples, QueryBatch
 
 _p = ops._p
 
@@ -542,6 +542,56 @@ class WholeSetCalls:
         if lab.numel() != prob.shape[0]:
             raise ValueError(f"evaluate: {lab.numel()} labels for {prob.shape[0]} ids")
         return U.device_metrics(prob, lab, thresholds)
+
+    def evaluate_ranking(self, ids, labels, ks=(100, 1000), chunk: Optional[int] = None) -> dict:
+        """The ranking metrics of a node set without its probabilities leaving the device: ``infer`` -> sigmoid -> pcg_pr_counts
+        (+ pcg_topk_alerts, a gather of the labels and a cumulative sum when ``ks`` is given) -> ``utils.ranking_from_counts``.
+        Keys: average_precision, gmean (of the argmax prediction), precision_at / recall_at (dicts keyed by k: the positives
+        among the first min(k, n) alerts over min(k, n) / over the number of positives), n_pos, n_points.  The alert order is
+        the stable sort by probability, descending; a tie at the cut k is resolved by input position (the lower position in
+        ``ids`` first).  Every value ``==`` ``utils.host_ranking`` on ``utils.predict_proba``'s output.  ids, labels: as
+        ``evaluate``; labels from the host also size the point arrays (their number of positives)."""
+        from . import utils as U
+        lab = self._eval_labels(labels)
+        cap = None if torch.is_tensor(labels) else int(np.count_nonzero(np.asarray(labels)))
+        with torch.no_grad():
+            prob = torch.sigmoid(self.infer(ids, chunk=chunk)).float()
+        if lab.numel() != prob.shape[0]:
+            raise ValueError(f"evaluate_ranking: {lab.numel()} labels for {prob.shape[0]} ids")
+        return U.device_ranking(prob, lab, ks, cap=cap)
+
+    def alerts(self, ids=None, k: int = 100, chunk: Optional[int] = None, labels=None, query: Optional[QueryBatch] = None) -> AlertList:
+        """The alert list: the k rows of the requested set with the highest positive-class probability, as ``graph.AlertList``
+        (ids / pos / prob [k] on the device, padded with -1 / -1 / -inf when the set has fewer than k rows): ``infer`` -> sigmoid
+        -> pcg_topk_alerts.  The order is the stable sort by probability, descending: among equal probabilities - test-mode
+        scores tie often, at saturated logits and on identical neighbourhoods - the lower position in ``ids`` comes first, so a
+        tie at the cut k is resolved by input position and the list is the same on every run.  ids: as ``infer`` (None = every
+        node); 1 <= k <= 65536.  labels (one per requested row, 0 / 1): the result also holds ``hits`` [k], the positives among
+        the alerts up to each slot.  query: the rows of that ``graph.QueryBatch`` are ranked through ``infer_new`` instead; ids
+        (and the returned ids) are then query-local.  Synchronises (the status words)."""
+        with torch.no_grad():
+            if query is None:
+                _, ids_dev, n = self._resident_ids(ids, "alerts")
+                prob = torch.sigmoid(self.infer(ids, chunk=chunk)).float()
+            else:
+                _, ids_dev, n = self._new_query(query, ids, "alerts")
+                prob = torch.sigmoid(self.infer_new(query, ids=ids, chunk=chunk)).float()
+            status = ops.eval_status(self.dev)
+            pos, score = ops.topk_alerts(prob, int(k))
+            safe = pos.clamp(min=0).long()
+            out_ids = torch.where(pos >= 0, ids_dev[safe] if n else torch.zeros_like(pos), torch.full_like(pos, -1))
+            hits = None
+            if labels is not None:
+                lab = self._eval_labels(labels)
+                if lab.numel() != n:
+                    raise ValueError(f"alerts: {lab.numel()} labels for {n} rows")
+                taken = (lab[safe] != 0) & (pos >= 0) if n else torch.zeros_like(pos, dtype=torch.bool)
+                hits = torch.cumsum(taken.to(torch.int64), 0)
+            st = int(status.item())
+            if st:
+                status.zero_()
+                raise _lib.PcgnnLibraryError("alerts: a NaN probability" if st & _lib.PCG_ST_EVAL_INPUT else f"device status {st}")
+        return AlertList(out_ids, pos, score, n, hits)
 
     def _eval_labels(self, labels) -> torch.Tensor:
         if torch.is_tensor(labels):
