@@ -671,6 +671,33 @@ int pcg_embed_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float 
                   int32_t chunk_rows, float *s0, int32_t score_base, const double *thresholds, void *workspace,
                   int64_t list_capacity, float *out_logits, float *out_center, float *out_emb, float *out_rel, uint32_t *status,
                   void *stream);
+/* Whole-set inference for the GraphSAGE / GCN baselines (BaselineEngine, pc-gnn_amd/baseline.py; src/graphsage.py:62-96, 127-150,
+ * 167-174, 200-232, 262-275).  For centre v: S(v) = row v of relation `rel`'s CSR (sorted, distinct), united with v itself when
+ * add_self is set and v is not in it; c = |S(v)|;
+ *   a(v)   = (sum of X[u], u in S(v)) / den,  den = (float)c (PCG_NORM_COUNT) or sqrtf((float)c) (PCG_NORM_SQRT_COUNT): one float32
+ *            division per element; c == 0: 0 / 0 = NaN, through the ReLU into the logits, like the reference;
+ *   z      = [X[v] | a(v)] (concat_self; K = 2 * feat_dim) or a(v) (K = feat_dim);
+ *   h      = relu(W_enc z), W_enc [emb][K] row-major;   logits = W_cls h, W_cls [2][emb].  No bias.
+ * The CSR row is read in place: no plan, no selection, no per-edge list.  pcg_baseline_workspace_bytes depends on chunk_rows and
+ * g->feat_stride only, never on degrees or edge counts.  A row's values are a function of the row alone - its summation order is
+ * picked by its own degree and fixed, no float atomics - so they are bit for bit the same whatever n, chunk_rows, the row's
+ * position in ids or the call.  The dense part is exact float32 (v_mfma_f32_16x16x4_f32).
+ *   out_logits [n][2];  out_emb [n][emb] (h) or NULL;  out_agg [n][feat_dim] (a) or NULL.
+ * Checks, before any launch: NULL g / g->X / m / W_enc / W_cls / ids / workspace / status / out_logits, n < 0, chunk_rows < 1, rel
+ * outside [0, n_rel), a norm other than the two constants, X or workspace not 16-byte aligned, workspace_bytes below
+ * pcg_baseline_workspace_bytes(g, m, chunk_rows): PCG_E_ARG; emb < 16, emb % 16 != 0, a table the other whole-set calls reject
+ * (feat_stride % 4 != 0 or > 512) or an LDS need above 160 KB: PCG_E_UNSUPPORTED.  n == 0: PCG_OK, nothing is enqueued.
+ * An id outside [0, n_nodes) - in ids or in the CSR - is clamped for the read and sets PCG_ST_LIST_ID_RANGE in *status.
+ * Three launches and a 4-byte memset per chunk; the weights are read during the call only (pass the live parameters). */
+typedef struct pcg_baseline_model {
+    int32_t rel, norm, add_self, concat_self, emb, _pad;
+    const float *W_enc;   /* [emb][K] */
+    const float *W_cls;   /* [2][emb] */
+} pcg_baseline_model;
+int64_t pcg_baseline_workspace_bytes(const pcg_graph_desc *g, const pcg_baseline_model *m, int32_t chunk_rows);
+int pcg_baseline_infer(const pcg_graph_desc *g, const pcg_baseline_model *m, const int32_t *ids, int32_t n, int32_t chunk_rows,
+                       void *workspace, int64_t workspace_bytes, float *out_logits, float *out_emb, float *out_agg,
+                       uint32_t *status, void *stream);
 /* The k most similar rows of bank [M][emb] for every row of Q [n][emb] (both float32, row-major, 16-byte aligned), without an
  * [n][M] matrix: exact-f32 MFMA scores and a running top-k (FusedPCGNN.nearest, ops.topk_similar).
  * metric - the score is always MAXIMISED: 0 dot q.c;  1 cosine q.c / (|q| |c|), 0 when either norm is 0;

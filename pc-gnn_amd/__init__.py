@@ -22,7 +22,8 @@ def __getattr__(name):
         "IntraAgg": ".layers", "InterAgg": ".layers", "InterAgg1": ".layers", "InterAgg3": ".layers",
         "InterAgg5": ".layers", "PCALayer": ".model", "ModelHandler": ".handler", "PCGNNTrainer": ".handler",
         "ResultManager": ".result_manager", "result_manager": None, "utils": None, "synth": None, "fused": None, "ops": None, "layers": None, "model": None, "graph": None,
-        "sampler": None, "handler": None, "graphsage": None, "dist": None,
+        "sampler": None, "handler": None, "graphsage": None, "dist": None, "baseline": None, "wholeset": None,
+        "BaselineEngine": ".baseline",
     }
     if name in table:
         if table[name] is None:

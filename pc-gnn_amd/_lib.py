@@ -77,6 +77,16 @@ class ExplainOut(C.Structure):
 ABI_STRUCTS = (AdamHyper, TrainState, SelectWs, Batch, DenseOut, ExplainOut)     # pcg_abi_layout's `which`, in order
 _H, _ST, _SEL, _B, _OUT, _XOUT = (C.POINTER(t) for t in ABI_STRUCTS)
 
+
+class BaselineModel(C.Structure):
+    """pcg_baseline_model: the shape and the two weight matrices of a GraphSAGE / GCN baseline (pcg_baseline_infer; not one of
+    pcg_abi_layout's structs - those are the training entry points')"""
+    _fields_ = [("rel", _I32), ("norm", _I32), ("add_self", _I32), ("concat_self", _I32), ("emb", _I32), ("_pad", _I32),
+                ("W_enc", _P), ("W_cls", _P)]
+
+
+_BM = C.POINTER(BaselineModel)
+
 # name -> (restype, argtypes); must list every symbol include/pcgnn.h declares
 PROTOTYPES = {
     "pcg_version": (C.c_char_p, []),
@@ -143,6 +153,8 @@ PROTOTYPES = {
     "pcg_infer_new": (C.c_int, [_G, _G, _P, _I32, _P, _I32, _I32, _P, _I32, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P]),
     "pcg_embed_set": (C.c_int, [_G, _P, _I32, _P, _I32, _I32, _P, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P, _P, _P]),
     "pcg_embed_new": (C.c_int, [_G, _G, _P, _I32, _P, _I32, _I32, _P, _I32, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "pcg_baseline_workspace_bytes": (_I64, [_G, _BM, _I32]),
+    "pcg_baseline_infer": (C.c_int, [_G, _BM, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P]),
     "pcg_topk_similar_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "pcg_topk_similar": (C.c_int, [_P, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "pcg_debug_set_topk_slices": (None, [_I32]),

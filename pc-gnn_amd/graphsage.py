@@ -11,6 +11,10 @@ self union (:78-79, :214) and the ``sqrt(count)`` normaliser (:224-226); the sma
 host with Python's ``random`` exactly like the reference (same draws under the same seed: checked
 against a fixture) and aggregates the explicit lists with ``pcg_segment_mean``.
 
+Evaluation of a whole node set in one call - ``model.infer`` / ``embed`` / ``evaluate`` / ``evaluate_ranking`` / ``alerts``,
+and ``utils.test`` with ``model.eval_by_infer = True`` - goes through ``baseline.BaselineEngine`` (pcg_baseline_infer: the CSR
+rows read in place, the encoder and the head on MFMA tiles); the default stays the per-batch ``to_prob`` loop below.
+
 One difference on purpose: ``to_prob`` accepts (and ignores) the ``labels`` / ``train_flag``
 arguments ``utils.test`` passes (utils.py:305), which the reference's ``GCN.to_prob(self, nodes)``
 (:172) does not - with the reference the baselines cannot be evaluated by its own ``test()``.
@@ -173,6 +177,42 @@ class _Head(nn.Module):
     def loss(self, nodes, labels):
         y = torch.as_tensor(labels, device=self.weight.device).long().reshape(-1)
         return self.xent(self.forward(nodes), y)                                 # :37-39 / :176-178
+
+    # -- whole-set calls (baseline.BaselineEngine: one call over a node set instead of the per-batch to_prob loop) ----------------
+    # eval_by_infer: utils.predict_proba / test / test_f1 / test_ranking take the whole-set path (ModelHandler:
+    # ``baseline_whole_set``).  False by default: the per-batch loop, what every caller got before these calls existed.
+    # (utils.test_ranking(on_device=True) does not look at it: it calls evaluate_ranking - the whole-set call - on any model that
+    #  has one, and raised ValueError for a baseline before.)
+    eval_by_infer = False
+
+    def engine(self):
+        """this model's ``baseline.BaselineEngine``, built on first use (it reads the live parameters at every call)"""
+        eng = self.__dict__.get("_engine")
+        if eng is None or eng.dev != self.weight.device:
+            from .baseline import BaselineEngine
+            eng = self.__dict__["_engine"] = BaselineEngine.from_model(self)
+        return eng
+
+    @property
+    def dev(self):
+        return self.weight.device
+
+    def infer(self, ids=None, chunk=None):
+        """logits [n, 2] of a whole node set in one call (``BaselineEngine.infer``)"""
+        return self.engine().infer(ids, chunk=chunk)
+
+    def embed(self, ids=None, chunk=None, want_logits=False, aggregates=False):
+        """the encoder's output [n, E] of a node set (``BaselineEngine.embed``)"""
+        return self.engine().embed(ids, chunk=chunk, want_logits=want_logits, aggregates=aggregates)
+
+    def evaluate(self, ids, labels, thresholds=None, chunk=None):
+        return self.engine().evaluate(ids, labels, thresholds=thresholds, chunk=chunk)
+
+    def evaluate_ranking(self, ids, labels, ks=(100, 1000), chunk=None):
+        return self.engine().evaluate_ranking(ids, labels, ks=ks, chunk=chunk)
+
+    def alerts(self, ids=None, k=100, chunk=None, labels=None, query=None):
+        return self.engine().alerts(ids, k=k, chunk=chunk, labels=labels, query=query)
 
 
 class GraphSage(_Head):

@@ -184,7 +184,8 @@ class ModelHandler(object):
     """``ModelHandler(config).train() -> (auc_test, recall_test, f1_macro_test)`` with the reference's config keys
     (generate_exp_config.ipynb:50-66): data_name, model (PCGNN | SAGE | GCN), seed, train_ratio, test_ratio, emb_size, rho,
     alpha, lr, weight_decay, batch_size, epochs, valid_epochs, patience (+ exp_num, kept for bookkeeping; + the optional
-    ``eval_on_device``: validation / test metrics from the counts formed on the device, ``utils.test(on_device=True)``).
+    ``eval_on_device``: validation / test metrics from the counts formed on the device, ``utils.test(on_device=True)``; + the
+    optional ``baseline_whole_set``: SAGE / GCN are evaluated by one whole-set call, ``baseline.BaselineEngine``, default false).
 
     The reference reads its datasets from files that exist nowhere offline (``load_data``, src/utils.py:66-207), so the
     graph is handed in: ``dataset = (homo, relation_list, feat_data, labels)`` - exactly what ``load_data`` returns
@@ -273,6 +274,8 @@ class ModelHandler(object):
         else:
             raise ValueError(f"model {args.model!r}: PCGNN, SAGE or GCN")
         model = model.to(dev)
+        # (optional key: validation / test through the whole-set call, baseline.BaselineEngine, instead of the per-batch loop)
+        model.eval_by_infer = bool(getattr(args, "baseline_whole_set", False))
         opt = torch.optim.Adam(filter(lambda p: p.requires_grad, model.parameters()), lr=args.lr, weight_decay=args.weight_decay)
         return model, None, opt
 

@@ -156,12 +156,11 @@ def _target_weights(what: str, target):
     return w0, w1
 
 
-class WholeSetCalls:
-    """The whole-set surface of ``fused.FusedPCGNN``, as a mix-in: it has no state and no ``__init__`` of its own.  What it uses
-    of the engine: ``g``, ``lib``, ``dev``, ``E``, ``theta``, ``thresholds``, ``rho``, ``_thr``; ``_stream()``, ``flush()``,
-    ``_raise_status``; ``_param_version``, ``infer_workspace_bytes``, ``_inf`` (every buffer and cache of these calls, grown on
-    demand: status, s0, new_s0, new_s0_version, ws, chosen_ws, new_ws, pos_keys, all_ids, bank, eval_labels) and
-    ``_new_scored_base`` - all of them created by the engine's ``__init__``."""
+class EvalCalls:
+    """What an engine with ``infer`` gets for nothing, as a mix-in without state: the metrics of a node set without its
+    probabilities leaving the device (``evaluate``, ``evaluate_ranking``) and the alert list (``alerts``).  What it uses of the
+    engine: ``infer(ids, chunk=)``, ``g``, ``dev``, ``flush()`` and ``_inf`` (all_ids, eval_labels) - ``alerts(query=)`` also
+    ``infer_new`` / ``_new_query``.  ``WholeSetCalls`` (FusedPCGNN) and ``baseline.BaselineEngine`` (GraphSAGE / GCN) inherit it."""
 
     def _resident_ids(self, ids, what: str):
         """What every call over the resident graph does first: a deferred update applied; -> whole_set_ids of ``ids`` (None =
@@ -172,6 +171,91 @@ class WholeSetCalls:
         if ids is None:
             inf["all_ids"] = ids_dev
         return ids_host, ids_dev, n
+
+    def evaluate(self, ids, labels, thresholds=None, chunk: Optional[int] = None) -> dict:
+        """The evaluation metrics of a node set without its probabilities leaving the device: ``infer`` -> sigmoid (torch, so
+        the scores are the very float32 values ``utils.predict_proba`` hands the host) -> the integer counts (pcg_eval_counts)
+        -> ``utils.metrics_from_counts``: every value ``==`` what ``utils.test`` / ``test_f1`` compute on the host.  ids as
+        ``infer`` (None = every node); labels: the ids' labels (host sequence or tensor) - they go to the device once and are
+        kept for the next pass over the same labels object / the same values; thresholds: None = linspace(0.01, 0.99, 100)."""
+        from . import utils as U
+        lab = self._eval_labels(labels)
+        with torch.no_grad():
+            prob = torch.sigmoid(self.infer(ids, chunk=chunk)).float()
+        if lab.numel() != prob.shape[0]:
+            raise ValueError(f"evaluate: {lab.numel()} labels for {prob.shape[0]} ids")
+        return U.device_metrics(prob, lab, thresholds)
+
+    def evaluate_ranking(self, ids, labels, ks=(100, 1000), chunk: Optional[int] = None) -> dict:
+        """The ranking metrics of a node set without its probabilities leaving the device: ``infer`` -> sigmoid -> pcg_pr_counts
+        (+ pcg_topk_alerts, a gather of the labels and a cumulative sum when ``ks`` is given) -> ``utils.ranking_from_counts``.
+        Keys: average_precision, gmean (of the argmax prediction), precision_at / recall_at (dicts keyed by k: the positives
+        among the first min(k, n) alerts over min(k, n) / over the number of positives), n_pos, n_points.  The alert order is
+        the stable sort by probability, descending; a tie at the cut k is resolved by input position (the lower position in
+        ``ids`` first).  Every value ``==`` ``utils.host_ranking`` on ``utils.predict_proba``'s output.  ids, labels: as
+        ``evaluate``; labels from the host also size the point arrays (their number of positives)."""
+        from . import utils as U
+        lab = self._eval_labels(labels)
+        cap = None if torch.is_tensor(labels) else int(np.count_nonzero(np.asarray(labels)))
+        with torch.no_grad():
+            prob = torch.sigmoid(self.infer(ids, chunk=chunk)).float()
+        if lab.numel() != prob.shape[0]:
+            raise ValueError(f"evaluate_ranking: {lab.numel()} labels for {prob.shape[0]} ids")
+        return U.device_ranking(prob, lab, ks, cap=cap)
+
+    def alerts(self, ids=None, k: int = 100, chunk: Optional[int] = None, labels=None, query: Optional[QueryBatch] = None) -> AlertList:
+        """The alert list: the k rows of the requested set with the highest positive-class probability, as ``graph.AlertList``
+        (ids / pos / prob [k] on the device, padded with -1 / -1 / -inf when the set has fewer than k rows): ``infer`` -> sigmoid
+        -> pcg_topk_alerts.  The order is the stable sort by probability, descending: among equal probabilities - test-mode
+        scores tie often, at saturated logits and on identical neighbourhoods - the lower position in ``ids`` comes first, so a
+        tie at the cut k is resolved by input position and the list is the same on every run.  ids: as ``infer`` (None = every
+        node); 1 <= k <= 65536.  labels (one per requested row, 0 / 1): the result also holds ``hits`` [k], the positives among
+        the alerts up to each slot.  query: the rows of that ``graph.QueryBatch`` are ranked through ``infer_new`` instead; ids
+        (and the returned ids) are then query-local.  Synchronises (the status words)."""
+        with torch.no_grad():
+            if query is None:
+                _, ids_dev, n = self._resident_ids(ids, "alerts")
+                prob = torch.sigmoid(self.infer(ids, chunk=chunk)).float()
+            else:
+                _, ids_dev, n = self._new_query(query, ids, "alerts")
+                prob = torch.sigmoid(self.infer_new(query, ids=ids, chunk=chunk)).float()
+            status = ops.eval_status(self.dev)
+            pos, score = ops.topk_alerts(prob, int(k))
+            safe = pos.clamp(min=0).long()
+            out_ids = torch.where(pos >= 0, ids_dev[safe] if n else torch.zeros_like(pos), torch.full_like(pos, -1))
+            hits = None
+            if labels is not None:
+                lab = self._eval_labels(labels)
+                if lab.numel() != n:
+                    raise ValueError(f"alerts: {lab.numel()} labels for {n} rows")
+                taken = (lab[safe] != 0) & (pos >= 0) if n else torch.zeros_like(pos, dtype=torch.bool)
+                hits = torch.cumsum(taken.to(torch.int64), 0)
+            st = int(status.item())
+            if st:
+                status.zero_()
+                raise _lib.PcgnnLibraryError("alerts: a NaN probability" if st & _lib.PCG_ST_EVAL_INPUT else f"device status {st}")
+        return AlertList(out_ids, pos, score, n, hits)
+
+    def _eval_labels(self, labels) -> torch.Tensor:
+        if torch.is_tensor(labels):
+            return ops._i32(labels, self.dev).view(-1)
+        host = np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)
+        cache = self._inf.setdefault("eval_labels", {})
+        key = host.size                                  # (one set per size: train-time validation and the final test alternate)
+        hit = cache.get(key)
+        if hit is None or not np.array_equal(hit[0], host):
+            if len(cache) >= 4:
+                cache.clear()
+            hit = cache[key] = (host.copy(), torch.from_numpy(host).to(self.dev))
+        return hit[1]
+
+
+class WholeSetCalls(EvalCalls):
+    """The whole-set surface of ``fused.FusedPCGNN``, as a mix-in: it has no state and no ``__init__`` of its own.  What it uses
+    of the engine: ``g``, ``lib``, ``dev``, ``E``, ``theta``, ``thresholds``, ``rho``, ``_thr``; ``_stream()``, ``flush()``,
+    ``_raise_status``; ``_param_version``, ``infer_workspace_bytes``, ``_inf`` (every buffer and cache of these calls, grown on
+    demand: status, s0, new_s0, new_s0_version, ws, chosen_ws, new_ws, pos_keys, all_ids, bank, eval_labels) and
+    ``_new_scored_base`` - all of them created by the engine's ``__init__``."""
 
     def _whole_set_call(self, name: str, ids_dev, n: int, caps, chunk, outputs, query: Optional[QueryBatch] = None,
                         reuse_scores: bool = True, weights=(), list_capacity: Optional[int] = None, read_status: bool = True):
@@ -528,80 +612,3 @@ class WholeSetCalls:
         floats, else ValueError.  The base graph is not modified; the training engine is left alone as by ``infer``.
         Synchronises once (the status word).  Out of scope: ``DistributedPCGNN``, the train-mode selection, GraphSAGE / GCN."""
         return self._explain_new("attribute_new", query, ids, chunk, target, True, bool(neighbours), reuse_scores, _list_capacity)[0]
-
-    def evaluate(self, ids, labels, thresholds=None, chunk: Optional[int] = None) -> dict:
-        """The evaluation metrics of a node set without its probabilities leaving the device: ``infer`` -> sigmoid (torch, so
-        the scores are the very float32 values ``utils.predict_proba`` hands the host) -> the integer counts (pcg_eval_counts)
-        -> ``utils.metrics_from_counts``: every value ``==`` what ``utils.test`` / ``test_f1`` compute on the host.  ids as
-        ``infer`` (None = every node); labels: the ids' labels (host sequence or tensor) - they go to the device once and are
-        kept for the next pass over the same labels object / the same values; thresholds: None = linspace(0.01, 0.99, 100)."""
-        from . import utils as U
-        lab = self._eval_labels(labels)
-        with torch.no_grad():
-            prob = torch.sigmoid(self.infer(ids, chunk=chunk)).float()
-        if lab.numel() != prob.shape[0]:
-            raise ValueError(f"evaluate: {lab.numel()} labels for {prob.shape[0]} ids")
-        return U.device_metrics(prob, lab, thresholds)
-
-    def evaluate_ranking(self, ids, labels, ks=(100, 1000), chunk: Optional[int] = None) -> dict:
-        """The ranking metrics of a node set without its probabilities leaving the device: ``infer`` -> sigmoid -> pcg_pr_counts
-        (+ pcg_topk_alerts, a gather of the labels and a cumulative sum when ``ks`` is given) -> ``utils.ranking_from_counts``.
-        Keys: average_precision, gmean (of the argmax prediction), precision_at / recall_at (dicts keyed by k: the positives
-        among the first min(k, n) alerts over min(k, n) / over the number of positives), n_pos, n_points.  The alert order is
-        the stable sort by probability, descending; a tie at the cut k is resolved by input position (the lower position in
-        ``ids`` first).  Every value ``==`` ``utils.host_ranking`` on ``utils.predict_proba``'s output.  ids, labels: as
-        ``evaluate``; labels from the host also size the point arrays (their number of positives)."""
-        from . import utils as U
-        lab = self._eval_labels(labels)
-        cap = None if torch.is_tensor(labels) else int(np.count_nonzero(np.asarray(labels)))
-        with torch.no_grad():
-            prob = torch.sigmoid(self.infer(ids, chunk=chunk)).float()
-        if lab.numel() != prob.shape[0]:
-            raise ValueError(f"evaluate_ranking: {lab.numel()} labels for {prob.shape[0]} ids")
-        return U.device_ranking(prob, lab, ks, cap=cap)
-
-    def alerts(self, ids=None, k: int = 100, chunk: Optional[int] = None, labels=None, query: Optional[QueryBatch] = None) -> AlertList:
-        """The alert list: the k rows of the requested set with the highest positive-class probability, as ``graph.AlertList``
-        (ids / pos / prob [k] on the device, padded with -1 / -1 / -inf when the set has fewer than k rows): ``infer`` -> sigmoid
-        -> pcg_topk_alerts.  The order is the stable sort by probability, descending: among equal probabilities - test-mode
-        scores tie often, at saturated logits and on identical neighbourhoods - the lower position in ``ids`` comes first, so a
-        tie at the cut k is resolved by input position and the list is the same on every run.  ids: as ``infer`` (None = every
-        node); 1 <= k <= 65536.  labels (one per requested row, 0 / 1): the result also holds ``hits`` [k], the positives among
-        the alerts up to each slot.  query: the rows of that ``graph.QueryBatch`` are ranked through ``infer_new`` instead; ids
-        (and the returned ids) are then query-local.  Synchronises (the status words)."""
-        with torch.no_grad():
-            if query is None:
-                _, ids_dev, n = self._resident_ids(ids, "alerts")
-                prob = torch.sigmoid(self.infer(ids, chunk=chunk)).float()
-            else:
-                _, ids_dev, n = self._new_query(query, ids, "alerts")
-                prob = torch.sigmoid(self.infer_new(query, ids=ids, chunk=chunk)).float()
-            status = ops.eval_status(self.dev)
-            pos, score = ops.topk_alerts(prob, int(k))
-            safe = pos.clamp(min=0).long()
-            out_ids = torch.where(pos >= 0, ids_dev[safe] if n else torch.zeros_like(pos), torch.full_like(pos, -1))
-            hits = None
-            if labels is not None:
-                lab = self._eval_labels(labels)
-                if lab.numel() != n:
-                    raise ValueError(f"alerts: {lab.numel()} labels for {n} rows")
-                taken = (lab[safe] != 0) & (pos >= 0) if n else torch.zeros_like(pos, dtype=torch.bool)
-                hits = torch.cumsum(taken.to(torch.int64), 0)
-            st = int(status.item())
-            if st:
-                status.zero_()
-                raise _lib.PcgnnLibraryError("alerts: a NaN probability" if st & _lib.PCG_ST_EVAL_INPUT else f"device status {st}")
-        return AlertList(out_ids, pos, score, n, hits)
-
-    def _eval_labels(self, labels) -> torch.Tensor:
-        if torch.is_tensor(labels):
-            return ops._i32(labels, self.dev).view(-1)
-        host = np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)
-        cache = self._inf.setdefault("eval_labels", {})
-        key = host.size                                  # (one set per size: train-time validation and the final test alternate)
-        hit = cache.get(key)
-        if hit is None or not np.array_equal(hit[0], host):
-            if len(cache) >= 4:
-                cache.clear()
-            hit = cache[key] = (host.copy(), torch.from_numpy(host).to(self.dev))
-        return hit[1]
