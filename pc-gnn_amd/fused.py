@@ -32,17 +32,21 @@ autograd (the backward is ``pcg_dense_vjp`` - the dense kernel's backward from t
 
 The whole-set calls over the resident graph and over query batches (``infer``, ``chosen``, ``attribute``, ``embed``, ``nearest``,
 ``evaluate``, the ``*_new`` forms) and their host planner live in wholeset.py; ``FusedPCGNN`` inherits them (``WholeSetCalls``).
+The hipGraph capture and the staged-epoch engine (``train_step_graph``, ``stage_epoch`` .. ``epoch_run``) live in epoch.py
+(``EpochCalls``); the launches of a step - every ``_enqueue_*`` - are here.
 
 Reference loop replaced: src/model_handler.py:147-153 (and :305 of utils.py for
 ``predict``).
 """
 import ctypes as C
 import os
+from contextlib import contextmanager
 from typing import Dict, Optional
 
 import torch
 
 from . import _lib, ops
+from .epoch import EpochCalls
 from .graph import DeviceGraph
 from .model import PCALayer
 from .wholeset import (WholeSetCalls, default_infer_chunk, infer_chunks, infer_row_caps, whole_set_buffers,  # noqa: F401
@@ -79,7 +83,7 @@ class _SeededDense(torch.autograd.Function):
         return (None, None, None, None) + tuple(fz._by_name(flat).values())
 
 
-class FusedPCGNN(WholeSetCalls):
+class FusedPCGNN(EpochCalls, WholeSetCalls):
     def __init__(self, model: PCALayer, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8,
                  max_batch: int = 1024, global_batch_scale: int = 1, list_capacity: Optional[int] = None,
                  pipeline: Optional[bool] = None, infer_workspace_bytes: int = 1 << 30, clf_ahead: Optional[bool] = None):
@@ -163,10 +167,7 @@ class FusedPCGNN(WholeSetCalls):
         else:
             self.clf_ahead = g.n_pos >= 1024
         self.status = torch.zeros(1, dtype=torch.int32, device=self.dev)   # ONE device status word
-        self._graphs = {}
-        self._ep_graphs = {}
-        self._ep_sets = None       # two sets of epoch buffers: ids | labels | plan slots (stage_epoch)
-        self._cur, self._cur_ready, self._ep_stride = 0, False, 0
+        self._init_epoch_state()   # (captured graphs, the two sets of epoch buffers: _alloc clears them)
         self._thr, self._rhos = ops._host_arrays(g, self.thresholds, self.rho)
         self._hyper = _lib.AdamHyper(lr, betas[0], betas[1], eps, weight_decay)
         self._alloc(max_batch)
@@ -264,6 +265,48 @@ class FusedPCGNN(WholeSetCalls):
     def _stream(self):
         return ops._stream(self.dev)
 
+    def _agg_of(self, B) -> torch.Tensor:
+        """the aggregates of a batch of B: the front of ``agg`` as [R, B, F]"""
+        R, F = self.R, self.F
+        return self.agg.view(-1)[:R * B * F].view(R, B, F)
+
+    def _cnt_of(self, B, p: int = 0) -> torch.Tensor:
+        """the kept counts of a batch of B in count buffer p, flat (``last_counts`` is the [R, B] view of the same storage)"""
+        return self.cnt2[p].view(-1)[:self.R * B]
+
+    def _fit(self, B, flush: bool = True):
+        """Grow every buffer for a batch above max_batch.  A deferred update is applied first - it lives in buffers that are
+        replaced; flush=False: the caller has flushed already."""
+        if B > self.maxB:
+            if flush:
+                self.flush()
+            self._alloc(B)
+
+    @contextmanager
+    def _bracket(self, always: bool = False):
+        """Two timing events around the launches made inside, appended to ``_prof`` as a (start, end) pair (bench.py).  Nothing is
+        recorded while ``_prof`` is None or the stream is capturing.  always: the events are recorded whatever ``_prof`` is - a
+        timed sequence of graph replays costs the same with and without a reader - and appended only if it is set."""
+        if not always and (self._prof is None or torch.cuda.is_current_stream_capturing()):
+            yield
+            return
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        yield
+        ev[1].record()
+        if self._prof is not None:
+            self._prof.append(ev)
+
+    @contextmanager
+    def _choosing(self, B):
+        """What the two select + gather calls share: -> (aggregates [R, B, F], flat counts) of the batch for the library call
+        made inside, which is bracketed for ``_prof``; afterwards ``last_counts`` names the counts it wrote."""
+        self._live = None                            # (lists, aggregates and counts are overwritten)
+        agg, cnt = self._agg_of(B), self._cnt_of(B)
+        with self._bracket():
+            yield agg, cnt
+        self.last_counts = cnt.view(self.R, B)
+
     def _plan_bytes(self, B):
         n = self.lib.pcg_choose_plan_bytes(self.g.desc_ref(), B, self.list_capacity)
         if n < 0:
@@ -360,24 +403,14 @@ class FusedPCGNN(WholeSetCalls):
         """select (+ the label classifier's step for this batch) and gather (+ the deferred update of the other parameters,
         + the next step's scores if score_next) of a training step: pcg_choose_gather_train."""
         g = self.g
-        self._live = None                            # (lists, aggregates and counts are overwritten)
-        agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
-        cnt = self.cnt.view(-1)[:g.R * B].view(g.R, B)
-        timed = self._prof is not None and not torch.cuda.is_current_stream_capturing()
-        if timed:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        _lib.check(self.lib.pcg_choose_gather_train(
-            g.desc_ref(), self._batch(ids, labels, B, plan, cnt), _p(self.s0), _p(self.keys) if g.n_pos else None, self._sel,
-            _p(agg), agg.stride(-2), self._st, 1 if score_next else 0,
-            None if next_touched is None else C.c_void_p(next_touched), 1 if self.presort else 0, self._stream()),
-            "pcg_choose_gather_train")
-        if timed:
-            ev[1].record()
-            self._prof.append(ev)
-        self.last_counts = cnt
+        with self._choosing(B) as (agg, cnt):
+            _lib.check(self.lib.pcg_choose_gather_train(
+                g.desc_ref(), self._batch(ids, labels, B, plan, cnt), _p(self.s0), _p(self.keys) if g.n_pos else None, self._sel,
+                _p(agg), agg.stride(-2), self._st, 1 if score_next else 0,
+                None if next_touched is None else C.c_void_p(next_touched), 1 if self.presort else 0, self._stream()),
+                "pcg_choose_gather_train")
         self._fresh = bool(score_next)
-        return agg, cnt
+        return agg, self.last_counts
 
     def _enqueue_choose(self, ids, labels, B, keys, train_flag, plan: int, sort_in_kernel: bool):
         """select + gather over the batch's plan (rows of several chunks are left as partial sums for the dense kernel).
@@ -385,22 +418,12 @@ class FusedPCGNN(WholeSetCalls):
         select kernel sorts them itself unless there are too many: then they are sorted already) and the launch clears the
         "deferred update pending" word."""
         g = self.g
-        self._live = None                            # (lists, aggregates and counts are overwritten)
-        agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
-        cnt = self.cnt.view(-1)[:g.R * B].view(g.R, B)
-        timed = self._prof is not None and not torch.cuda.is_current_stream_capturing()
-        if timed:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        _lib.check(self.lib.pcg_choose_gather_planned(
-            g.desc_ref(), _p(ids), _p(labels if train_flag else None), B, _p(self.s0), None, _p(keys), self._thr, self._rhos,
-            1 if train_flag else 0, 0, _p(agg), agg.stride(-2), _p(cnt), _p(self.data), C.c_void_p(plan), self.list_capacity,
-            _p(self.status), _p(self.sync) if sort_in_kernel else None, self._stream()), "pcg_choose_gather_planned")
-        if timed:
-            ev[1].record()
-            self._prof.append(ev)
-        self.last_counts = cnt
-        return agg, cnt
+        with self._choosing(B) as (agg, cnt):
+            _lib.check(self.lib.pcg_choose_gather_planned(
+                g.desc_ref(), _p(ids), _p(labels if train_flag else None), B, _p(self.s0), None, _p(keys), self._thr, self._rhos,
+                1 if train_flag else 0, 0, _p(agg), agg.stride(-2), _p(cnt), _p(self.data), C.c_void_p(plan), self.list_capacity,
+                _p(self.status), _p(self.sync) if sort_in_kernel else None, self._stream()), "pcg_choose_gather_planned")
+        return agg, self.last_counts
 
     def _enqueue_tail(self, ids, labels, B, agg, plan: int, train: bool, combined=None, adam_clf: Optional[bool] = None, cnt=None):
         """dense tail reading the gather's partial sums (no combine launch); training: the gradient slabs are left pending
@@ -410,7 +433,7 @@ class FusedPCGNN(WholeSetCalls):
         reduces / all-reduces them itself; 1: the label classifier's Adam by the kernel's last workgroup (the four-launch step of
         pcg_step_scores_train); 4: transposed activations only, nothing marked as waiting (gradients())."""
         g = self.g
-        cnt = self.cnt.view(-1)[:g.R * B] if cnt is None else cnt
+        cnt = self._cnt_of(B) if cnt is None else cnt
         adam_clf = (3 if train else 0) if adam_clf is None else int(adam_clf)
         out = _lib.DenseOut(_p(self.logits), _p(self.center), _p(combined), _p(self.row_loss) if labels is not None else None)
         _lib.check(self.lib.pcg_train_dense(
@@ -433,7 +456,7 @@ class FusedPCGNN(WholeSetCalls):
         bufs: the (s0, keys) pair the launch reads (select) or writes (the gather launch's score pass), default the engine's own"""
         g = self.g
         self._live = None                            # (lists, aggregates and counts are overwritten)
-        agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
+        agg = self._agg_of(B)
         s0, keys = (self.s0, self.keys) if bufs is None else bufs
         _lib.check(self.lib.pcg_choose_train_part(
             part, g.desc_ref(), self._batch(ids, labels, B, plan, cnt), _p(s0), _p(keys) if g.n_pos else None, self._sel, _p(agg),
@@ -464,9 +487,8 @@ class FusedPCGNN(WholeSetCalls):
         n = len(steps)
         if not self._fresh:
             self._enqueue_refresh()
-        R, F = g.R, g.feat_dim
         st = self._stream()
-        cnt = lambda p, B: self.cnt2[p].view(-1)[:R * B]
+        cnt = lambda p, B: self._cnt_of(B, p)
         own, alt = (self.s0, self.keys), (self.s0_alt, self.keys_alt)
         buf = lambda t: own if (n - t) % 2 == 0 else alt
         slot = lambda t: self.clf_slots[t % 3]
@@ -480,7 +502,7 @@ class FusedPCGNN(WholeSetCalls):
         for t, (ids, lab, B, plan) in enumerate(steps):
             # (the gather launch's score pass writes batch t + 2's buffers with the classifier the launch before has stepped)
             self._enqueue_part(2, ids, lab, B, plan, cnt(p, B), 0, bufs=buf(t + 2), score_next=t + 2 <= n)
-            agg = self.agg.view(-1)[:R * B * F].view(R, B, F)
+            agg = self._agg_of(B)
             if t + 1 == n:
                 self._enqueue_tail(ids, lab, B, agg, plan, True, cnt=cnt(p, B))       # (_fresh is off: no key sort rides here)
                 break
@@ -493,7 +515,7 @@ class FusedPCGNN(WholeSetCalls):
                 self._out, _p(slot(t + 2)) if cB else None, _p(s0n), _p(keysn) if g.n_pos else None,
                 _p(buf(t + 2)[1]) if (g.n_pos and t + 2 <= n) else None, st), "pcg_dense_select_ahead")
             p ^= 1
-        self.last_counts = self.cnt2[p].view(-1)[:R * B].view(R, B)
+        self.last_counts = cnt(p, B).view(g.R, B)
         self._fresh = True
 
     def _enqueue_pipelined(self, steps):
@@ -508,15 +530,14 @@ class FusedPCGNN(WholeSetCalls):
         g, lib = self.g, self.lib
         if not self._fresh:
             self._enqueue_refresh()
-        R, F = g.R, g.feat_dim
         st = self._stream()
-        cnt = lambda p, B: self.cnt2[p].view(-1)[:R * B]
+        cnt = lambda p, B: self._cnt_of(B, p)
         ids, lab, B, plan = steps[0]
         self._enqueue_part(1, ids, lab, B, plan, cnt(0, B), 1 if self.presort else 0, clf_out=self.clf_slots[0])
         p = 0
         for t, (ids, lab, B, plan) in enumerate(steps):
             self._enqueue_part(2, ids, lab, B, plan, cnt(p, B), 0)
-            agg = self.agg.view(-1)[:R * B * F].view(R, B, F)
+            agg = self._agg_of(B)
             if t + 1 == len(steps):
                 self._fresh = True
                 self._enqueue_tail(ids, lab, B, agg, plan, True, cnt=cnt(p, B))
@@ -527,7 +548,7 @@ class FusedPCGNN(WholeSetCalls):
                 self._batch(nids, nlab, nB, nplan, cnt(p ^ 1, nB)), _p(agg), agg.stride(1), _p(self.clf_slots[p]), self._out,
                 _p(self.clf_slots[p ^ 1]), _p(self.s0), _p(self.keys) if g.n_pos else None, st), "pcg_dense_select_train")
             p ^= 1
-        self.last_counts = self.cnt2[p].view(-1)[:R * B].view(R, B)
+        self.last_counts = cnt(p, B).view(g.R, B)
         self._fresh = True
 
     def flush(self):
@@ -577,9 +598,7 @@ class FusedPCGNN(WholeSetCalls):
         if B == 0:
             return
         self._theta_written()
-        if B > self.maxB:
-            self.flush()
-            self._alloc(B)
+        self._fit(B)
         self._lastB = B
         if allreduce is None:
             if plan is None:
@@ -595,432 +614,7 @@ class FusedPCGNN(WholeSetCalls):
         self._enqueue_adam(B, apply=True, from_grad=True)
         self.clf_next.copy_(self.theta[self.n_rest:])      # (the label classifier is stepped with everything else here)
 
-    def train_step_graph(self, ids: torch.Tensor, labels: torch.Tensor, timed: bool = False):
-        """Same as train_step through captured hipGraphs (one set per batch size): one graph launch
-        per step.  timed=True (bench.py, every Nth step) replays the step as [plan + scores graph] ->
-        choose+aggregate bracketed by HIP events -> [dense+Adam graph]; same kernels, same order."""
-        B = ids.numel()
-        if B == 0:
-            return
-        self._theta_written()
-        if B > self.maxB:
-            self.flush()
-            self._alloc(B)
-        self._lastB = B
-        gr = self._graphs.get(B)
-        if gr is None:
-            gr = self._capture(B)
-        self.ids_buf[:B].copy_(ids)
-        self.lab_buf[:B].copy_(labels)
-        if timed and self._prof is not None:
-            gr["pre"].replay()
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-            gr["choose"].replay()          # the same launches as inside "full", as a graph of their own
-            ev[1].record()
-            self._prof.append(ev)
-            self.last_counts = self.cnt.view(-1)[:self.g.R * B].view(self.g.R, B)
-            gr["post"].replay()
-        else:
-            gr["full"].replay()
-
-    def _capture_graphs(self, fns, warm=None):
-        """Warm up (kernel attributes, per-batch-size plan slots: nothing may allocate inside a capture) on a side
-        stream, capture every fn into a hipGraph of its own, and put the optimizer state back.  A deferred Adam update
-        of real steps is applied first (the saved state then includes it); the warm-up's own is flushed and undone."""
-        self.flush()
-        # (the classifier slots, s0_alt / keys_alt and the second count buffer are scratch of ONE pipelined sequence: nothing of
-        #  them is read after it, so they are not part of the state; s0 / keys are marked stale below)
-        state = (self.theta.clone(), self.m.clone(), self.v.clone(), self.step_counter.clone(), self.clf_next.clone())
-        prof, self._prof = self._prof, None
-        s = torch.cuda.Stream(self.dev)
-        s.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(s):
-            for fn in (warm if warm is not None else fns):
-                fn()
-            self.flush()
-        torch.cuda.current_stream(self.dev).wait_stream(s)
-        graphs = []
-        # (no garbage collection while a stream is capturing: a collected engine of the caller's - tensors, events, other graphs -
-        #  is torn down with HIP calls that are not allowed during a capture and end the process)
-        import gc
-        gc.collect()
-        was_on = gc.isenabled()
-        gc.disable()
-        try:
-            for fn in fns:
-                gr = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gr):
-                    fn()
-                graphs.append(gr)
-        finally:
-            if was_on:
-                gc.enable()
-        for dst, src in zip((self.theta, self.m, self.v, self.step_counter, self.clf_next), state):
-            dst.copy_(src)
-        self._fresh = False                          # (s0 holds the warm-up's scores)
-        self._prof = prof
-        return graphs
-
-    def _capture(self, B):
-        ids, lab = self.ids_buf[:B], self.lab_buf[:B]
-        keys = self.keys if self.g.n_pos else None
-        g = self.g
-        agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
-        plan = self._plan_slot(B).data_ptr()
-
-        def pre():                     # (a step on its own: nothing is known about the batch before or after it)
-            self._enqueue_plan_one(ids, lab, B, True)
-            self._enqueue_refresh(self._touch_one.data_ptr() if self.touched_on else None)
-
-        def post():
-            self._enqueue_tail(ids, lab, B, agg, plan, True)
-            self.flush()
-
-        def choose():
-            self._enqueue_choose_train(ids, lab, B, plan, False)
-
-        def full():
-            pre()
-            choose()
-            post()
-
-        names = ("full", "pre", "choose", "post")
-        graphs = dict(zip(names, self._capture_graphs([full, pre, choose, post], warm=[full])))
-        self._graphs[B] = graphs
-        return graphs
-
-    # -- whole-epoch path: ids / labels of an epoch live in static buffers, one plan slot and one graph per batch ------
-    # There are TWO sets of epoch buffers (ids | labels | plan slots).  The picks of an epoch and its plans depend on nothing
-    # a training step computes, so with ``epoch_run(prefetch=True)`` the sampler and the plan launches of epoch e + 1 run on a
-    # parallel branch of epoch e's graph, into the other set - off the steps' serial chain altogether.
-    @property
-    def _ep_ids(self):
-        return None if self._ep_sets is None else self._ep_sets[self._cur]["ids"]
-
-    @property
-    def _ep_lab(self):
-        return self._ep_sets[self._cur]["lab"]
-
-    @property
-    def _ep_plans(self):
-        return None if self._ep_sets is None else self._ep_sets[self._cur]["plans"]
-
-    def stage_epoch(self, n: int, batch_size: int, n_epochs: int = 1):
-        """Static id / label buffers and plan slots of n_epochs epochs of n picks each (the ids are filled by begin_epoch or by a
-        sampler; ``plan_staged()`` must follow before any of the staged steps runs).  Several epochs staged together are sampled
-        and planned by ONE launch each - the sampler's and the plan's latency chains are paid once per n_epochs epochs - and are
-        walked as one sequence of batches 0 .. n_epochs * ceil(n / batch_size) - 1 (every epoch's last batch may be the shorter
-        one).  Returns the CURRENT set's (ids, labels), n_epochs * n long.
-        Another (n, batch_size, n_epochs) than the last call's DROPS a set that ``epoch_run(prefetch=...)`` has prepared: its ids
-        and plans are laid out for the old shape.  The call waits for whatever is still preparing it, the set counts as not
-        ready, and the next epoch is sampled and planned anew, at the new shape.  The epoch numbers the dropped set had consumed
-        are SKIPPED, not drawn again: the sampler's device counter only ever moves forward (it was moved on when the set was
-        planned), so the next epoch sampled is the one after the dropped set's last.  Every epoch number still names
-        independent draws of the same distribution, and no number is trained twice."""
-        if batch_size > self.maxB:
-            self.flush()
-            self._alloc(batch_size)
-        nb_e = -(-n // batch_size)
-        nb, total = nb_e * n_epochs, n * n_epochs
-        stride = self._plan_bytes(batch_size)
-        sets = self._ep_sets
-        if sets is None or sets[0]["ids"].numel() < total or self._ep_stride != stride or sets[0]["plans"].numel() < nb * stride:
-            if torch.cuda.is_current_stream_capturing():
-                raise _lib.PcgnnLibraryError("stage_epoch with a new shape inside a graph capture")
-            self._drop_prepared()                    # (before the old buffers go: nothing may still be writing them)
-            self._ep_sets = [dict(ids=torch.zeros(total, dtype=torch.int32, device=self.dev),
-                                  lab=torch.zeros(total, dtype=torch.int32, device=self.dev),
-                                  plans=torch.zeros(nb * stride, dtype=torch.uint8, device=self.dev),
-                                  touched=torch.zeros(nb * self._touch_stride, dtype=torch.uint8, device=self.dev)
-                                  if self.touched_on else None) for _ in range(2)]
-            self._ep_stride = stride
-            self._cur, self._cur_ready = 0, False
-            self._ep_graphs.clear()
-        shape = (n, batch_size, n_epochs)
-        if getattr(self, "_ep_shape", shape) != shape:
-            # another epoch shape inside the same buffers: the last batch's (shorter) plan layout moves to another slot, and the
-            # plan launch's look-back tags (a small integer per workgroup) would sit on top of whatever the old layout left
-            # there - zero the slots so that no stale word can pass for a published total
-            if torch.cuda.is_current_stream_capturing():
-                raise _lib.PcgnnLibraryError("stage_epoch with a new epoch size inside a graph capture")
-            # a set prepared ahead holds the old shape's ids and is about to lose its plans: it is dropped (its epoch numbers are
-            # skipped), after whatever is still writing it has finished
-            self._drop_prepared()
-            for st in self._ep_sets:
-                st["plans"].zero_()
-            self._ep_graphs.clear()
-        self._ep_shape = shape
-        self._ep_n, self._ep_bs, self._ep_k = n, batch_size, n_epochs
-        # batch j of the staged sequence: (first pick, size)
-        self._ep_batches = [(e * n + b * batch_size, min(batch_size, n - b * batch_size)) for e in range(n_epochs) for b in range(nb_e)]
-        return self._ep_ids[:total], self._ep_lab[:total]
-
-    def _drop_prepared(self):
-        """Forget a set that ``epoch_run(prefetch=...)`` has sampled and planned ahead - its buffers are about to be rewritten or
-        replaced.  The current stream first waits for the side stream's sampler and plan launches (prefetch="stream"): nothing
-        may still be writing the set.  The epoch numbers it had consumed are skipped (``stage_epoch``)."""
-        if not torch.cuda.is_current_stream_capturing():      # (a capturing stream cannot wait for work outside its capture)
-            main = torch.cuda.current_stream(self.dev)
-            if getattr(self, "_ev_ready", None) is not None:
-                main.wait_event(self._ev_ready)
-            if getattr(self, "_side", None) is not None:
-                main.wait_stream(self._side)
-        self._cur_ready, self._ev_ready = False, None
-
-    def take_prefetched(self) -> bool:
-        """True if the current set already holds a sampled and planned epoch that no step has used yet (left by
-        ``epoch_run(prefetch=True)``) - the caller then starts on it instead of sampling; the set counts as used from here on."""
-        ready, self._cur_ready = self._cur_ready, False
-        if ready and getattr(self, "_ev_ready", None) is not None:       # (prepared on the side stream: epoch_run(prefetch="stream"))
-            torch.cuda.current_stream(self.dev).wait_event(self._ev_ready)
-            self._ev_ready = None
-        return ready
-
-    def plan_staged(self, bump_counter: Optional[torch.Tensor] = None, which: Optional[int] = None):
-        """Plan every batch of the staged epoch (set `which`, default the current one): one launch (after the sampler, before
-        the epoch's first step).  bump_counter: the sampler's device epoch counter, incremented by it."""
-        st = self._ep_sets[self._cur if which is None else which]
-        self._enqueue_plan(st["ids"], st["lab"], self._ep_n, self._ep_bs, st["plans"], self._ep_stride, True, bump_counter, self._ep_k)
-        if self.touched_on:
-            nb_e = -(-self._ep_n // self._ep_bs)
-            for e in range(self._ep_k):              # (an epoch's last batch may be the shorter one: the maps are made epoch by epoch)
-                self._enqueue_mark(st["ids"][e * self._ep_n:], self._ep_n, self._ep_bs, st["touched"][e * nb_e * self._touch_stride:],
-                                   st["plans"].data_ptr() + e * nb_e * self._ep_stride, self._ep_stride)
-            self._fresh = False                      # (new maps: the rows scored so far need not cover the new first batch)
-
-    def _ep_plan(self, b: int, which: Optional[int] = None) -> int:
-        return self._ep_sets[self._cur if which is None else which]["plans"].data_ptr() + b * self._ep_stride
-
-    def _ep_touch(self, b: int, which: Optional[int] = None) -> Optional[int]:
-        if not self.touched_on:
-            return None
-        return self._ep_sets[self._cur if which is None else which]["touched"].data_ptr() + b * self._touch_stride
-
-    def _ep_next_touch(self, b: int, which: Optional[int] = None) -> Optional[int]:
-        """the map of the batch after b, if the staged sequence has one"""
-        if not self.touched_on or b + 1 >= len(self._ep_batches):
-            return None
-        return self._ep_touch(b + 1, which)
-
-    def begin_epoch(self, ids: torch.Tensor, labels: torch.Tensor, batch_size: int):
-        """Stage an epoch's (already shuffled) ids and labels and plan its batches; afterwards ``epoch_step(b)`` is exactly
-        one graph launch - no copies, no indexing kernels (model_handler.py:142-148 slices a Python list here)."""
-        n = ids.numel()
-        ep_ids, ep_lab = self.stage_epoch(n, batch_size)
-        self._drop_prepared()                        # (the ids go into the current set: an epoch prepared ahead there is lost)
-        ep_ids.copy_(ids)
-        ep_lab.copy_(labels)
-        self.plan_staged()
-
-    def epoch_step(self, b: int, defer: bool = False):
-        """Batch b of the staged (and planned) epoch as one graph replay.  defer: as inside epoch_run - the Adam update of
-        everything but the label classifier is left to the next batch's front launch (the epoch's last batch flushes it), so
-        the parameters are complete only after the last batch or a flush()."""
-        if b >= len(self._ep_batches):
-            return
-        lo, B = self._ep_batches[b]
-        self._lastB = B
-        self._theta_written()
-        defer = defer and b + 1 < len(self._ep_batches)
-        key = (self._cur, lo, B, self._ep_shape, "deferred") if defer else (self._cur, lo, B, self._ep_shape)
-        gr = self._ep_graphs.get(key)
-        if gr is None:
-            ids, lab = self._ep_ids[lo:lo + B], self._ep_lab[lo:lo + B]
-            gr = self._capture_graphs([lambda: self.train_step(ids, lab, defer=defer, plan=self._ep_plan(b), touched=self._ep_touch(b),
-                                                               next_touched=self._ep_next_touch(b))])[0]
-            self._ep_graphs[key] = gr
-        if not self._fresh:                          # (the graph was captured with the scores at hand, or scores them itself)
-            self._enqueue_refresh(self._ep_touch(b))
-        gr.replay()
-        self._fresh = (not self.touched_on) or self._ep_next_touch(b) is not None
-
-    def epoch_step_timed(self, b: int, eager: bool = True, flush: bool = True):
-        """Batch b of the staged epoch with HIP events around the select + gather call (appended to ``_prof``): the same
-        kernels in the same order as one step of ``epoch_run``, reading the staged ids in place (no copies, no label
-        gather).  eager: the four kernels launched one by one with the two event records between them (the host stays
-        ahead of the GPU, so the events bracket the two kernels and nothing else); otherwise three graphs - scores | select +
-        gather | dense - whose launch latency lands inside the bracket."""
-        if b >= len(self._ep_batches):
-            return
-        lo, B = self._ep_batches[b]
-        self._lastB = B
-        self._theta_written()
-        key = (self._cur, lo, B, self._ep_shape, "timed")
-        grs = self._ep_graphs.get(key)
-        ids, lab = self._ep_ids[lo:lo + B], self._ep_lab[lo:lo + B]
-        g = self.g
-        plan = self._ep_plan(b)
-        agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
-        keys = self.keys if g.n_pos else None
-        # the staged sequence's last batch: nothing follows that would apply the deferred update (flush=False: the caller's next
-        # launches - the next group's first gather launch, or its own flush - do)
-        last = flush and b + 1 >= len(self._ep_batches)
-        touched, nxt = self._ep_touch(b), self._ep_next_touch(b)
-        score_next = (not self.touched_on) or nxt is not None
-        if not self._fresh:
-            self._enqueue_refresh(touched)
-        if eager:
-            self._enqueue_choose_train(ids, lab, B, plan, score_next, nxt)           # (records the two events itself)
-            self._enqueue_tail(ids, lab, B, agg, plan, True)
-            if last:
-                self.flush()
-            self.last_counts = self.cnt.view(-1)[:g.R * B].view(g.R, B)
-            return
-        if grs is None:
-            parts = (lambda: self._enqueue_choose_train(ids, lab, B, plan, score_next, nxt),
-                     lambda: (self._enqueue_tail(ids, lab, B, agg, plan, True), self.flush() if last else None))
-            grs = self._capture_graphs(list(parts), warm=[lambda: (self._enqueue_refresh(touched), parts[0](), parts[1]())])
-            self._ep_graphs[key] = grs
-            self._enqueue_refresh(touched)
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-        grs[0].replay()
-        ev[1].record()
-        if self._prof is not None:
-            self._prof.append(ev)
-        self.last_counts = self.cnt.view(-1)[:g.R * B].view(g.R, B)
-        grs[1].replay()
-        self._fresh = score_next
-
-    def epoch_run(self, n_steps: Optional[int] = None, sample=None, bump_counter: Optional[torch.Tensor] = None,
-                  flush: bool = True, prefetch: bool = False, first_step: int = 0):
-        """All batches of the staged epoch as ONE graph launch: the host latency between two graph launches (~8 us)
-        is paid once per epoch instead of once per batch.  ``sample(ids, labels)``, if given, is enqueued (and captured): it
-        fills the given id / label buffers on the device (pick + shuffle + labels), so a replay is a whole new epoch;
-        the plans of all batches follow (which also bumps ``bump_counter``, the sampler's epoch number).
-        flush=False: the last batch's deferred Adam update (everything but the label classifier) is left to whatever comes
-        next - the next epoch's first front launch applies it, any other public call flushes it first.
-        prefetch=True (needs ``sample``): the sampler and the plans of the NEXT epoch run on a parallel branch of this epoch's
-        graph, into the other buffer set; afterwards that set is the current one and ready (``take_prefetched``).  The first
-        such call - or one after the ready set was used up by other calls - samples its own epoch first.
-        A prepared set is DROPPED by whatever rewrites or replaces its buffers before a step has used it: ``stage_epoch`` with
-        another (n, batch_size, n_epochs), ``begin_epoch`` (its ids go into that set), a batch above max_batch anywhere (every
-        buffer is re-allocated).  The epoch numbers the dropped set had consumed are skipped - ``bump_counter`` is never moved
-        back - and the next epoch is sampled and planned anew.  Calls that leave the epoch buffers alone (``train_step`` within
-        max_batch, ``predict``, ``infer``, ``chosen``, ``flush``) leave the prepared set ready.
-        prefetch="stream": the same division of labour without a fork inside the graph: the sampler and plan launches of the next
-        epoch are enqueued - by the host, behind this epoch's graph launch - on a second stream, where they run beside this
-        epoch's kernels; the only cross-stream waits are two events per epoch (the other buffer set is free / is ready).
-        first_step > 0: the REST of an epoch that is staged and planned already and whose first batches have been run some other
-        way (batches first_step .. n_steps - 1): no sampler, no plans."""
-        self._theta_written()
-        nb = len(self._ep_batches)
-        n_steps = nb if n_steps is None else min(n_steps, nb)
-        n = self._ep_n * self._ep_k
-        batches = list(self._ep_batches)
-        if first_step > 0:
-            sample, prefetch = None, False
-        on_stream = prefetch == "stream" and sample is not None
-        prefetch = prefetch is True and sample is not None
-        cur = self._cur
-        primed = (prefetch or on_stream) and self._cur_ready
-        key = ("epoch", cur, self._ep_shape, n_steps, sample is not None, None if bump_counter is None else bump_counter.data_ptr(),
-               flush, prefetch, primed, on_stream, first_step)
-        main = torch.cuda.current_stream(self.dev)
-        if primed and getattr(self, "_ev_ready", None) is not None:
-            # the side stream has sampled and planned this set: wait here, in front of a capture too - its warm-up plans the
-            # set again and runs the steps over it
-            main.wait_event(self._ev_ready)
-            self._ev_ready = None
-        gr = self._ep_graphs.get(key)
-        if gr is None:
-            st = self._ep_sets[cur]
-            nxt = self._ep_sets[cur ^ 1]
-            def run():
-                if self._pipelines(batches[first_step:n_steps]):
-                    self._lastB = batches[n_steps - 1][1]
-                    self._enqueue_pipelined([(st["ids"][lo:lo + B], st["lab"][lo:lo + B], B, self._ep_plan(b, cur))
-                                             for b, (lo, B) in enumerate(batches) if first_step <= b < n_steps])
-                else:
-                    for b in range(first_step, n_steps):
-                        lo, B = batches[b]
-                        self.train_step(st["ids"][lo:lo + B], st["lab"][lo:lo + B], defer=True, plan=self._ep_plan(b, cur),
-                                        touched=self._ep_touch(b, cur), next_touched=self._ep_next_touch(b, cur))
-                if flush:
-                    self.flush()
-            def warm_run():                      # (the warm-up leaves the staged ids - and the epoch counter - as they are)
-                if first_step == 0:
-                    self.plan_staged(which=cur)
-                elif not self._fresh:
-                    self._enqueue_refresh(self._ep_touch(first_step, cur))
-                run()
-                if prefetch or on_stream:        # (the other set's plan slots and kernels get their first use outside a capture)
-                    self.plan_staged(which=cur ^ 1)
-            def sampled_run():
-                if not primed and first_step == 0:
-                    if sample is not None:
-                        sample(st["ids"][:n], st["lab"][:n])
-                    self.plan_staged(bump_counter, which=cur)
-                if prefetch:                     # fork: the next epoch's sampler + plans beside this epoch's steps
-                    main = torch.cuda.current_stream(self.dev)
-                    side = torch.cuda.Stream(self.dev)
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side):
-                        sample(nxt["ids"][:n], nxt["lab"][:n])
-                        self.plan_staged(bump_counter, which=cur ^ 1)
-                    run()
-                    main.wait_stream(side)
-                else:
-                    run()
-            gr = self._capture_graphs([sampled_run], warm=[warm_run])[0]
-            self._ep_graphs[key] = gr
-        self._lastB = batches[n_steps - 1][1]
-        # (whole-table engine: the graph was captured with the scores at hand - it holds no score launch of its own; a
-        #  touched-rows engine's graph scores its first batch's rows itself, behind its sampler and maps)
-        if first_step > 0:
-            if not self._fresh:                      # (the graph was captured with the scores at hand)
-                self._enqueue_refresh(self._ep_touch(first_step, cur))
-        elif not self.touched_on and not self._fresh:
-            self._enqueue_refresh()
-        gr.replay()
-        self._fresh = (not self.touched_on) or self._ep_next_touch(n_steps - 1, cur) is not None
-        if on_stream:
-            # the next epoch's sampler + plans, on the side stream: behind the graph launched BEFORE this one (the last reader of
-            # the other set), beside this one
-            if getattr(self, "_side", None) is None:
-                self._side, self._ev_free = torch.cuda.Stream(self.dev), None
-            nxt = self._ep_sets[cur ^ 1]
-            if self._ev_free is not None:
-                self._side.wait_event(self._ev_free)
-            with torch.cuda.stream(self._side):
-                sample(nxt["ids"][:n], nxt["lab"][:n])
-                self.plan_staged(bump_counter, which=cur ^ 1)
-                self._ev_ready = torch.cuda.Event()
-                self._ev_ready.record(self._side)
-            self._ev_free = torch.cuda.Event()
-            self._ev_free.record(main)               # (this epoch's graph: the last reader of the set it ran on)
-            self._cur, self._cur_ready = cur ^ 1, True
-        elif prefetch:
-            self._cur, self._cur_ready = cur ^ 1, True
-        else:
-            self._cur_ready = False
-        return n_steps
-
-    def read_batch_lists(self, b: int):
-        """The selection lists batch b of the staged epoch has in the workspace RIGHT NOW - what the last select launch on that
-        batch's plan slot wrote (the data part is shared by all batches: call it before another batch is selected) - copied to
-        the host: sets[r][i] for relation r, centre i.  Synchronises.  (bench.py's `verified`, tests.)"""
-        import numpy as np
-        g, lib = self.g, self.lib
-        B = self._ep_batches[b][1]
-        rows = g.R * B
-        torch.cuda.synchronize(self.dev)
-        off = lambda which: int(lib.pcg_choose_workspace_offset(g.desc_ref(), B, self.list_capacity, which))
-        slot = self._ep_plans[b * self._ep_stride:(b + 1) * self._ep_stride]
-        begin = slot[off(0):off(0) + 8 * (rows + 1)].view(torch.int64).cpu().numpy()
-        length = slot[off(1):off(1) + 4 * rows].view(torch.int32).cpu().numpy()
-        d0 = off(2) - self._plan_bytes(B)
-        lst = self.data[d0:d0 + 4 * max(int(begin[-1]), 1)].view(torch.int32).cpu().numpy()
-        sets = []
-        for r in range(g.R):
-            row_sets = []
-            for i in range(B):
-                row = r * B + i
-                seg = lst[begin[row]:begin[row] + length[row]]
-                row_sets.append(set(seg[seg >= 0].tolist()))
-            sets.append(row_sets)
-        return sets
+    # train_step_graph, begin_epoch / stage_epoch .. epoch_step, epoch_run, read_batch_lists: EpochCalls (epoch.py)
 
     def check(self):
         """Raise if any batch since the last check did not fit its selection list (the kernels then select nothing and
@@ -1063,8 +657,7 @@ class FusedPCGNN(WholeSetCalls):
         classifier's tiles included); via="slabs": per-tile gradient slabs summed in tile order (the data-parallel paths')."""
         B = ids.numel()
         self.flush()
-        if B > self.maxB:
-            self._alloc(B)
+        self._fit(B, flush=False)
         if via == "slabs":
             self._enqueue_grad_slabs(ids, labels, B)
             self.step_counter -= 1               # the dense kernel counted a step that is not taken
@@ -1089,8 +682,7 @@ class FusedPCGNN(WholeSetCalls):
         (PCALayer.forward, model.py:34-39; utils.py:305 calls it with train_flag=False)."""
         B = ids.numel()
         self.flush()
-        if B > self.maxB:
-            self._alloc(B)
+        self._fit(B, flush=False)
         plan = self._enqueue_plan_one(ids, labels, B, train_flag)
         keys = self._enqueue_scores(train_flag)
         agg, _ = self._enqueue_choose(ids, labels, B, keys, train_flag, plan, sort_in_kernel=False)
@@ -1140,8 +732,7 @@ class FusedPCGNN(WholeSetCalls):
             if tuple(d.shape) != (B, 2) or d.device != self.dev:
                 raise ValueError(f"{what}: a [{B}, 2] tensor on {self.dev} expected, got {tuple(d.shape)} on {d.device}")
             seeds.append(d.detach().to(torch.float32).contiguous())
-        agg = self.agg.view(-1)[:g.R * B * g.feat_dim].view(g.R, B, g.feat_dim)
-        cnt = self.cnt.view(-1)[:g.R * B]
+        agg, cnt = self._agg_of(B), self._cnt_of(B)
         dense_out = None if out is None else _lib.DenseOut(_p(out[0]), _p(out[1]), None, None)
         _lib.check(self.lib.pcg_dense_vjp(
             g.desc_ref(), self._st, self._batch(live["ids"], None, B, live["plan"], cnt), _p(agg), agg.stride(1), self._sel,
