@@ -698,6 +698,41 @@ int64_t pcg_baseline_workspace_bytes(const pcg_graph_desc *g, const pcg_baseline
 int pcg_baseline_infer(const pcg_graph_desc *g, const pcg_baseline_model *m, const int32_t *ids, int32_t n, int32_t chunk_rows,
                        void *workspace, int64_t workspace_bytes, float *out_logits, float *out_emb, float *out_agg,
                        uint32_t *status, void *stream);
+/* Training steps of the GraphSAGE / GCN baselines (BaselineEngine.train_step / train_epoch / loss_and_grad; src/graphsage.py:37-39,
+ * 176-178 with torch.optim.Adam, src/model_handler.py:124, 149-153): ids [n] with labels [n] (int32, 0 / 1) in batches of
+ * batch_rows, the last one shorter; batch i is step first_step + i.  Per batch, on the stream, with no host synchronisation:
+ *   the aggregation of pcg_baseline_infer -> baseline_train_dense_kernel -> baseline_wgrad_adam_kernel.
+ *   forward: pcg_baseline_infer's own tile code - the logits are bit for bit what it returns for those ids;
+ *   loss_i = two-class cross entropy of row i;  out_loss[batch] = (sum of loss_i: a tile's 16 rows in row order, the tiles in
+ *            tile order) / B - nn.CrossEntropyLoss()'s mean;
+ *   dlogits = (softmax - onehot) / B;  dpre = (W_cls^T dlogits) where h > 0 (h <= 0: 0; a NaN h lets it through, as torch's ReLU);
+ *   dW_enc[e][k] = sum_t dpre[t][e] z[t][k];  dW_cls[c][e] = sum_t dlogits[t][c] h[t][e]: float32 MFMA sums over the batch in a
+ *            fixed order (no float atomics: bitwise the same run to run); batches of more than 1024 rows are shared by up to four
+ *            workgroups per 16 x 16 tile (ceil(B / 1024), at most 4), their partial tiles added in part order.
+ *   apply != 0: the thread that owns a parameter applies torch.optim.Adam's update (coupled weight decay, step number
+ *            first_step + batch) to W_enc / W_cls IN PLACE - through m->W_enc / m->W_cls, which must be writable - and to
+ *            m_enc / v_enc [emb][K], m_cls / v_cls [2][emb]; the next batch's dense launch is the first reader.
+ *   apply == 0: nothing is updated; grad_out [2 * emb + emb * K] = [dW_cls | dW_enc] of the one batch (n <= batch_rows).
+ *            (apply != 0 with grad_out: the last batch's gradient.)
+ * A centre without neighbours (no add_self) makes its aggregate, the loss and every gradient NaN, as autograd does.
+ * workspace: pcg_baseline_train_workspace_bytes(g, m, batch_rows) bytes, 16-byte aligned; a function of batch_rows,
+ * g->feat_dim, g->feat_stride and the model's shape only.  Its contents are irrelevant on entry.
+ * Checks, before any launch: pcg_baseline_infer's on g, m, ids, workspace, status; NULL opt / labels / out_loss, n < 0,
+ * batch_rows < 1; apply != 0 with a NULL m_enc / v_enc / m_cls / v_cls or first_step < 1; apply == 0 with a NULL grad_out or
+ * n > batch_rows; workspace_bytes too small: PCG_E_ARG.  Shapes: PCG_E_UNSUPPORTED exactly where pcg_baseline_infer returns it.
+ * n == 0: PCG_OK, nothing is enqueued.  An id outside [0, n_nodes) is clamped for the read and sets PCG_ST_LIST_ID_RANGE; a label
+ * outside {0, 1} sets PCG_ST_EVAL_INPUT and its row contributes nothing to the loss or the gradients (it still counts in B). */
+typedef struct pcg_baseline_opt {
+    float *m_enc, *v_enc;   /* [emb][K] */
+    float *m_cls, *v_cls;   /* [2][emb] */
+    int64_t first_step;     /* the 1-based number of the first batch's step; by value: the caller owns the count */
+    int32_t apply, _pad;
+    pcg_adam_hyper hyper;
+} pcg_baseline_opt;
+int64_t pcg_baseline_train_workspace_bytes(const pcg_graph_desc *g, const pcg_baseline_model *m, int32_t batch_rows);
+int pcg_baseline_train(const pcg_graph_desc *g, const pcg_baseline_model *m, const pcg_baseline_opt *opt, const int32_t *ids,
+                       const int32_t *labels, int32_t n, int32_t batch_rows, void *workspace, int64_t workspace_bytes,
+                       float *out_loss /* [ceil(n / batch_rows)] */, float *grad_out, uint32_t *status, void *stream);
 /* The k most similar rows of bank [M][emb] for every row of Q [n][emb] (both float32, row-major, 16-byte aligned), without an
  * [n][M] matrix: exact-f32 MFMA scores and a running top-k (FusedPCGNN.nearest, ops.topk_similar).
  * metric - the score is always MAXIMISED: 0 dot q.c;  1 cosine q.c / (|q| |c|), 0 when either norm is 0;

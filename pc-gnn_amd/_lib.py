@@ -85,7 +85,14 @@ class BaselineModel(C.Structure):
                 ("W_enc", _P), ("W_cls", _P)]
 
 
-_BM = C.POINTER(BaselineModel)
+class BaselineOpt(C.Structure):
+    """pcg_baseline_opt: the Adam state, the first batch's step number and the hyper-parameters of pcg_baseline_train (apply = 0:
+    gradients only)"""
+    _fields_ = [("m_enc", _P), ("v_enc", _P), ("m_cls", _P), ("v_cls", _P), ("first_step", _I64), ("apply", _I32), ("_pad", _I32),
+                ("hyper", AdamHyper)]
+
+
+_BM, _BO = C.POINTER(BaselineModel), C.POINTER(BaselineOpt)
 
 # name -> (restype, argtypes); must list every symbol include/pcgnn.h declares
 PROTOTYPES = {
@@ -155,6 +162,8 @@ PROTOTYPES = {
     "pcg_embed_new": (C.c_int, [_G, _G, _P, _I32, _P, _I32, _I32, _P, _I32, C.POINTER(_F64), _P, _I64, _P, _P, _P, _P, _P, _P]),
     "pcg_baseline_workspace_bytes": (_I64, [_G, _BM, _I32]),
     "pcg_baseline_infer": (C.c_int, [_G, _BM, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P]),
+    "pcg_baseline_train_workspace_bytes": (_I64, [_G, _BM, _I32]),
+    "pcg_baseline_train": (C.c_int, [_G, _BM, _BO, _P, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P]),
     "pcg_topk_similar_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "pcg_topk_similar": (C.c_int, [_P, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "pcg_debug_set_topk_slices": (None, [_I32]),

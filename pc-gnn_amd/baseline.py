@@ -1,15 +1,24 @@
-"""Whole-set inference for the GraphSAGE / GCN baselines (``graphsage.GraphSage`` / ``graphsage.GCN``): ``BaselineEngine``.
+"""The GraphSAGE / GCN baselines (``graphsage.GraphSage`` / ``graphsage.GCN``) on the device: ``BaselineEngine``.
 
-One call over any node set (or the whole graph) instead of the per-batch ``to_prob`` loop: pcg_baseline_infer (csrc/baseline.hip)
-reads every centre's CSR row in place - no plan, no selection, no per-edge list - and runs the encoder and the head on exact
-float32 MFMA tiles.  ``infer`` returns the logits, ``embed`` the encoder's output (and the aggregates); ``evaluate``,
-``evaluate_ranking`` and ``alerts`` are ``wholeset.EvalCalls``', the methods a FusedPCGNN has.  The engine holds no copy of the
-parameters: every call passes the live ``enc.weight`` / ``model.weight``, so an optimizer step between two calls is seen.
-Out of scope: training (torch autograd over the per-batch aggregator), the random fan-out, query batches, ``nearest``, attribution.
+Whole-set inference - one call over any node set (or the whole graph) instead of the per-batch ``to_prob`` loop: pcg_baseline_infer
+(csrc/baseline.hip) reads every centre's CSR row in place - no plan, no selection, no per-edge list - and runs the encoder and
+the head on exact float32 MFMA tiles.  ``infer`` returns the logits, ``embed`` the encoder's output (and the aggregates);
+``evaluate``, ``evaluate_ranking`` and ``alerts`` are ``wholeset.EvalCalls``', the methods a FusedPCGNN has.
+
+Training - pcg_baseline_train (csrc/baseline_train.hip): the same aggregation and forward tile, the two-class cross entropy, the
+backward to ``enc.weight`` / ``weight`` as MFMA GEMMs over the batch and torch.optim.Adam's update, per batch in three launches
+with no host synchronisation.  ``train_step`` / ``train_epoch`` run the engine's own Adam (``configure_optimizer``) in place on the
+live parameters; ``loss_and_grad`` / ``backward`` stop at the gradients, so that any ``torch.optim`` optimizer or clipping can
+follow.  Nothing here reads the device: ``check()`` reads the status word once and raises on a bad id or label.
+
+The engine holds no copy of the parameters: every call passes the live ``enc.weight`` / ``model.weight``, so a step between two
+calls - the engine's or an optimizer's - is seen.
+Out of scope: the random fan-out, query batches, ``nearest``, attribution, custom losses, gradients to the feature table.
 """
 import ctypes as C
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -36,7 +45,8 @@ def model_shape(model) -> dict:
 
 class BaselineEngine(EvalCalls):
     """The whole-set calls of a GraphSAGE / GCN baseline: ``infer``, ``embed`` and, through ``wholeset.EvalCalls``, ``evaluate``,
-    ``evaluate_ranking`` and ``alerts`` (resident ids only).  Build it with ``from_model``."""
+    ``evaluate_ranking`` and ``alerts`` (resident ids only), and its training calls: ``train_step``, ``train_epoch``,
+    ``loss_and_grad``, ``backward``.  Build it with ``from_model``."""
 
     def __init__(self, model, graph, workspace_bytes: int = 1 << 30):
         self.model = model
@@ -46,7 +56,9 @@ class BaselineEngine(EvalCalls):
         _lib.load()
         self.E = self.shape["emb"]
         self.workspace_bytes = int(workspace_bytes)          # the default chunk keeps the workspace within this
-        self._inf = {}                                       # status, ws, all_ids, eval_labels: grown on demand
+        self._inf = {}                                       # status, ws, train_ws, all_ids, eval_labels: grown on demand
+        self._hyper = None                                   # configure_optimizer
+        self._opt = None                                     # the engine's Adam state, made by the first train_step
         K = (2 if self.shape["concat_self"] else 1) * graph.feat_dim
         if tuple(model.enc.weight.shape) != (self.E, K) or tuple(model.weight.shape) != (2, self.E):
             raise ValueError(f"BaselineEngine: encoder weight {tuple(model.enc.weight.shape)} / head weight {tuple(model.weight.shape)}, "
@@ -108,11 +120,18 @@ class BaselineEngine(EvalCalls):
                                                _p(logits), _p(emb), _p(agg), _p(inf["status"]), ops._stream(self.dev)),
                    "pcg_baseline_infer")
         del keep
-        st = int(inf["status"].item())
+        self.check()
+
+    def check(self):
+        """Reads the status word once (synchronises) and raises if a call since the last look met an id outside the feature
+        table - in ids or in the graph's rows - or, training, a label outside {0, 1}.  The word is cleared for the next call."""
+        status = self._inf.get("status")
+        st = 0 if status is None else int(status.item())
         if st:
-            inf["status"].zero_()
-            raise _lib.PcgnnLibraryError("an id outside the feature table (in ids or in the graph's rows)"
-                                         if st & _lib.PCG_ST_LIST_ID_RANGE else f"device status {st}")
+            status.zero_()
+            what = [msg for bit, msg in ((_lib.PCG_ST_LIST_ID_RANGE, "an id outside the feature table (in ids or in the graph's rows)"),
+                                         (_lib.PCG_ST_EVAL_INPUT, "a label outside {0, 1}")) if st & bit]
+            raise _lib.PcgnnLibraryError("; ".join(what) if what else f"device status {st}")
 
     def infer(self, ids=None, chunk: Optional[int] = None) -> torch.Tensor:
         """The logits [n, 2] of a whole node set in one call: ``model.forward`` without the batches.  ids: node ids (any order,
@@ -144,3 +163,137 @@ class BaselineEngine(EvalCalls):
         if query is not None:
             raise ValueError("alerts: query batches are not supported for the GraphSAGE / GCN baselines")
         return super().alerts(ids, k=k, chunk=chunk, labels=labels)
+
+
+    # ---- training (pcg_baseline_train) ----------------------------------------------------------------------------------------
+    def configure_optimizer(self, lr: float, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8):
+        """The hyper-parameters of the engine's own Adam (torch.optim.Adam's, coupled weight decay), what ``train_step`` /
+        ``train_epoch`` apply.  The state (moments, step count) is created on first use and kept across calls of this."""
+        self._hyper = _lib.AdamHyper(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay))
+
+    def _adam(self) -> dict:
+        """the engine's Adam state: m / v of both matrices (zeros on first use) and the number of steps taken"""
+        if self._hyper is None:
+            raise _lib.PcgnnLibraryError("BaselineEngine: configure_optimizer(lr, weight_decay) before the first train_step")
+        if self._opt is None:
+            w_enc, w_cls = self.model.enc.weight, self.model.weight
+            self._opt = dict(step=0, m_enc=torch.zeros_like(w_enc.data), v_enc=torch.zeros_like(w_enc.data),
+                             m_cls=torch.zeros_like(w_cls.data), v_cls=torch.zeros_like(w_cls.data))
+        return self._opt
+
+    def reset_optimizer(self):
+        """zero moments and step count: the next ``train_step`` is step 1 (the hyper-parameters stay)"""
+        self._opt = None
+
+    def optimizer_state(self) -> dict:
+        """a copy of the engine's Adam state: ``step`` and the tensors ``m_enc``, ``v_enc`` [E, K], ``m_cls``, ``v_cls`` [2, E]"""
+        o = self._adam()
+        return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()}
+
+    def load_optimizer_state(self, state: dict):
+        """``optimizer_state()``'s dict back in (shapes checked)"""
+        o = self._adam()
+        for k in ("m_enc", "v_enc", "m_cls", "v_cls"):
+            if tuple(state[k].shape) != tuple(o[k].shape):
+                raise ValueError(f"load_optimizer_state: {k} {tuple(state[k].shape)}, expected {tuple(o[k].shape)}")
+        for k in ("m_enc", "v_enc", "m_cls", "v_cls"):
+            o[k].copy_(state[k])
+        o["step"] = int(state["step"])
+
+    def _train_args(self, ids, labels, what: str):
+        """ids and their labels as int32 device tensors.  Host sequences are range-checked here; device tensors are not read -
+        the kernels clamp what they index and report through the status word (``check``)."""
+        if torch.is_tensor(ids):
+            ids_dev = ops._i32(ids, self.dev).view(-1)
+        else:
+            host = np.asarray(ids).reshape(-1).astype(np.int64)
+            if host.size and (host.min() < 0 or host.max() >= self.g.n_nodes):
+                raise ValueError(f"{what}: ids outside 0 .. {self.g.n_nodes - 1}")
+            ids_dev = torch.from_numpy(host.astype(np.int32)).to(self.dev)
+        if torch.is_tensor(labels):
+            lab_dev = ops._i32(labels, self.dev).view(-1)
+        else:
+            host = np.asarray(labels).reshape(-1).astype(np.int64)
+            if host.size and (host.min() < 0 or host.max() > 1):
+                raise ValueError(f"{what}: labels outside {{0, 1}}")
+            lab_dev = torch.from_numpy(host.astype(np.int32)).to(self.dev)
+        if lab_dev.numel() != ids_dev.numel():
+            raise ValueError(f"{what}: {lab_dev.numel()} labels for {ids_dev.numel()} ids")
+        return ids_dev, lab_dev, int(ids_dev.numel())
+
+    def train_workspace_bytes_of(self, batch_rows: int) -> int:
+        m, _ = self._model_desc()
+        nbytes = int(_lib.load().pcg_baseline_train_workspace_bytes(self.g.desc_ref(), C.byref(m), int(batch_rows)))
+        if nbytes < 0:
+            raise _lib.PcgnnLibraryError(f"pcg_baseline_train_workspace_bytes rejected batch {batch_rows} ({nbytes})")
+        return nbytes
+
+    def _train_call(self, ids_dev, lab_dev, n: int, batch_rows: int, apply: bool, grad_out):
+        """pcg_baseline_train over n > 0 ids -> the batches' losses [ceil(n / batch_rows)]; nothing is read back"""
+        inf = self._inf
+        nbytes = self.train_workspace_bytes_of(batch_rows)
+        if inf.get("train_ws") is None or inf["train_ws"].numel() < nbytes:
+            inf["train_ws"] = None
+            inf["train_ws"] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        if inf.get("status") is None:
+            inf["status"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        n_batches = (n + batch_rows - 1) // batch_rows
+        losses = torch.empty(n_batches, dtype=torch.float32, device=self.dev)
+        m, keep = self._model_desc()
+        if apply:
+            o = self._adam()
+            opt = _lib.BaselineOpt(m_enc=o["m_enc"].data_ptr(), v_enc=o["v_enc"].data_ptr(), m_cls=o["m_cls"].data_ptr(),
+                                   v_cls=o["v_cls"].data_ptr(), first_step=o["step"] + 1, apply=1, hyper=self._hyper)
+        else:
+            opt = _lib.BaselineOpt(apply=0)
+        _lib.check(_lib.load().pcg_baseline_train(self.g.desc_ref(), C.byref(m), C.byref(opt), _p(ids_dev), _p(lab_dev), n, batch_rows,
+                                               _p(inf["train_ws"]), inf["train_ws"].numel(), _p(losses), _p(grad_out),
+                                               _p(inf["status"]), ops._stream(self.dev)), "pcg_baseline_train")
+        del keep
+        if apply:
+            o["step"] += n_batches
+        return losses
+
+    def loss_and_grad(self, ids, labels):
+        """(loss, d_enc [E, K], d_cls [2, E]) of one batch: ``model.loss(ids, labels)`` and its gradients to ``enc.weight`` /
+        ``weight``, device tensors; nothing is updated.  ids, labels: device tensors, numpy arrays or lists (duplicate ids count
+        twice)."""
+        ids_dev, lab_dev, n = self._train_args(ids, labels, "loss_and_grad")
+        if n == 0:
+            raise ValueError("loss_and_grad: an empty batch has no mean loss")
+        E = self.E
+        grad = torch.empty(2 * E + self.model.enc.weight.numel(), dtype=torch.float32, device=self.dev)
+        with torch.no_grad():
+            loss = self._train_call(ids_dev, lab_dev, n, n, False, grad)[0]
+        return loss, grad[2 * E:].view(tuple(self.model.enc.weight.shape)), grad[:2 * E].view(2, E)
+
+    def backward(self, ids, labels, accumulate: bool = False):
+        """``loss_and_grad`` with the gradients put into ``enc.weight.grad`` / ``weight.grad`` (added to what is there when
+        accumulate) -> the loss: any ``torch.optim`` optimizer, clipping or accumulation can follow."""
+        loss, d_enc, d_cls = self.loss_and_grad(ids, labels)
+        for p, d in ((self.model.enc.weight, d_enc), (self.model.weight, d_cls)):
+            if accumulate and p.grad is not None:
+                p.grad.add_(d)
+            else:
+                p.grad = d.clone()
+        return loss
+
+    def train_step(self, ids, labels):
+        """One training step on the batch: forward, loss, backward and the engine's own Adam (``configure_optimizer``) on the
+        live parameters, in place -> the loss, a device scalar that nothing reads."""
+        ids_dev, lab_dev, n = self._train_args(ids, labels, "train_step")
+        if n == 0:
+            raise ValueError("train_step: an empty batch")
+        with torch.no_grad():
+            return self._train_call(ids_dev, lab_dev, n, n, True, None)[0]
+
+    def train_epoch(self, ids, labels, batch_size: int):
+        """``train_step`` over ids [b0, b0 + batch_size) for b0 = 0, batch_size, ... - the batches in the given order, the last
+        one partial - in ONE call -> their losses [n_batches] (device).  Bit for bit the same steps one by one."""
+        ids_dev, lab_dev, n = self._train_args(ids, labels, "train_epoch")
+        if int(batch_size) < 1:
+            raise ValueError(f"train_epoch: batch_size {batch_size}")
+        if n == 0:
+            return torch.empty(0, dtype=torch.float32, device=self.dev)
+        with torch.no_grad():
+            return self._train_call(ids_dev, lab_dev, n, min(int(batch_size), n), True, None)

@@ -5,7 +5,7 @@ Same class names and constructor arguments as the reference: ``MeanAggregator`` 
 (:234-275), ``GCN`` (:154-178).  The aggregation is the same kernel as PC-GNN's with the
 choose step switched off (threshold 1 => keep every neighbour), ``add_self`` for the GCN-style
 self union (:78-79, :214) and the ``sqrt(count)`` normaliser (:224-226); the small dense tail
-(``relu(W . x^T)``, classifier, loss) is torch with autograd.
+(``relu(W . x^T)``, classifier, loss) is torch with autograd - ``forward`` / ``loss`` below, the per-batch path.
 
 ``MeanAggregator.forward(..., num_sample=k)`` (random fan-out, :70-74) draws the sample on the
 host with Python's ``random`` exactly like the reference (same draws under the same seed: checked
@@ -14,6 +14,9 @@ against a fixture) and aggregates the explicit lists with ``pcg_segment_mean``.
 Evaluation of a whole node set in one call - ``model.infer`` / ``embed`` / ``evaluate`` / ``evaluate_ranking`` / ``alerts``,
 and ``utils.test`` with ``model.eval_by_infer = True`` - goes through ``baseline.BaselineEngine`` (pcg_baseline_infer: the CSR
 rows read in place, the encoder and the head on MFMA tiles); the default stays the per-batch ``to_prob`` loop below.
+Training on the device goes through the same engine (pcg_baseline_train): ``model.train_step`` / ``train_epoch`` run forward,
+loss, backward and Adam per batch with no host round trip, ``loss_and_grad`` / ``backward`` stop at the gradients
+(``ModelHandler``: ``baseline_fused_train``); ``model.loss(...).backward()`` with a torch optimizer stays the default.
 
 One difference on purpose: ``to_prob`` accepts (and ignores) the ``labels`` / ``train_flag``
 arguments ``utils.test`` passes (utils.py:305), which the reference's ``GCN.to_prob(self, nodes)``
@@ -213,6 +216,38 @@ class _Head(nn.Module):
 
     def alerts(self, ids=None, k=100, chunk=None, labels=None, query=None):
         return self.engine().alerts(ids, k=k, chunk=chunk, labels=labels, query=query)
+
+    # -- training on the device (baseline.BaselineEngine: pcg_baseline_train) ----------------------------------------------------
+    def configure_optimizer(self, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8):
+        return self.engine().configure_optimizer(lr, weight_decay, betas=betas, eps=eps)
+
+    def loss_and_grad(self, ids, labels):
+        """(loss, d enc.weight, d weight) of one batch, nothing updated (``BaselineEngine.loss_and_grad``)"""
+        return self.engine().loss_and_grad(ids, labels)
+
+    def backward(self, ids, labels, accumulate=False):
+        """the batch's gradients into ``enc.weight.grad`` / ``weight.grad`` -> the loss (``BaselineEngine.backward``)"""
+        return self.engine().backward(ids, labels, accumulate=accumulate)
+
+    def train_step(self, ids, labels):
+        """one step of the engine's own Adam on the batch -> the loss, a device scalar (``BaselineEngine.train_step``)"""
+        return self.engine().train_step(ids, labels)
+
+    def train_epoch(self, ids, labels, batch_size):
+        """``train_step`` over the batches of ids in one call -> their losses (``BaselineEngine.train_epoch``)"""
+        return self.engine().train_epoch(ids, labels, batch_size)
+
+    def check(self):
+        return self.engine().check()
+
+    def optimizer_state(self):
+        return self.engine().optimizer_state()
+
+    def load_optimizer_state(self, state):
+        return self.engine().load_optimizer_state(state)
+
+    def reset_optimizer(self):
+        return self.engine().reset_optimizer()
 
 
 class GraphSage(_Head):

@@ -185,7 +185,9 @@ class ModelHandler(object):
     (generate_exp_config.ipynb:50-66): data_name, model (PCGNN | SAGE | GCN), seed, train_ratio, test_ratio, emb_size, rho,
     alpha, lr, weight_decay, batch_size, epochs, valid_epochs, patience (+ exp_num, kept for bookkeeping; + the optional
     ``eval_on_device``: validation / test metrics from the counts formed on the device, ``utils.test(on_device=True)``; + the
-    optional ``baseline_whole_set``: SAGE / GCN are evaluated by one whole-set call, ``baseline.BaselineEngine``, default false).
+    optional ``baseline_whole_set``: SAGE / GCN are evaluated by one whole-set call, ``baseline.BaselineEngine``, default false;
+    + the optional ``baseline_fused_train``: SAGE / GCN train through ``BaselineEngine.train_epoch`` - one call per epoch, the
+    engine's own Adam on the device - instead of the autograd loop, default false).
 
     The reference reads its datasets from files that exist nowhere offline (``load_data``, src/utils.py:66-207), so the
     graph is handed in: ``dataset = (homo, relation_list, feat_data, labels)`` - exactly what ``load_data`` returns
@@ -277,6 +279,9 @@ class ModelHandler(object):
         # (optional key: validation / test through the whole-set call, baseline.BaselineEngine, instead of the per-batch loop)
         model.eval_by_infer = bool(getattr(args, "baseline_whole_set", False))
         opt = torch.optim.Adam(filter(lambda p: p.requires_grad, model.parameters()), lr=args.lr, weight_decay=args.weight_decay)
+        # (optional key: training through BaselineEngine.train_epoch - the same Adam, applied on the device)
+        if bool(getattr(args, "baseline_fused_train", False)):
+            model.configure_optimizer(args.lr, args.weight_decay)
         return model, None, opt
 
     def train(self):
@@ -289,6 +294,7 @@ class ModelHandler(object):
         auc_best, f1_mac_best, epoch_best = 1e-10, 1e-10, 0                                              # :125
         saved = False
         on_device = bool(getattr(args, "eval_on_device", False))        # (optional key: metrics from device-side counts, utils.test)
+        fused_baseline = engine is None and bool(getattr(args, "baseline_fused_train", False))
         if engine is not None:
             sampler = PickSampler(idx_train, y_train, ds["homo_deg"][np.asarray(idx_train)], dev, seed=args.seed)
             pick_size = 2 * len(ds["train_pos"])                                                        # :130
@@ -313,6 +319,12 @@ class ModelHandler(object):
                 group_left = k
             if engine is not None:
                 group_left -= 1
+            elif fused_baseline:
+                # the same shuffle; the epoch's list in one call: every batch's forward, backward and Adam on the device
+                sampled = list(idx_train)
+                random.shuffle(sampled)
+                epoch_ids = torch.as_tensor(np.asarray(sampled, dtype=np.int64), device=dev)
+                model.train_epoch(epoch_ids, labels_dev[epoch_ids], args.batch_size)
             else:
                 sampled = list(idx_train)                                                                # :132-133
                 random.shuffle(sampled)
@@ -341,6 +353,8 @@ class ModelHandler(object):
                 break
         if engine is not None:
             engine.check()
+        if fused_baseline:
+            model.check()
         print("Restore model from epoch {}".format(epoch_best))                                          # :175-177
         if saved:
             if engine is not None:
