@@ -221,29 +221,13 @@ static int launch_attr_dense(const DenseArgs &a, const AttrArgs &x, int B, hipSt
     const bool wlds = infer_wlds(F, E, R);            // (the forward's own choice: the logits are pcg_infer_set's)
     const size_t smem = attr_smem_bytes(F, E, R, wlds);
     typedef void (*kern_t)(const DenseArgs, const AttrArgs, int);
-    kern_t kern;
-    bool persist = true;
-    if (R == 3 && F == 32 && E == 64 && wlds) kern = attr_dense_kernel<true, 32, 64, 3, true>;
-    else if (R == 3 && F == 25 && E == 64 && wlds) kern = attr_dense_kernel<true, 25, 64, 3, true>;
-    else if (R == 3 && F == 32 && E == 128 && !wlds) kern = attr_dense_kernel<false, 32, 128, 3, true>;
-    else if (R == 3 && F == 25 && E == 128 && !wlds) kern = attr_dense_kernel<false, 25, 128, 3, true>;
-    else {
-        kern = wlds ? attr_dense_kernel<true, 0, 0, 0, false> : attr_dense_kernel<false, 0, 0, 0, false>;
-        persist = false;
-    }
-    static kern_t attr_done[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool seen = false;
-    for (kern_t k : attr_done) seen = seen || k == kern;
-    if (!seen) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-            hipSuccess)
-            return PCG_E_LAUNCH;
-        for (kern_t &k : attr_done)
-            if (!k) {
-                k = kern;
-                break;
-            }
-    }
+    bool persist = false;
+    const kern_t kern = dense_dispatch(F, E, R, wlds, [&persist](auto s) -> kern_t {
+        using S = decltype(s);
+        persist = S::F != 0;
+        return attr_dense_kernel<S::wlds, S::F, S::E, S::R, S::F != 0>;
+    });
+    if (allow_dynamic_lds(kern, 160 * 1024) != PCG_OK) return PCG_E_LAUNCH;
     const int n_tiles = (B + TB - 1) / TB;
     const int blocks = persist ? pcg_infer_blocks(B) : n_tiles;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(DENSE_THREADS), smem, st, a, x, n_tiles);

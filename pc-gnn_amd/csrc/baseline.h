@@ -373,18 +373,6 @@ __device__ __forceinline__ void baseline_tile_forward(const BaselineDense &a, co
     }
 }
 
-static int baseline_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cus[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-        cus[dev] = n;
-    }
-    return cus[dev];
-}
-
 // the call's workspace: agg [chunk][feat_stride] | queue [chunk] | counter.  Nothing in it depends on degrees or edge counts.
 struct BaselineCarve {
     int64_t agg, queue, counter, total;
@@ -440,7 +428,7 @@ static inline void baseline_fill(const pcg_graph_desc *g, const pcg_baseline_mod
 // a chunk's aggregation: counter = 0 -> the rows of up to BL_ROW_MAX neighbours -> the queue of the longer ones
 static int launch_baseline_agg(const BaselineAgg &a, hipStream_t st) {
     const bool two = a.feat_stride > 256;                // float4 chunks per lane: 1 covers rows of up to 256 floats
-    const int cus = baseline_cus();
+    const int cus = device_cus(256);
     if (hipMemsetAsync(a.counter, 0, sizeof(uint32_t), st) != hipSuccess) return PCG_E_LAUNCH;
     const int64_t row_blocks = ((int64_t)a.B + 3) / 4, row_room = (int64_t)cus * 8;
     const dim3 rows_grid((unsigned)(row_blocks < row_room ? row_blocks : row_room));
@@ -459,7 +447,7 @@ static int launch_baseline_agg(const BaselineAgg &a, hipStream_t st) {
 static inline unsigned baseline_dense_grid(int n_tiles, size_t smem) {
     int per_cu = (int)((size_t)160 * 1024 / smem);
     per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
-    const int64_t room = (int64_t)baseline_cus() * per_cu;
+    const int64_t room = (int64_t)device_cus(256) * per_cu;
     return (unsigned)(n_tiles < room ? n_tiles : room);
 }
 

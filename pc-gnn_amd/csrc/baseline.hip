@@ -39,16 +39,7 @@ __global__ void __launch_bounds__(BL_DENSE_THREADS) baseline_dense_kernel(const 
 
 template <bool WLDS>
 static int launch_baseline_dense(const BaselineDense &a, size_t smem, hipStream_t st) {
-    static bool attr_done[64] = {false};                      // per device: the attribute belongs to a device's copy of the kernel
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return PCG_E_LAUNCH;
-    const bool known = dev >= 0 && dev < 64;
-    if (!known || !attr_done[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(baseline_dense_kernel<WLDS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess)
-            return PCG_E_LAUNCH;
-        if (known) attr_done[dev] = true;
-    }
+    if (allow_dynamic_lds(baseline_dense_kernel<WLDS>, 160 * 1024) != PCG_OK) return PCG_E_LAUNCH;
     const int n_tiles = (int)(((int64_t)a.B + TB - 1) / TB);
     hipLaunchKernelGGL(baseline_dense_kernel<WLDS>, dim3(baseline_dense_grid(n_tiles, smem)), dim3(BL_DENSE_THREADS), smem, st, a, n_tiles);
     PCG_LAUNCH_CHECK();

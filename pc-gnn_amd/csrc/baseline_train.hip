@@ -266,16 +266,7 @@ static int baseline_train_carve(const pcg_graph_desc *g, const pcg_baseline_mode
 
 template <bool WLDS>
 static int launch_baseline_train_dense(const BaselineTrainDense &a, size_t smem, hipStream_t st) {
-    static bool attr_done[64] = {false};                      // per device: the attribute belongs to a device's copy of the kernel
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return PCG_E_LAUNCH;
-    const bool known = dev >= 0 && dev < 64;
-    if (!known || !attr_done[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(baseline_train_dense_kernel<WLDS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return PCG_E_LAUNCH;
-        if (known) attr_done[dev] = true;
-    }
+    if (allow_dynamic_lds(baseline_train_dense_kernel<WLDS>, 160 * 1024) != PCG_OK) return PCG_E_LAUNCH;
     const int n_tiles = (int)(((int64_t)a.d.B + TB - 1) / TB);
     hipLaunchKernelGGL(baseline_train_dense_kernel<WLDS>, dim3(baseline_dense_grid(n_tiles, smem)), dim3(BL_DENSE_THREADS), smem, st, a,
                        n_tiles);

@@ -2,6 +2,7 @@
 // dense.hip (dense_step_kernel) and select.hip (dense_select_kernel: the tiles of batch t beside the selection of batch t + 1).
 #pragma once
 #include "choose.h"
+#include "launch.h"
 #include "wgrad.h"
 
 namespace pcg {
@@ -723,6 +724,24 @@ static inline bool dense_wlds(int F, int E, int R) {
     const int ntile_e = E / 16, kparts = ntile_e <= DENSE_WAVES ? DENSE_WAVES / ntile_e : 1;
     // the K-split partial tiles of `combined` live where the W_intra copies were
     return dense_smem_bytes(F, E, R, true) <= 160 * 1024 && DENSE_THREADS % (E / 4) == 0 && (size_t)kparts * TB * E <= (size_t)R * K1p * (E + 4);
+}
+
+// The instantiated shapes of dense_tile_body's kernels, listed HERE and nowhere else: YelpChi (F 32) and Amazon (F 25) at emb 64
+// (weights in LDS) and emb 128 (weights streamed), three relations; anything else gets the run-time shape <wlds, 0, 0, 0>.
+// wlds is the launcher's own rule (dense_wlds; infer_wlds for the forward-only launches); pick is a generic lambda that turns the
+// shape's tag into the launcher's kernel pointer, with whatever further template arguments that kernel has.
+template <bool WLDS, int F_, int E_, int R_>
+struct DenseShape {
+    static constexpr bool wlds = WLDS;
+    static constexpr int F = F_, E = E_, R = R_;
+};
+template <class Pick>
+static inline auto dense_dispatch(int F, int E, int R, bool wlds, Pick pick) -> decltype(pick(DenseShape<true, 0, 0, 0>())) {
+    if (R == 3 && F == 32 && E == 64 && wlds) return pick(DenseShape<true, 32, 64, 3>());
+    if (R == 3 && F == 25 && E == 64 && wlds) return pick(DenseShape<true, 25, 64, 3>());
+    if (R == 3 && F == 32 && E == 128 && !wlds) return pick(DenseShape<false, 32, 128, 3>());
+    if (R == 3 && F == 25 && E == 128 && !wlds) return pick(DenseShape<false, 25, 128, 3>());
+    return wlds ? pick(DenseShape<true, 0, 0, 0>()) : pick(DenseShape<false, 0, 0, 0>());
 }
 
 struct DenseExtra {          // the optional parts of a launch

@@ -199,27 +199,12 @@ static int launch_dense(const pcg_graph_desc *g, const float *theta, int32_t emb
     const bool wlds = dense_wlds(F, E, R);
     const size_t smem = dense_smem_bytes(F, E, R, wlds);
     const int n_tiles = (B + TB - 1) / TB;
-    // the instantiated shapes: YelpChi (F 32) and Amazon (F 25) at emb 64 and 128, three relations; anything else: run-time shape
     typedef void (*kern_t)(const DenseArgs);
-    kern_t kern;
-    if (R == 3 && F == 32 && E == 64 && wlds) kern = dense_step_kernel<true, 32, 64, 3>;
-    else if (R == 3 && F == 25 && E == 64 && wlds) kern = dense_step_kernel<true, 25, 64, 3>;
-    else if (R == 3 && F == 32 && E == 128 && !wlds) kern = dense_step_kernel<false, 32, 128, 3>;
-    else if (R == 3 && F == 25 && E == 128 && !wlds) kern = dense_step_kernel<false, 25, 128, 3>;
-    else kern = wlds ? dense_step_kernel<true, 0, 0, 0> : dense_step_kernel<false, 0, 0, 0>;
-    static kern_t attr_done[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool seen = false;
-    for (kern_t k : attr_done) seen = seen || k == kern;
-    if (!seen) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-            hipSuccess)
-            return PCG_E_LAUNCH;
-        for (kern_t &k : attr_done)
-            if (!k) {
-                k = kern;
-                break;
-            }
-    }
+    const kern_t kern = dense_dispatch(F, E, R, wlds, [](auto s) -> kern_t {
+        using S = decltype(s);
+        return dense_step_kernel<S::wlds, S::F, S::E, S::R>;
+    });
+    if (allow_dynamic_lds(kern, 160 * 1024) != PCG_OK) return PCG_E_LAUNCH;
     const dim3 grid(n_tiles * a.n_split + n_sort_blocks), block(DENSE_THREADS);
     const size_t sort_smem = n_sort_blocks ? sizeof(uint64_t) * DENSE_SORT_TILE + sizeof(int) * DENSE_THREADS : 0;
     hipLaunchKernelGGL(kern, grid, block, smem > sort_smem ? smem : sort_smem, static_cast<hipStream_t>(stream), a);

@@ -64,21 +64,9 @@ bool infer_wlds(int F, int E, int R) {
     return (int64_t)kparts * TB * E <= (int64_t)(1 + R) * TB * (E + 1);
 }
 
-static int device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cus[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-        cus[dev] = n;
-    }
-    return cus[dev];
-}
-
 static int infer_blocks(int B) {
     const int n_tiles = (B + TB - 1) / TB;
-    const int cus = device_cus();
+    const int cus = device_cus(256);
     return n_tiles < cus ? n_tiles : cus;
 }
 
@@ -87,29 +75,13 @@ int launch_infer_dense(const DenseArgs &a, int B, hipStream_t st, float *h_out) 
     const bool wlds = infer_wlds(F, E, R);
     const size_t smem = dense_smem_bytes(F, E, R, wlds);
     typedef void (*kern_t)(const DenseArgs, int, float *);
-    kern_t kern;
-    bool persist = true;
-    if (R == 3 && F == 32 && E == 64 && wlds) kern = infer_dense_kernel<true, 32, 64, 3, true>;
-    else if (R == 3 && F == 25 && E == 64 && wlds) kern = infer_dense_kernel<true, 25, 64, 3, true>;
-    else if (R == 3 && F == 32 && E == 128 && !wlds) kern = infer_dense_kernel<false, 32, 128, 3, true>;
-    else if (R == 3 && F == 25 && E == 128 && !wlds) kern = infer_dense_kernel<false, 25, 128, 3, true>;
-    else {
-        kern = wlds ? infer_dense_kernel<true, 0, 0, 0, false> : infer_dense_kernel<false, 0, 0, 0, false>;
-        persist = false;
-    }
-    static kern_t attr_done[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool seen = false;
-    for (kern_t k : attr_done) seen = seen || k == kern;
-    if (!seen) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-            hipSuccess)
-            return PCG_E_LAUNCH;
-        for (kern_t &k : attr_done)
-            if (!k) {
-                k = kern;
-                break;
-            }
-    }
+    bool persist = false;                             // (the fixed shapes only: see infer_dense_kernel)
+    const kern_t kern = dense_dispatch(F, E, R, wlds, [&persist](auto s) -> kern_t {
+        using S = decltype(s);
+        persist = S::F != 0;
+        return infer_dense_kernel<S::wlds, S::F, S::E, S::R, S::F != 0>;
+    });
+    if (allow_dynamic_lds(kern, 160 * 1024) != PCG_OK) return PCG_E_LAUNCH;
     const int n_tiles = (B + TB - 1) / TB;
     hipLaunchKernelGGL(kern, dim3(persist ? infer_blocks(B) : n_tiles), dim3(DENSE_THREADS), smem, st, a, n_tiles, h_out);
     PCG_LAUNCH_CHECK();

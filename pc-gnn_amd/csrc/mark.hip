@@ -14,6 +14,7 @@
 // rows; marking them with scattered one-byte stores (mark_long_kernel, score.hip: every store its own partially written line)
 // took 0.88 ms per 20-batch epoch + 0.46 ms for the other rows + the zeroing pass - 67 us per step, 17 % of it.
 #include "choose.h"
+#include "launch.h"
 
 namespace pcg {
 
@@ -269,13 +270,7 @@ int pcg_mark_touched_planned(const pcg_graph_desc *g, const int32_t *nodes, int3
     a.n_ranges = (int)((map_stride + (1ll << shift) - 1) >> shift);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t smem = (size_t)1 << (shift - 3);
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(pcg::mark_sweep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                64 * 1024) != hipSuccess)
-            return PCG_E_LAUNCH;
-        attr_done = true;
-    }
+    if (pcg::allow_dynamic_lds(pcg::mark_sweep_kernel, 64 * 1024) != PCG_OK) return PCG_E_LAUNCH;
     hipLaunchKernelGGL(pcg::mark_sweep_kernel, dim3(a.n_slots * a.n_ranges), dim3(pcg::SWEEP_THREADS), smem, st, a);
     PCG_LAUNCH_CHECK();
     // per batch: as many workgroups as its rows could need (a wave per row of > 64 neighbours, per four shorter ones), the whole

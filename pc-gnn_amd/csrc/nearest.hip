@@ -291,13 +291,7 @@ int pcg_topk_similar(const float *Q, int32_t n, const float *bank, int32_t M, in
                            (int64_t)M, emb, qn2, cn2);
         PCG_LAUNCH_CHECK();
     }
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(pcg::topk_scan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                pcg::TOPK_SMEM_MAX) != hipSuccess)
-            return PCG_E_LAUNCH;
-        attr_done = true;
-    }
+    if (pcg::allow_dynamic_lds(pcg::topk_scan_kernel, pcg::TOPK_SMEM_MAX) != PCG_OK) return PCG_E_LAUNCH;
     const int64_t row_stride = (int64_t)n_qt * 16;
     hipLaunchKernelGGL(pcg::topk_scan_kernel, dim3((n_qt + W - 1) / W, S), dim3(64 * W), smem, st, Q, n, bank, M, emb, k, metric, q_ids,
                        bank_ids, qn2, cn2, slice_tiles, row_stride, S > 1 ? part_pos : out_pos, S > 1 ? part_score : out_score);

@@ -1877,17 +1877,6 @@ int launch_select_rows(const ChooseArgs &a, hipStream_t st) {
     as.key_cap = big ? BIG_KEYCAP : WG_KEYCAP;
     const int nblk = big ? (blocks > 512 ? 512 : blocks) : blocks;
     const size_t smem = select_smem_bytes(as.key_cap);
-    if (big) {
-        static bool attr_big = false;
-        if (!attr_big) {
-            const void *ks[6] = {reinterpret_cast<const void *>(select_rows<0, false>), reinterpret_cast<const void *>(select_rows<1, false>),
-                                 reinterpret_cast<const void *>(select_rows<2, false>), reinterpret_cast<const void *>(select_rows<0, true>),
-                                 reinterpret_cast<const void *>(select_rows<1, true>), reinterpret_cast<const void *>(select_rows<2, true>)};
-            for (const void *k : ks)
-                if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return PCG_E_LAUNCH;
-            attr_big = true;
-        }
-    }
     const int row_blocks = nblk - (a.clf.clf_next ? a.clf.n_wg : 0);      // (training: one of the workgroups steps the label classifier)
     const int rc = select_sort_shape(as, row_blocks);
     if (rc != PCG_OK) return rc;
@@ -1895,9 +1884,10 @@ int launch_select_rows(const ChooseArgs &a, hipStream_t st) {
     const bool pre = as.n_sort == 0;
     const int clf = !a.clf.clf_next ? 0 : a.g.feat_stride > 256 ? 2 : 1;
     typedef void (*sel_kern_t)(const ChooseArgs);
-    const sel_kern_t kern = clf == 2 ? (pre ? select_rows<2, true> : select_rows<2, false>)
-                          : clf == 1 ? (pre ? select_rows<1, true> : select_rows<1, false>)
-                                     : (pre ? select_rows<0, true> : select_rows<0, false>);
+    const sel_kern_t kerns[2][3] = {{select_rows<0, false>, select_rows<1, false>, select_rows<2, false>},
+                                    {select_rows<0, true>, select_rows<1, true>, select_rows<2, true>}};
+    const sel_kern_t kern = kerns[pre][clf];
+    if (big && allow_dynamic_lds(kern, (int)smem) != PCG_OK) return PCG_E_LAUNCH;     // (BIG_KEYCAP keys: beyond 64 KiB)
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(SEL_NW * PCG_WAVE), smem, st, as);
     PCG_LAUNCH_CHECK();
     if (a.g.max_degree > as.key_cap) {       // rows too long for the LDS keys: their own launch (hub-heavy graphs only)
@@ -1910,13 +1900,7 @@ int launch_select_rows(const ChooseArgs &a, hipStream_t st) {
         }
         static_assert(LONG_KEYCAP == LONG_NW * PCG_WAVE * 32, "pass A of an LDS row keeps one bit per iteration in a uint32");
         const size_t long_smem = sizeof(uint32_t) * (LONG_KEYCAP + 4 * LONG_NW * PCG_WAVE + PCG_WAVE) + sizeof(int) * (2 * LONG_NW + 8);
-        static bool attr_done = false;
-        if (!attr_done) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(select_long_rows), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)long_smem) != hipSuccess)
-                return PCG_E_LAUNCH;
-            attr_done = true;
-        }
+        if (allow_dynamic_lds(select_long_rows, (int)long_smem) != PCG_OK) return PCG_E_LAUNCH;
         ChooseArgs al = as;                  // (the keys are sorted by now: nothing to sort, nothing to wait for)
         al.n_sort = 0;
         al.pending_clear = nullptr;
@@ -1986,19 +1970,16 @@ __global__ void __launch_bounds__(DENSE_THREADS) dense_select_kernel(const Dense
 // needs the chip's other CUs: at most PCG_PIPE_MAX_TILES (default 128) tiles.  Not for rows beyond the select kernel's LDS keys
 // (their launch of its own), nor feature rows of more than 256 floats (the classifier step's wide variant).
 int dense_select_blocks(const pcg_graph_desc &g, int emb, int B) {
-    static int max_tiles = -1, n_cu = 0;
+    static int max_tiles = -1;
     if (max_tiles < 0) {
         const char *e = getenv("PCG_PIPE_MAX_TILES");
         max_tiles = e ? atoi(e) : 128;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            n_cu = 0;
     }
     if (B < 1 || emb < 16 || emb % 16 != 0 || g.n_rel < 1 || g.n_rel > PCG_MAX_REL) return 0;
     const int n_tiles = (B + TB - 1) / TB;
     if (n_tiles > max_tiles || g.feat_stride > 256 || g.max_degree > WG_KEYCAP) return 0;
     if (dense_smem_bytes(g.feat_dim, emb, g.n_rel, dense_wlds(g.feat_dim, emb, g.n_rel)) > 160 * 1024) return 0;
-    int n_sel = n_cu - n_tiles;
+    int n_sel = device_cus(0) - n_tiles;     // (a failed query: no CU to spare, 0 below)
     n_sel = (n_sel > SEL_BLOCKS ? SEL_BLOCKS : n_sel) / SEL_SHARDS * SEL_SHARDS;
     const int n_sort = g.n_pos > 0 && g.n_pos <= RANK_MAX ? (g.n_pos + PCG_WAVE - 1) / PCG_WAVE : 0;
     if (n_sel < 64 || n_sel - 8 < n_sort) return 0;
@@ -2022,28 +2003,12 @@ int launch_dense_select(const DenseArgs &d, const ChooseArgs &a, int n_sel, hipS
     const bool wlds = dense_wlds(F, E, R);
     const size_t dsm = dense_smem_bytes(F, E, R, wlds), ssm = select_smem_bytes(DENSE_WAVES * WAVE_AREA, DENSE_WAVES);
     typedef void (*kern_t)(const DenseArgs, const ChooseArgs, const int);
-    kern_t kern;
     const bool pre = as.n_sort == 0;         // the select half's presorted instantiation (select_rows_body)
-#define PCG_DS_KERN(W, F, E, R) (pre ? dense_select_kernel<W, F, E, R, true> : dense_select_kernel<W, F, E, R, false>)
-    if (R == 3 && F == 32 && E == 64 && wlds) kern = PCG_DS_KERN(true, 32, 64, 3);
-    else if (R == 3 && F == 25 && E == 64 && wlds) kern = PCG_DS_KERN(true, 25, 64, 3);
-    else if (R == 3 && F == 32 && E == 128 && !wlds) kern = PCG_DS_KERN(false, 32, 128, 3);
-    else if (R == 3 && F == 25 && E == 128 && !wlds) kern = PCG_DS_KERN(false, 25, 128, 3);
-    else kern = wlds ? PCG_DS_KERN(true, 0, 0, 0) : PCG_DS_KERN(false, 0, 0, 0);
-#undef PCG_DS_KERN
-    static kern_t attr_done[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool seen = false;
-    for (kern_t k : attr_done) seen = seen || k == kern;
-    if (!seen) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-            hipSuccess)
-            return PCG_E_LAUNCH;
-        for (kern_t &k : attr_done)
-            if (!k) {
-                k = kern;
-                break;
-            }
-    }
+    const kern_t kern = dense_dispatch(F, E, R, wlds, [pre](auto s) -> kern_t {
+        using S = decltype(s);
+        return pre ? dense_select_kernel<S::wlds, S::F, S::E, S::R, true> : dense_select_kernel<S::wlds, S::F, S::E, S::R, false>;
+    });
+    if (allow_dynamic_lds(kern, 160 * 1024) != PCG_OK) return PCG_E_LAUNCH;
     static_assert(sizeof(uint64_t) * DENSE_SORT_TILE + sizeof(int) * DENSE_THREADS <= 64 * 1024, "the riders' LDS is within every dense shape's");
     hipLaunchKernelGGL(kern, dim3(d.n_tile_blocks + n_sel + n_riders), dim3(DENSE_THREADS), dsm > ssm ? dsm : ssm, st, d, as, n_sel);
     PCG_LAUNCH_CHECK();

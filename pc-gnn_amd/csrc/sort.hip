@@ -4,7 +4,7 @@
 // Keys are unique 64-bit (orderable(score) << 32 | position in train_pos), so the
 // result is a total order: equal scores stay in list order.  Small P: one-launch rank sort;
 // large P: bucket sort (sampled splitters, scatter, rank sort inside the buckets).
-#include "common.h"
+#include "launch.h"
 
 namespace pcg {
 
@@ -317,12 +317,7 @@ int launch_bk_onepass(const uint64_t *raw, int n_pos, uint64_t *keys, int cap, u
     int nb, ns;
     bk1_geometry(n_pos, nb, ns);
     const size_t smem = sizeof(uint64_t) * (BK1_TILE + SORT_THREADS);
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(bk_onepass), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return PCG_E_LAUNCH;
-        attr_done = true;
-    }
+    if (allow_dynamic_lds(bk_onepass, (int)smem) != PCG_OK) return PCG_E_LAUNCH;
     hipLaunchKernelGGL(bk_onepass, dim3(nb + 8), dim3(SORT_THREADS), smem, st, raw, n_pos, nb, ns, keys, cap, status);
     PCG_LAUNCH_CHECK();
     return PCG_OK;

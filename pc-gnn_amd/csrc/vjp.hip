@@ -62,27 +62,12 @@ extern "C" int pcg_dense_vjp(const pcg_graph_desc *g, const pcg_train_state *st,
     const int F = g->feat_dim, E = st->emb, R = g->n_rel;
     const bool wlds = dense_wlds(F, E, R);
     const size_t smem = dense_smem_bytes(F, E, R, wlds);
-    // the shape dispatch of the training launch (dense.hip)
     typedef void (*kern_t)(const DenseArgs, const float *, const float *);
-    kern_t kern;
-    if (R == 3 && F == 32 && E == 64 && wlds) kern = dense_vjp_kernel<true, 32, 64, 3>;
-    else if (R == 3 && F == 25 && E == 64 && wlds) kern = dense_vjp_kernel<true, 25, 64, 3>;
-    else if (R == 3 && F == 32 && E == 128 && !wlds) kern = dense_vjp_kernel<false, 32, 128, 3>;
-    else if (R == 3 && F == 25 && E == 128 && !wlds) kern = dense_vjp_kernel<false, 25, 128, 3>;
-    else kern = wlds ? dense_vjp_kernel<true, 0, 0, 0> : dense_vjp_kernel<false, 0, 0, 0>;
-    static kern_t attr_done[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool seen = false;
-    for (kern_t k : attr_done) seen = seen || k == kern;
-    if (!seen) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-            hipSuccess)
-            return PCG_E_LAUNCH;
-        for (kern_t &k : attr_done)
-            if (!k) {
-                k = kern;
-                break;
-            }
-    }
+    const kern_t kern = dense_dispatch(F, E, R, wlds, [](auto s) -> kern_t {
+        using S = decltype(s);
+        return dense_vjp_kernel<S::wlds, S::F, S::E, S::R>;
+    });
+    if (allow_dynamic_lds(kern, 160 * 1024) != PCG_OK) return PCG_E_LAUNCH;
     // (acts mode: one workgroup per tile - a.n_split is 1)
     hipLaunchKernelGGL(kern, dim3((unsigned)a.n_tile_blocks), dim3(DENSE_THREADS), smem, static_cast<hipStream_t>(stream), a, d_logits,
                        d_center);

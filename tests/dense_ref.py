@@ -233,6 +233,49 @@ def kernel_of(user, F, E, R):
     return f"{USERS[user]}<{args}" + ((", true>" if fixed else ", false>") if forward_only else ">")
 
 
+# The fifth user: the fused launch of the pipelined training step (launch_dense_select, csrc/select.hip) - the same six shapes by
+# training's rule, times PRE, the select half's presorted instantiation: twelve kernels.
+FUSED_KERNEL = "dense_select_kernel"
+PIPE_MAX_TILES, WG_KEYCAP, SEL_BLOCKS, SEL_SHARDS, RANK_MAX = 128, 10240, 768, 8, 16384
+
+
+def dense_select_blocks(F, E, R, B, n_pos, max_degree, cus=None):
+    """dense_select_blocks of csrc/select.hip, restated: the select workgroups of the fused launch beside the tiles of a batch of
+    B rows, or 0 - the step keeps its three launches"""
+    cus = EDGE_CUS if cus is None else cus
+    if B < 1 or E < 16 or E % 16 or not 1 <= R <= 8:
+        return 0
+    n_tiles = (B + TILE_ROWS - 1) // TILE_ROWS
+    if n_tiles > PIPE_MAX_TILES or (F + 3) // 4 * 4 > 256 or max_degree > WG_KEYCAP:
+        return 0
+    if dense_smem_bytes(F, E, R, dense_wlds(F, E, R)) > 160 * 1024:
+        return 0
+    n_sel = max(min(cus - n_tiles, SEL_BLOCKS), 0) // SEL_SHARDS * SEL_SHARDS
+    n_sort = (n_pos + 63) // 64 if 0 < n_pos <= RANK_MAX else 0
+    return n_sel if n_sel >= 64 and n_sel - 8 >= n_sort else 0
+
+
+def fused_steps_ahead(F, E, R, B, n_pos, max_degree, switch, n_steps):
+    """FusedPCGNN._ahead, restated: whether a pipelined sequence of n_steps batches of up to B rows steps the label classifier
+    two batches ahead - the switch (clf_ahead), three steps or more, the keys a refresh leaves sorted (pcg_dense_sorts_keys; or
+    none at all) and room for the sort riders (pcg_dense_select_ahead_ok)"""
+    tiles, riders = (B + TILE_ROWS - 1) // TILE_ROWS, (n_pos + 63) // 64
+    presort = 1 <= n_pos <= RANK_MAX and tiles + riders <= 256
+    room = dense_select_blocks(F, E, R, B, n_pos, max_degree) > 0 and (n_pos <= 0 or (n_pos <= RANK_MAX and riders <= 4 * tiles))
+    return bool(switch and n_steps >= 3 and (presort or n_pos == 0) and room)
+
+
+def fused_kernel_of(F, E, R, B, n_pos, max_degree, ahead):
+    """The instantiation launch_dense_select picks for the tiles of a batch of B rows beside a selection whose keys were sorted a
+    launch earlier (ahead) or are sorted in the launch itself, as the kernel's name; None: the step is not pipelined"""
+    if not dense_select_blocks(F, E, R, B, n_pos, max_degree):
+        return None
+    wlds = dense_wlds(F, E, R)
+    args = f"{F}, {E}, {R}" if FIXED.get((F, E, R)) == wlds else "0, 0, 0"
+    pre = ahead or not 0 < n_pos <= RANK_MAX           # (nothing for the select half to sort: sorted already, or no in-kernel sort)
+    return f"{FUSED_KERNEL}<{str(wlds).lower()}, {args}, {str(bool(pre)).lower()}>"
+
+
 # Edge shapes: what the host rules accept and the tables above do not reach.  Per shape: (the training kernel, batch sizes, seed
 # of the case).  tests/test_edge_shapes_host.py re-derives every statement below from the restated rules:
 #   (16, 64, 4)   the run-time LDS-weight kernels of all four users; R = 4

@@ -4,6 +4,8 @@ tests/test_gpu_edge_shapes.py, tests/test_gpu_grad_f64.py and tests/test_gpu_cus
 * which of its six instantiations each of the four users of dense_tile_body - training, the seeded backward, whole-set inference,
   attribution - picks for every shape, from the host's dispatch rules restated in Python, and that the 24 instantiations are
   each launched by a shape some GPU test runs;
+* the same for the fifth user, the fused launch of the pipelined step (twelve instantiations: the six times the select half's
+  presorted variant), conditioned on what dense_select_blocks accepts and on when the classifier runs two batches ahead;
 * the attribution's LDS overlay: every combination is in the table - the fourth (dcat over, dx0 appended), which only the padding
   of K2 makes reachable and only at R = 1, included;
 * the attribution's shape limit through the C ABI (fake descriptors, n = 0: nothing is launched), against the restated rule;
@@ -95,6 +97,68 @@ def test_every_instantiation_is_launched_by_a_gpu_test_shape():
     # the fixed F = 25 vjp kernels, and the vjp on wide rows
     assert {(25, 64, 3), (25, 128, 3)} <= set(V.SHAPES) and max(s[0] for s in V.SHAPES) > 64
     assert D.REL_DEG.keys() >= {4, 7, 8} and all(len(D.REL_DEG[R]) == R for R in D.REL_DEG)
+
+
+# ---- the fifth user: the fused launch of the pipelined step -------------------------------------------------------------------------
+def graph_of(w):
+    """(F, R, train positives, maximum degree): what the fused launch's host rules read of a workload"""
+    return w.X.shape[1], len(w.csr), len(w.train_pos), max(int(np.diff(ip).max()) for ip, _ in w.csr)
+
+
+def fused_kernels(w, E, B, switch, lengths):
+    """the fused launch's instantiations that sequences of `lengths` steps over batches of B rows launch, the engine's clf_ahead
+    switch as given (None: its default, on from 1024 train positives); a sequence is pipelined from two steps (_pipelines)"""
+    F, R, P, deg = graph_of(w)
+    switch = P >= 1024 if switch is None else switch
+    got = {D.fused_kernel_of(F, E, R, B, P, deg, D.fused_steps_ahead(F, E, R, B, P, deg, switch, n)) for n in lengths if n >= 2}
+    return got - {None}
+
+
+def compared_lengths(w, B):
+    """the sequences of test_gpu_pipelined_step._run_and_compare: two epochs, one epoch, batches 0 .. mid"""
+    nb = -(-2 * len(w.train_pos) // B)
+    return 2 * nb, nb, nb // 2 + 1
+
+
+def test_every_fused_launch_instantiation_is_launched_by_a_gpu_test():
+    """tests/test_gpu_pipelined_step.py (but for its other shapes), tests/test_gpu_clf_ahead.py and
+    tests/test_gpu_launch_sequences.py train at emb 64 on F = 32 and F = 25 only, and the F = 25 graph has too few train positives
+    for the classifier to run ahead: three of the twelve kernels.  The other shapes of test_gpu_pipelined_step.py reach the other
+    nine, each case the kernel it is there for."""
+    from pcgnn_amd import synth
+    from tests import test_gpu_clf_ahead as CA
+    from tests import test_gpu_launch_sequences as LS
+    from tests import test_gpu_pipelined_step as PS
+    name = lambda w, F, E, R, pre: f"{D.FUSED_KERNEL}<{str(w).lower()}, {F}, {E}, {R}, {str(pre).lower()}>"
+    want = {name(*inst, pre) for inst in D.INSTANTIATIONS for pre in (True, False)}
+    assert len(want) == 12
+    mini = lambda feat: synth.make_workload("mini", PS.MINI["n"], feat, PS.MINI["rel_edges"], PS.MINI["pos_rate"], seed=PS.MINI["seed"])
+    old = set()
+    for w, batches in ((mini(32), [256]), (synth.yelp_like(0), [1024, 2048]), (synth.amazon_like(0), [256])):
+        for B in batches:
+            got = fused_kernels(w, 64, B, None, compared_lengths(w, B))
+            assert got, (w.name, B)                                       # (pipelined, as the tests assert on the device)
+            old |= got
+    assert D.dense_select_blocks(32, 64, 3, 2064, 1000, 100) == 0         # test_above_threshold_falls_back: 129 tiles
+    for with_pos in (True, False):                                        # test_gpu_clf_ahead.py: both engines of a pair
+        w = CA.workload(with_pos)[0]
+        for switch in (True, False):
+            old |= fused_kernels(w, 64, CA.B, switch, (1, 2, 3, 4, 5, 6, 7))
+    for switch in (None, True, False):                                    # test_gpu_launch_sequences.py: new_trainer(ahead=...)
+        old |= fused_kernels(mini(32), 64, LS.BATCH, switch, (2, 3, 6))
+    assert old == {name(True, 32, 64, 3, True), name(True, 32, 64, 3, False), name(True, 25, 64, 3, False)}, old
+    new = set()
+    for feat, emb, ahead in PS.OTHER_SHAPES:
+        w = mini(feat)
+        got = fused_kernels(w, emb, PS.MINI["B"], ahead, compared_lengths(w, PS.MINI["B"]))
+        wlds = D.dense_wlds(feat, emb, 3)
+        shape = (feat, emb, 3) if D.FIXED.get((feat, emb, 3)) == wlds else (0, 0, 0)
+        mine = name(wlds, *shape, ahead)
+        assert mine in got and mine not in old and mine not in new, (feat, emb, ahead, got)
+        new.add(mine)
+    assert new == want - old and len(new) == len(PS.OTHER_SHAPES) == 9
+    # the two run-time-shape cases are the edge table's (30, 64, 3), weights in LDS, and (64, 64, 3), weights streamed
+    assert EXPECTED[(30, 64, 3)][0] and not EXPECTED[(64, 64, 3)][0]
 
 
 def test_the_table_has_the_maximum_relation_count_and_more_column_tiles_than_waves():

@@ -23,11 +23,16 @@ def _pair(w, B, **cfg):
     return a, b
 
 
-def _run_and_compare(w, B, expect_pipelined):
-    a, b = _pair(w, B)
+def _run_and_compare(w, B, expect_pipelined, ahead=None, **cfg):
+    """ahead: the engine's clf_ahead switch (None: its default for the graph); cfg: further trainer settings (emb_size)"""
+    a, b = _pair(w, B, **cfg)
     nb = a.batches_per_epoch()
     assert a.pick_size % B != 0, "the last batch of every epoch must be partial"
     assert (a.fused._pipe_blocks > 0) == expect_pipelined
+    if ahead is not None:
+        a.fused.clf_ahead = b.fused.clf_ahead = ahead
+        # (switched on, the two-epoch group below must take the schedule: the select halves' presorted instantiation)
+        assert not ahead or a.fused._ahead([(None, None, B, 0)] * (2 * nb))
     mid = nb // 2
     lists = []
     for t in (a, b):
@@ -56,6 +61,22 @@ def test_pipelined_equals_three_launches_mini():
     from pcgnn_amd import synth
     w = synth.make_workload("mini", 6000, 32, (4000, 30000, 90000), 0.12, seed=3)
     _run_and_compare(w, 256, True)
+
+
+# The instantiations of the fused launch that the tests of this file, tests/test_gpu_clf_ahead.py and
+# tests/test_gpu_launch_sequences.py do not launch (tests/test_edge_shapes_host.py works out which, and that these cases reach
+# them): (feature width, emb_size, the classifier two batches ahead).  emb 128 at the two fixed widths, the two run-time-shape
+# kernels (F 30: weights in LDS, F 64: weights streamed) with the select half sorting its keys (False) and finding them sorted
+# (True: the presorted instantiation), and the presorted fixed kernel of F 25 at emb 64.
+OTHER_SHAPES = [(F, E, ahead) for F, E in [(32, 128), (25, 128), (30, 64), (64, 64)] for ahead in (False, True)] + [(25, 64, True)]
+MINI = dict(n=6000, rel_edges=(4000, 30000, 90000), pos_rate=0.12, seed=3, B=256)
+
+
+@pytest.mark.parametrize("feat,emb,ahead", OTHER_SHAPES)
+def test_pipelined_equals_three_launches_other_shapes(feat, emb, ahead):
+    from pcgnn_amd import synth
+    w = synth.make_workload("mini", MINI["n"], feat, MINI["rel_edges"], MINI["pos_rate"], seed=MINI["seed"])
+    _run_and_compare(w, MINI["B"], True, ahead=ahead, emb_size=emb)
 
 
 # (batch 2048: 128 tiles, the largest batch the fused launch takes - and two classifier workgroups, whose last one counts the step)
