@@ -1018,6 +1018,36 @@ int64_t pcg_topk_alerts_workspace_bytes(int64_t n, int32_t k);
 int pcg_topk_alerts(const float *p1, int32_t stride, int64_t n, int32_t k, void *workspace, int32_t *out_pos, float *out_score,
                     uint32_t *status, void *stream);
 
+/* ---- alert cases ------------------------------------------------------------------
+ * The slots of a member list grouped into linked rings, without the list or the CSR leaving the device.
+ *   members [m] i32 in alert order, 0 <= m <= PCG_ALERTS_MAX_K: a node id in [0, n_nodes) or -1 (padding: in no case); any other
+ *   value sets PCG_ST_LIST_ID_RANGE and is treated as padding.  rel_mask: bit r selects relation r; non-zero, no bit at or
+ *   above g->n_rel.  Slot p is linked to slot q != p when members[p] == members[q], or when for a selected relation r members[q]
+ *   occurs in row r of members[p] or members[p] in row r of members[q] (an edge stored one way links; there is no 2-hop linking).
+ *   A case is a connected component of the valid slots under "linked"; its head is its lowest slot; cases are numbered 0 .. C - 1 by
+ *   ascending head.
+ *   case_of [m] i32: the slot's case, -1 for padding | head [m] i32: entries [0, C) are written |
+ *   offsets [m + 1] i32: entries [0, C] are written, offsets[C] = the number of valid slots | order [m] i32: entries
+ *   [offsets[c], offsets[c + 1]) are case c's slots, ascending; the entries from offsets[C] on are the padding slots, ascending |
+ *   links [m] i32: entries [0, C) = over the case's slots p and the selected relations, the CSR entries of members[p] whose target is a
+ *   member node other than members[p] (directed entries: a symmetric edge counts twice, self-loops count zero); the rest 0 |
+ *   hits [m] i32, with labels [m] i32 (one per slot; both or neither NULL): entries [0, C) = the case's slots with label 1; the rest 0.
+ *   A label outside {0, 1} on a valid slot sets PCG_ST_EVAL_INPUT |
+ *   hdr [4] i32 = C, the number of valid slots, *status as the call's last launch found it, 0.
+ * Launches: three memsets (the header, the counters and the position map, 4 n_nodes bytes) | init | link (a wave per slot and relation; rows of
+ * more than 512 entries are queued) | long rows (16 workgroups per queued row) | flatten | number (one workgroup) | assign |
+ * pcg_topk_alerts over the case numbers (the stable order) | offsets and header (one workgroup).  Lock-free union-find whose root is
+ * the component's lowest slot whatever order the unions land in; integer sums only: the same bits on every run.  Every retry loop is
+ * bounded by m; one that runs out sets PCG_ST_SYNC_TIMEOUT.  A CSR entry outside [0, n_nodes) is skipped and sets
+ * PCG_ST_LIST_ID_RANGE.  workspace: pcg_alert_cases_workspace_bytes(g->n_nodes, m) bytes, 256-byte aligned, contents irrelevant on
+ * entry (capturable).  m == 0: C = 0, offsets[0] = 0 and the header are written, nothing else is read or written (members and the
+ * other outputs may be NULL).  PCG_E_ARG before any launch: a NULL required pointer, m outside [0, PCG_ALERTS_MAX_K], an empty or
+ * out-of-range rel_mask, labels without hits or hits without labels, a workspace too small or misaligned. */
+int64_t pcg_alert_cases_workspace_bytes(int64_t n_nodes, int32_t m);
+int pcg_alert_cases(const pcg_graph_desc *g, const int32_t *members, int32_t m, uint32_t rel_mask, const int32_t *labels, void *workspace,
+                    int64_t workspace_bytes, int32_t *case_of, int32_t *head, int32_t *offsets, int32_t *order, int32_t *links,
+                    int32_t *hits, int32_t *hdr, uint32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ def __getattr__(name):
     # an environment where only the toolchain is wanted
     import importlib
     table = {
-        "DeviceGraph": ".graph", "adj_to_csr": ".graph", "QueryBatch": ".graph", "BaseShape": ".graph", "ChosenLists": ".graph", "Attribution": ".graph", "NearestExamples": ".graph", "AlertList": ".graph",
+        "DeviceGraph": ".graph", "adj_to_csr": ".graph", "QueryBatch": ".graph", "BaseShape": ".graph", "ChosenLists": ".graph", "Attribution": ".graph", "NearestExamples": ".graph", "AlertList": ".graph", "CaseList": ".graph",
         "IntraAgg": ".layers", "InterAgg": ".layers", "InterAgg1": ".layers", "InterAgg3": ".layers",
         "InterAgg5": ".layers", "PCALayer": ".model", "ModelHandler": ".handler", "PCGNNTrainer": ".handler",
         "ResultManager": ".result_manager", "result_manager": None, "utils": None, "synth": None, "fused": None, "ops": None, "layers": None, "model": None, "graph": None,

@@ -183,6 +183,8 @@ PROTOTYPES = {
     "pcg_pr_counts": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
     "pcg_topk_alerts_workspace_bytes": (_I64, [_I64, _I32]),
     "pcg_topk_alerts": (C.c_int, [_P, _I32, _I64, _I32, _P, _P, _P, _P, _P]),
+    "pcg_alert_cases_workspace_bytes": (_I64, [_I64, _I32]),
+    "pcg_alert_cases": (C.c_int, [_G, _P, _I32, C.c_uint32, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pcg_step_front_train": (C.c_int, [_G, _ST, _P, _P, _B, _SEL, _P]),
     "pcg_grad_reduce": (C.c_int, [_P, _I32, _I64, _P, _P, _P]),
     "pcg_adam_apply_pending": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _I32, _H, _P]),

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBNAME = "libpcgnn_hip.so"
-SOURCES = ["score.hip", "mark.hip", "sort.hip", "segmean_pick.hip", "choose.hip", "select.hip", "gather.hip", "dense.hip", "vjp.hip", "halo.hip", "infer.hip", "infer_new.hip", "eval.hip", "rank_eval.hip", "rank.hip", "attr.hip", "explain_new.hip", "nearest.hip", "baseline.hip", "baseline_train.hip"]
+SOURCES = ["score.hip", "mark.hip", "sort.hip", "segmean_pick.hip", "choose.hip", "select.hip", "gather.hip", "dense.hip", "vjp.hip", "halo.hip", "infer.hip", "infer_new.hip", "eval.hip", "rank_eval.hip", "rank.hip", "attr.hip", "explain_new.hip", "nearest.hip", "baseline.hip", "baseline_train.hip", "cases.hip"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
 

@@ -373,6 +373,57 @@ class AlertList:
         return out if self.hits is None else out + (self.hits.cpu().numpy(),)
 
 
+class CaseList:
+    """Alerts grouped into cases (``FusedPCGNN.cases``, ``ops.group_members``; the kernel: pcg_alert_cases).  A slot is a position
+    of the member list, which is in alert order.  Slot p is linked to slot q when both name the same node or when, in a selected
+    relation, either node occurs in the other's CSR row (an edge stored one way links; a shared neighbour that is no member
+    does not: there is no 2-hop linking).  A case is a connected component of the non-padding slots; its head is its lowest
+    slot - its highest-ranked alert - and cases are numbered by ascending head, so case 0 holds alert 0.  Every value is a
+    function of the inputs alone: the same bits on every run.
+
+    case_of [m] int32: the slot's case, -1 for padding | head [C] int32 | offsets [C + 1] int32 and order [m_valid] int32: case
+    c's slots, ascending, are order[offsets[c] : offsets[c + 1]] | links [C] int32: the CSR entries of the case's members, over
+    the selected relations, whose target is another member node (directed: a symmetric edge counts twice; self-loops count
+    zero) | hits [C] int32 or None: the case's slots with label 1 | n_cases: C | members [m] int32: the grouped ids |
+    alerts: the ``AlertList`` the members are the ids of, or None.  Device tensors (the methods work on CPU tensors too)."""
+
+    def __init__(self, case_of: torch.Tensor, head: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor, links: torch.Tensor,
+                 hits: Optional[torch.Tensor], n_cases: int, members: torch.Tensor, alerts: Optional["AlertList"] = None):
+        self.case_of, self.head, self.offsets, self.order, self.links, self.hits = case_of, head, offsets, order, links, hits
+        self.n_cases, self.members, self.alerts = int(n_cases), members, alerts
+
+    def size(self) -> torch.Tensor:
+        """[C] int32: the slots of each case."""
+        return self.offsets[1:] - self.offsets[:-1]
+
+    def case(self, c: int):
+        """The slots of case c, ascending - with an alert list attached (slots, ids, prob)."""
+        if not 0 <= c < self.n_cases:
+            raise IndexError(f"case {c} of {self.n_cases}")
+        lo, hi = (int(v) for v in self.offsets[c:c + 2].tolist())
+        slots = self.order[lo:hi]
+        if self.alerts is None:
+            return slots
+        at = slots.long()
+        return slots, self.alerts.ids[at], self.alerts.prob[at]
+
+    def expected_hits(self) -> torch.Tensor:
+        """float64 [C]: the sum of the members' positive-class probabilities per case (needs the alert list).  A segmented
+        reduction over ``order`` (torch.segment_reduce: every case is summed on its own, in slot order) - no atomics, no
+        ``index_add_``, the same bits on every run."""
+        if self.alerts is None:
+            raise ValueError("expected_hits: this CaseList was made from bare members, without an alert list's probabilities")
+        p = self.alerts.prob[self.order.long()].double()
+        if self.n_cases == 0:
+            return p[:0]
+        return torch.segment_reduce(p, "sum", lengths=self.size().long(), unsafe=True)
+
+    def to_numpy(self):
+        """(case_of, head, offsets, order, links) - with labels (..., hits) - as host arrays."""
+        out = tuple(t.cpu().numpy() for t in (self.case_of, self.head, self.offsets, self.order, self.links))
+        return out if self.hits is None else out + (self.hits.cpu().numpy(),)
+
+
 class BaseShape:
     """What a ``QueryBatch`` is validated against: the base graph's node count, feature width and relation count.  A
     ``DeviceGraph`` has the same three attributes; this stands in for one where there is no GPU (host-side checks, tests)."""

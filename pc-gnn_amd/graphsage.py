@@ -217,6 +217,10 @@ class _Head(nn.Module):
     def alerts(self, ids=None, k=100, chunk=None, labels=None, query=None):
         return self.engine().alerts(ids, k=k, chunk=chunk, labels=labels, query=query)
 
+    def cases(self, ids=None, k=100, relations=None, chunk=None, labels=None, query=None):
+        """the alert list grouped into linked cases (``EvalCalls.cases``)"""
+        return self.engine().cases(ids, k=k, relations=relations, chunk=chunk, labels=labels, query=query)
+
     # -- training on the device (baseline.BaselineEngine: pcg_baseline_train) ----------------------------------------------------
     def configure_optimizer(self, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8):
         return self.engine().configure_optimizer(lr, weight_decay, betas=betas, eps=eps)

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .graph import ChosenLists, DeviceGraph
+from .graph import CaseList, ChosenLists, DeviceGraph
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -558,6 +558,72 @@ def topk_alerts(prob: torch.Tensor, k: int, stream=None, status: Optional[torch.
     st = _stream(dev) if stream is None else C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
     _lib.check(lib.pcg_topk_alerts(p1, stride, n, k, _p(ws), _p(pos), _p(score), _p(status), st), "pcg_topk_alerts")
     return pos, score
+
+
+def relation_mask(g: DeviceGraph, relations) -> int:
+    """``relations`` (None = all, else a non-empty subset of range(R)) as pcg_alert_cases' bit mask."""
+    if relations is None:
+        return (1 << g.R) - 1
+    rel = sorted({int(r) for r in relations})
+    if not rel or rel[0] < 0 or rel[-1] >= g.R:
+        raise ValueError(f"relations: a non-empty subset of range({g.R}), got {list(relations)!r}")
+    return sum(1 << r for r in rel)
+
+
+def group_members_enqueue(g: DeviceGraph, members: torch.Tensor, rel_mask: int, labels: Optional[torch.Tensor], status: torch.Tensor):
+    """pcg_alert_cases on the current stream, nothing read back: -> (case_of, head, offsets, order, links, hits or None, hdr), every
+    buffer at the size include/pcgnn.h documents (head / links / hits [m], offsets [m + 1], order [m], hdr [4] = C, valid slots,
+    the status word, 0).  members int32 [m] and labels int32 [m] or None on the device.  Capture-safe once the per-device
+    workspace has its size (a first call outside the capture)."""
+    lib = _lib.load()
+    dev = g.device
+    m = int(members.numel())
+    if m > _lib.PCG_ALERTS_MAX_K:
+        raise ValueError(f"group_members: at most {_lib.PCG_ALERTS_MAX_K} members, got {m}")
+    nbytes = int(lib.pcg_alert_cases_workspace_bytes(g.n_nodes, m))
+    if nbytes < 0:
+        _lib.check(nbytes, f"pcg_alert_cases_workspace_bytes(n_nodes={g.n_nodes}, m={m})")
+    ws = _cached_ws(_eval_cache(dev), "cases_ws", nbytes, dev)
+    cap = max(m, 1)                                                     # (an empty tensor has no address)
+    case_of, head, order, links = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(4))
+    offsets = torch.empty(m + 1, dtype=torch.int32, device=dev)
+    hits = None if labels is None else torch.empty(cap, dtype=torch.int32, device=dev)
+    hdr = torch.empty(4, dtype=torch.int32, device=dev)
+    _lib.check(lib.pcg_alert_cases(g.desc_ref(), _p(members) if m else None, m, rel_mask, _p(labels) if m else None, _p(ws), nbytes,
+                                   _p(case_of), _p(head), _p(offsets), _p(order), _p(links), _p(hits) if m else None, _p(hdr),
+                                   _p(status), _stream(dev)), "pcg_alert_cases")
+    return case_of[:m], head, offsets, order, links, hits, hdr
+
+
+def group_members(g: DeviceGraph, members, relations=None, labels=None, status: Optional[torch.Tensor] = None, alerts=None):
+    """Members grouped into cases (pcg_alert_cases) -> ``graph.CaseList``.  members: up to 65536 node ids of ``g`` in alert
+    order (int sequence or tensor), -1 = padding (in no case); slot p is linked to slot q when both name the same node or, in a
+    selected relation, either node is in the other's CSR row; a case is a connected component, numbered by its lowest slot.
+    relations: None = all, else a non-empty subset of range(R).  labels (one per slot, 0 / 1): the result holds ``hits``.
+    Enqueues on the current stream and reads the header - the number of cases and the status word - once: an id that is
+    neither -1 nor a node (it is then treated as padding), a label outside {0, 1} or a bounded loop that ran out raises.
+    status: a zeroed int32 device word of the caller's - then nothing raises, the word is the report (``check_status``).
+    Out of scope: the ids of a query batch (they are query-local), a partitioned graph, 2-hop linking, more than 65536 members."""
+    dev = g.device
+    members = _i32(members, dev).view(-1)
+    m = int(members.numel())
+    rel_mask = relation_mask(g, relations)
+    lab = None
+    if labels is not None:
+        lab = _i32(labels, dev).view(-1)
+        if lab.numel() != m:
+            raise ValueError(f"group_members: {lab.numel()} labels for {m} members")
+    own = status is None
+    st = torch.zeros(1, dtype=torch.int32, device=dev) if own else status
+    case_of, head, offsets, order, links, hits, hdr = group_members_enqueue(g, members, rel_mask, lab, st)
+    n_cases, n_valid, word, _ = (int(v) for v in hdr.tolist())            # the one synchronisation
+    if own and word:
+        what = [name for bit, name in ((_lib.PCG_ST_LIST_ID_RANGE, "a member id that is neither -1 nor a node of the graph"),
+                                       (_lib.PCG_ST_EVAL_INPUT, "a label outside {0, 1}"),
+                                       (_lib.PCG_ST_SYNC_TIMEOUT, "a bounded union-find loop ran out")) if word & bit]
+        raise _lib.PcgnnLibraryError(f"group_members: {', '.join(what) or 'device status'} (status {word})")
+    return CaseList(case_of, head[:n_cases], offsets[:n_cases + 1], order[:n_valid], links[:n_cases],
+                    None if hits is None else hits[:n_cases], n_cases, members, alerts)
 
 
 TOPK_METRICS = {"dot": 0, "cosine": 1, "l2": 2}

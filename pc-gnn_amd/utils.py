@@ -402,6 +402,26 @@ def similar_examples(engine, ids, k: int = 5, labels=None, query=None):
         return near, prob, ex
 
 
+def alert_cases(model_or_engine, ids, k: int = 100, labels=None, relations=None):
+    """The k highest-scoring rows of ``ids`` grouped into cases - rings of alerts linked through the graph's relations - as
+    ``graph.CaseList``, for any model or engine that has ``alerts`` (FusedPCGNN, BaselineEngine, GraphSage, GCN): its own
+    ``cases`` where it has one, else ``alerts`` -> ``ops.group_members`` on the engine's graph.  labels (one per row of ids,
+    0 / 1): the positives per case.  relations: None = all.  Out of scope: query batches, partitioned graphs, 2-hop linking."""
+    if hasattr(model_or_engine, "cases"):
+        return model_or_engine.cases(ids, k=k, relations=relations, labels=labels)
+    if not hasattr(model_or_engine, "alerts") or not hasattr(model_or_engine, "g"):
+        raise ValueError("alert_cases needs a model or engine that has alerts (and its resident graph)")
+    from . import ops
+    al = model_or_engine.alerts(ids, k=k)
+    slot_labels = None
+    if labels is not None:
+        lab = torch.as_tensor(np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)).to(al.pos.device).to(torch.int32).view(-1)
+        if lab.numel() != al.n:
+            raise ValueError(f"alert_cases: {lab.numel()} labels for {al.n} rows")
+        slot_labels = lab[al.pos.clamp(min=0).long()] if al.n else torch.zeros_like(al.pos)
+    return ops.group_members(model_or_engine.g, al.ids, relations=relations, labels=slot_labels, alerts=al)
+
+
 def predict_proba(test_nodes, model, batch_size: int, labels=None) -> np.ndarray:
     """Test-mode class probabilities [n, 2] of ``test_nodes`` (sigmoid of the gnn logits, utils.py:305), on the host.
     A FusedPCGNN runs its whole-set pass (``infer``: one call, one score pass) - test-mode results do not depend on how the

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .graph import AlertList, Attribution, ChosenLists, NearestExamples, QueryBatch
+from .graph import AlertList, Attribution, CaseList, ChosenLists, NearestExamples, QueryBatch
 
 _p = ops._p
 
@@ -235,6 +235,27 @@ class EvalCalls:
                 status.zero_()
                 raise _lib.PcgnnLibraryError("alerts: a NaN probability" if st & _lib.PCG_ST_EVAL_INPUT else f"device status {st}")
         return AlertList(out_ids, pos, score, n, hits)
+
+    def cases(self, ids=None, k: int = 100, relations=None, chunk: Optional[int] = None, labels=None, query=None) -> CaseList:
+        """The alert list grouped into cases, as ``graph.CaseList``: ``alerts(ids, k, chunk)`` -> pcg_alert_cases on its ids.  Two
+        alerts are linked when they are the same node or when, in a selected relation of the resident graph, either is in the
+        other's CSR row; a case is a connected component, its head the highest-ranked alert in it, and cases are numbered by
+        their heads, so case 0 holds alert 0 - every integer the same on every run, like the alert order itself.  relations:
+        None = all, else a non-empty subset of range(R).  labels (one per requested row, 0 / 1, as for ``alerts``): gathered to
+        the slots; the result holds ``hits`` [C], the positives per case.  The alert list is attached (``.alerts``).
+        Out of scope: ``query=`` batches (their ids are query-local: ValueError), partitioned graphs (``DistributedPCGNN``),
+        2-hop linking, more than 65536 alerts.  Synchronises (the alert list's status word, then the case header)."""
+        if query is not None:
+            raise ValueError("cases: a query batch's alert ids are query-local; grouping them against the resident graph is not supported")
+        ops.relation_mask(self.g, relations)                               # (a bad relation set fails before the inference pass)
+        al = self.alerts(ids, k=k, chunk=chunk)
+        slot_labels = None
+        if labels is not None:
+            lab = self._eval_labels(labels)
+            if lab.numel() != al.n:
+                raise ValueError(f"cases: {lab.numel()} labels for {al.n} rows")
+            slot_labels = lab[al.pos.clamp(min=0).long()] if al.n else torch.zeros_like(al.pos)
+        return ops.group_members(self.g, al.ids, relations=relations, labels=slot_labels, alerts=al)
 
     def _eval_labels(self, labels) -> torch.Tensor:
         if torch.is_tensor(labels):
