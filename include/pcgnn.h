@@ -99,16 +99,22 @@ typedef struct pcg_adam_hyper {
 typedef struct pcg_train_state {
     float *theta, *m, *v;        /* the flat parameter buffer (pcg_dense_param_offset) and Adam's moments, n_params floats each */
     int32_t *step_counter;       /* int32 [1]: Adam's t, counted on the device */
-    uint32_t *sync_words;        /* pcg_sync_words_count() zero-initialised words: [0] arrival ticket (0 between launches), [1] "an
-                                    update is waiting" (1: gradient slabs, 2: activations), [2] its slab / tile count, [3] and
-                                    the words behind it: pcg_choose_gather_planned's in-kernel sort */
+    uint32_t *sync_words;        /* pcg_sync_words_count() words, zero-initialised ONCE by the caller; the launches keep them from
+                                    then on: [0] arrival ticket (0 between launches), [1] "an update is waiting" - the pending
+                                    word - (1: gradient slabs, 2: activations; 0 once it has been applied), [2] its slab / tile
+                                    count, [3] and the words behind it: pcg_choose_gather_planned's in-kernel sort (every launch
+                                    leaves them zero) */
     float *clf_next;             /* [2 * feat_dim + 2] (W row-major, then b): the label classifier one step ahead of theta's copy -
                                     the one the next select launch scores by (pcg_choose_gather_train) */
     float *slabs;                /* [max(pcg_dense_n_tiles(B), 8), n_params]: per-tile gradient slabs, and the classifier step's
-                                    scratch.  NULL in pcg_train_dense: inference (no gradient, no step counted) */
+                                    scratch; no initial contents required (a launch writes the slabs it or its successor reads).
+                                    NULL in pcg_train_dense: inference (no gradient, no step counted) */
     float *acts;                 /* [pcg_wgrad_act_rows(...), act_ld], 16-byte aligned: the transposed activations of
-                                    pcg_train_dense(adam_clf = 3 / 4) that the weight-gradient GEMMs read.  NULL: the gradient-slab paths */
-    float *wg_scratch;           /* pcg_wgrad_scratch_bytes(...) zero-initialised bytes; may be NULL for act_ld <= 1024 */
+                                    pcg_train_dense(adam_clf = 3 / 4) that the weight-gradient GEMMs read; no initial contents
+                                    required (a dense launch writes every column of its batch's tiles, the columns beyond the
+                                    batch as zeros, and the GEMMs read those tiles only).  NULL: the gradient-slab paths */
+    float *wg_scratch;           /* pcg_wgrad_scratch_bytes(...) bytes, zero-initialised ONCE by the caller; every launch leaves
+                                    them so (the tiles' arrival counters); may be NULL for act_ld <= 1024 */
     int32_t emb;                 /* embedding width E */
     int32_t act_ld;              /* floats per row of acts: the largest batch rounded up to 16 */
     float lambda_1;              /* weight of the label classifier's loss term (src/model.py:54-61) */
@@ -120,7 +126,8 @@ typedef struct pcg_train_state {
 typedef struct pcg_select_ws {
     const double *thresholds;    /* HOST double [n_rel] */
     const double *rho;           /* HOST double [n_rel] */
-    void *workspace;             /* the DATA part (pcg_choose_data_bytes) when the batches carry their plan, else the single buffer */
+    void *workspace;             /* the DATA part (pcg_choose_data_bytes; no initial contents required) when the batches carry their
+                                    plan, else the single buffer (zero-initialised ONCE by the caller; every launch leaves it so) */
     uint32_t *status;            /* the device status word */
     int64_t list_capacity;
     int32_t add_self;
@@ -132,7 +139,8 @@ typedef struct pcg_batch {
     const int32_t *ids;          /* int32 [B] centre ids (the `nodes` of the selection entry points) */
     const int32_t *labels;       /* int32 [B] */
     int32_t *cnt;                /* int32 [n_rel * B]: |chosen set|, written by the batch's select launch, read by its dense launch */
-    const void *plan;            /* the batch's plan part (a slot pcg_plan_batches filled); NULL: it lies inside the workspace */
+    const void *plan;            /* the batch's plan part (a slot pcg_plan_batches filled; the slots: zero-initialised ONCE by the
+                                    caller; every launch leaves them so); NULL: it lies inside the workspace */
     int32_t B;
     float inv_count;             /* 1 / global batch size: the weight of a row's loss */
 } pcg_batch;
@@ -218,7 +226,8 @@ int pcg_pos_sort(const pcg_graph_desc *g, const float *s0, uint64_t *keys, void 
  *   cnt     int32 [n_rel * B]             |chosen set|
  *   agg     float [n_rel * B, agg_stride] mean of the chosen rows (cols < feat_dim);
  *           norm = PCG_NORM_COUNT | PCG_NORM_SQRT_COUNT (graphsage.py:224-226)
- *   workspace: pcg_choose_workspace_bytes(g, B, list_capacity) bytes, 256-byte aligned;
+ *   workspace: pcg_choose_workspace_bytes(g, B, list_capacity) bytes, 256-byte aligned,
+ *           zero-initialised ONCE by the caller; every launch leaves it so ("Initial contents" below);
  *           list_capacity (< 2^31 entries) bounds sum over rows of
  *           pcg_sel_capacity_row(...); if a batch needs more, nothing is selected and
  *           PCG_ST_SEL_OVERFLOW is OR-ed into *status (uint32 device word; zero it yourself).
@@ -230,7 +239,19 @@ int pcg_pos_sort(const pcg_graph_desc *g, const float *s0, uint64_t *keys, void 
  * queues, the gather's chunk table - a function of the batch's ids, labels and CSR degrees only) and the DATA part (what a
  * step writes: selection list, per-chunk partial sums, key scratch).  pcg_choose_workspace_bytes = both, the plan part first
  * (the single-buffer layout every entry point without a `plan` argument uses).  pcg_choose_plan_bytes / _data_bytes: the
- * parts on their own, for callers that keep one plan part per batch of an epoch (pcg_plan_batches) and ONE data part. */
+ * parts on their own, for callers that keep one plan part per batch of an epoch (pcg_plan_batches) and ONE data part.
+ *
+ * Initial contents.  The PLAN part - of the single buffer, or a slot of pcg_plan_batches / pcg_plan_epochs - is zero-initialised
+ * ONCE by the caller; every launch leaves it so: the words the launches count from zero (the 768 bytes at its start: the select
+ * launches' queue heads and arrival counters, the plan launch's sequence word) are put back or moved on by the launch that used
+ * them, and everything else in it is written by a plan before anything reads it.  A slot stays valid for as long as the same
+ * bytes are planned for the SAME B.  Before a slot of pcg_plan_batches / pcg_plan_epochs is planned for another B - another
+ * layout over the same bytes, whose look-back tags would sit on whatever the old layout left there - zero it again.  The single
+ * buffer of the entry points without a `plan` argument may change B from call to call without being zeroed again: their plan
+ * launches publish nothing through look-back words, and the 768 bytes do not move with B.
+ * The DATA part: no initial contents required - the selection list, the per-chunk partial sums and the key scratch are written
+ * by the step that reads them - and one data part may serve plan slots of any B, in any order, without being zeroed in between.
+ * (In the single buffer it lies behind the plan part of the call's B.) */
 int64_t pcg_choose_workspace_bytes(const pcg_graph_desc *g, int32_t B, int64_t list_capacity);
 int64_t pcg_choose_plan_bytes(const pcg_graph_desc *g, int32_t B, int64_t list_capacity);
 int64_t pcg_choose_data_bytes(const pcg_graph_desc *g, int32_t B, int64_t list_capacity);
@@ -299,7 +320,9 @@ int pcg_choose_select_planned(const pcg_graph_desc *g, const int32_t *nodes, con
  * labels and the CSR degrees, never on a parameter; the reference does this bookkeeping per batch, src/layers.py:217-219,
  * 246-262).  Batch s = nodes[s * B, min((s + 1) * B, n_total)) (the last one may be shorter) is planned into
  * plans + s * plan_stride (plan_stride >= pcg_choose_plan_bytes(g, B, list_capacity), a multiple of 256); thresholds .. add_self
- * and list_capacity as the *_planned calls that follow will be given.  An overflowing batch sets PCG_ST_SEL_OVERFLOW and
+ * and list_capacity as the *_planned calls that follow will be given.  plans: zero-initialised ONCE by the caller; every launch
+ * leaves it so - for the same (n_total, B); zero the slots again before another B or epoch size is planned into them ("Initial
+ * contents" above: the last, shorter batch's layout moves to another slot).  An overflowing batch sets PCG_ST_SEL_OVERFLOW and
  * selects nothing.  bump_counter (may be NULL): a device uint64 incremented by the launch (the sampler's epoch number -
  * pcg_pick_shuffled with bump = 0 in front of it). */
 int pcg_plan_batches(const pcg_graph_desc *g, const int32_t *nodes, const int32_t *labels, int32_t n_total, int32_t B,
@@ -682,6 +705,8 @@ int pcg_embed_new(const pcg_graph_desc *g, const pcg_graph_desc *q, const float 
  * g->feat_stride only, never on degrees or edge counts.  A row's values are a function of the row alone - its summation order is
  * picked by its own degree and fixed, no float atomics - so they are bit for bit the same whatever n, chunk_rows, the row's
  * position in ids or the call.  The dense part is exact float32 (v_mfma_f32_16x16x4_f32).
+ * workspace: pcg_baseline_workspace_bytes(g, m, chunk_rows) bytes, no initial contents required (every chunk zeroes the long-row
+ * queue's counter itself; the aggregates and the queue are written before they are read).
  *   out_logits [n][2];  out_emb [n][emb] (h) or NULL;  out_agg [n][feat_dim] (a) or NULL.
  * Checks, before any launch: NULL g / g->X / m / W_enc / W_cls / ids / workspace / status / out_logits, n < 0, chunk_rows < 1, rel
  * outside [0, n_rel), a norm other than the two constants, X or workspace not 16-byte aligned, workspace_bytes below

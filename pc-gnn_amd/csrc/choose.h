@@ -51,7 +51,9 @@ struct Workspace {
     unsigned char *plan_totals;   // [blocks of the two-pass plan] PlanTotals
     int4 *chunk_desc;      // [chunk_cap] per gather chunk: {row, first list entry, entries in use (select), chunks of the row}
     float *partial;        // [chunk_cap, feat_stride]
-    uint32_t *row_ticket;  // [rows] arrivals of a multi-chunk row's chunks (gather; reset by the row's last chunk)
+    uint32_t *row_ticket;  // [rows] unused, reserved: no kernel reads or writes it (rows of several chunks are added up from
+                           // `partial` in chunk order, by combine_rows or the dense launch); it keeps its place in the data part so
+                           // that pcg_choose_data_bytes and pcg_choose_workspace_offset stay what they are
     int32_t *list;         // [list_capacity]  chosen ids; -1 = hole
     uint32_t *key_scratch; // [scratch_cap] distance keys of rows too long for the select kernel's LDS: max_degree entries for
                            // each workgroup of select_long_rows

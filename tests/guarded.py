@@ -21,6 +21,7 @@ The pattern is the 32-bit word 0x00000003: read as an int32 it is a small valid 
 stray READ of a band cannot turn into a wild address.  The body of every take starts as ZERO, ``torch.empty`` included: the
 arena never hands a body out twice, and pre-filling ``empty`` bodies with the pattern - which would also find reliance on
 accidentally zero memory - is left out on purpose: a look-back or ticket word a kernel spins on would then start at 3.
+(That is tests/dirty.py's job: ``torch.empty`` bodies and cached workspaces pre-filled, region by region as the header allows.)
 
 A returned tensor has ``storage_offset() == 0`` and a storage of exactly its own bytes (it is re-imported through DLPack):
 ``fused.py`` takes parameter offsets from ``view.storage_offset()`` relative to ``theta``'s own storage.
@@ -177,6 +178,7 @@ def _on_arena(arena: GuardedArena, device) -> bool:
 _PLAIN = {"dtype", "device", "requires_grad", "layout", "pin_memory", "memory_format"}
 
 
+# (tests/dirty.py imports _plain: what goes to the real function here goes to it there too - keep the two in step)
 def _plain(kw: dict, contiguous_input: bool = True) -> bool:
     """only what a plain dense allocation says: anything else (out=, names=, requires_grad, pinned, sparse, channels-last) goes
     to the real function"""
